@@ -2,7 +2,7 @@
 """Headline benchmark: samples/s of forward + log|det J| for the cfg2 / cfg3 flow of BASELINE.json
 (4-layer MAF + RQ-spline(8 bins), 3x1000 atoms = 3000 features, batch 65536, fp32) on N MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over the 65536-sample batch: for each of the 4 MAF layers the masked
@@ -14,15 +14,23 @@ RCCL all-gather of 9 scalars per rank when N > 1).  Inputs are resident in HBM b
 
 N > 1 is BASELINE config 3: the SAME 65536-sample batch sharded by rows over the ranks (8192 per GPU at N = 8,
 ``tfep_amd.distributed.shard_rows``), a full weight replica per rank, no collective on the data path: STRONG scaling
-(``--scaling weak`` gives every rank its own 65536 rows instead).  Rank 0 prints ONE JSON line.  After the timed
-headline region the same process also times (a) the step with the packed weights cached across forwards
-(``cached_repack``; the headline re-packs every step), (b) the step on the exact-fp32 MFMA GEMMs (``exact_fp32``),
-(c) at N = 1 one layer's blocked inverse (8192 rows) and training step (16 384 rows) with their rooflines
-(``other_paths``) and (d), on rank 0 at N = 1, the CPU restatement of the path on the host cores (``cpu_baseline``).
-(``TFEP_BENCH_ARMS=cached,exact,inverse,train,cfg45`` -- a subset -- selects which of the extra arms run, for debugging
-one of them; the default is all of them.)  ``other_paths`` also carries BASELINE configs 4 and 5 at size: the forward of
-the 4-layer circular-spline and Moebius flows on 512 torsions (batch 131 072) and one dynamics + Jacobian-vector-product
-evaluation of the EGNN continuous flow (3 x 256 atoms, batch 16 384), each with its roofline.
+(``--scaling weak`` gives every rank its own 65536 rows instead).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, runs W untimed and exactly K timed steps and prints the headline line (``value``, ``ms_per_step``
+and the fused kernel's roofline from HIP events of those same K steps).  ``--dump-outputs DIR`` then also writes what
+the last timed step returned, as float32 ``.npy`` files: ``log_det_J.npy`` (every row), ``delta_f.npy`` (the estimator,
+shape (1,)) and ``y_sample.npy`` (a fixed, seeded sample of rows of y, at most 48 MB; on rank 0 of N > 1, its own rows).
+The inputs and the weights are seeded, so two runs with the same arguments see the same data.
+
+With ``--full``, after the timed headline region the same process also times (a) the step with the packed weights
+cached across forwards (``cached_repack``; the headline re-packs every step), (b) the step on the exact-fp32 MFMA
+GEMMs (``exact_fp32``), (c) at N = 1 one layer's blocked inverse (8192 rows) and training step (16 384 rows) with their
+rooflines (``other_paths``) and (d), on rank 0 at N = 1, the CPU restatement of the path on the host cores
+(``cpu_baseline``).  (``TFEP_BENCH_ARMS=cached,exact,inverse,train,cfg45`` -- a subset -- selects which of the extra
+arms run, for debugging one of them; the default is all of them; ``--no-extra-arms`` / ``--no-cpu-baseline`` drop
+them from a ``--full`` run.)  ``other_paths`` also carries BASELINE configs 4 and 5 at size: the forward of the 4-layer
+circular-spline and Moebius flows on 512 torsions (batch 131 072) and one dynamics + Jacobian-vector-product evaluation
+of the EGNN continuous flow (3 x 256 atoms, batch 16 384), each with its roofline.
 """
 import argparse
 import json
@@ -283,6 +291,21 @@ def rows_for_rank(batch, rank, world, scaling='strong'):
     return rank * batch, (rank + 1) * batch, world * batch
 
 
+Y_SAMPLE_BYTES = 48 << 20             # --dump-outputs: rows of y kept (with log_det_J, well under 64 MB in all)
+
+
+def dump_outputs(out_dir, y, ldj, delta_f, seed=0):
+    """What one step returned, as float32 .npy files under ``out_dir``: every row of log|det J|, the estimator, and the
+    rows of y at a fixed, seeded sample of row indices (sorted; all rows when they fit in ``Y_SAMPLE_BYTES``)."""
+    os.makedirs(out_dir, exist_ok=True)
+    B, D = y.shape
+    n = min(B, max(1, Y_SAMPLE_BYTES // (4 * D)))
+    rows = torch.arange(B) if n == B else torch.randperm(B, generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    arrays = {'y_sample': y[rows.to(y.device)], 'log_det_J': ldj, 'delta_f': delta_f.reshape(1)}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -298,7 +321,16 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extra-arms', action='store_true',
                     help='skip the cached-repack and exact-fp32 arms and the one-layer inverse / training-step lines')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run the extra arms (cached repack, exact fp32, other paths and '
+                         'configs 4 / 5 with their rooflines) and the CPU baseline; a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step returned to DIR/<name>.npy (float32; y as a seeded row sample)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not args.full:
+        args.no_extra_arms = args.no_cpu_baseline = True
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # not under a launcher: the ranks are CHILD processes of this one, which has not touched the GPU and never will
@@ -404,6 +436,8 @@ def main():
         per_rank_ms = [float(g[1]) for g in gathered]
     else:
         per_rank_tf, per_rank_ms = [achieved], [float(per_rank[1])]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *out)
 
     # ---------------------------------------------------------------- extra arms (same process, same device)
     extra = {}

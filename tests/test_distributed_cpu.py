@@ -303,6 +303,38 @@ def test_bench_spawns_its_own_ranks_when_run_without_a_launcher():
     assert bad.returncode != 0 and not [l for l in bad.stdout.splitlines() if l.startswith('{')]
 
 
+def test_bench_dump_outputs_are_the_last_step_and_repeat(tmp_path):
+    """``bench.py --dump-outputs DIR`` (gloo rehearsal, one process): float32 .npy files of what the last timed step
+    returned, the same arrays from a second run with the same arguments; --steps sets the number of timed steps."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    env['TFEP_BENCH_BACKEND'] = 'gloo'
+    runs = []
+    for i in range(2):
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--features', '66', '--batch', '1000',
+               '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / f'run{i}')]
+        p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, p.stdout
+        res = json.loads(lines[0])
+        assert res['steps'] == 3 and res['warmup'] == 1 and res['ms_per_step'] > 0
+        runs.append({n: np.load(tmp_path / f'run{i}' / f'{n}.npy') for n in ('y_sample', 'log_det_J', 'delta_f')})
+    a, b = runs
+    assert a['y_sample'].shape == (1000, 66) and a['log_det_J'].shape == (1000,) and a['delta_f'].shape == (1,)
+    for n in a:
+        assert a[n].dtype == np.float32 and np.array_equal(a[n], b[n]), n
+    np.testing.assert_allclose(float(a['delta_f'][0]), res['delta_f_estimate'], rtol=1e-6)
+    # the rehearsal's identity flow: y is the bench's own seeded input
+    x = torch.randn(1000, 66, generator=torch.Generator().manual_seed(1234)).clamp_(-4.9, 4.9)
+    np.testing.assert_array_equal(a['y_sample'], x.numpy())
+    bad = subprocess.run(cmd[:-2] + ['--steps', '0'], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert bad.returncode != 0
+
+
 def _overlap_worker(rank, world, port, q):
     """Two stacked linears with gradients above / below the in-place threshold: ``allreduce_gradients`` and the hook-driven
     ``OverlappedGradientSync`` must both give the sum over ranks WITHOUT a staging copy of the large gradients."""

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 B="$GRAFT_REPO_ROOT/bench.py"
 S="$GRAFT_REPO_ROOT/tools/summarize_prof.py"
 C5="$GRAFT_REPO_ROOT/tools/measure_cfg5.py"
-python3 $B --steps 5 --warmup 2 > $OUT/bench_full.json 2> $OUT/bench_full.err
+python3 $B --steps 5 --warmup 2 --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 echo "bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_kt -- python3 $B --steps 2 --warmup 1 --no-cpu-baseline --no-extra-arms > $OUT/bench_under_rocprof.json 2> /tmp/p_kt.err
 python3 $S /tmp/p_kt $OUT/bench

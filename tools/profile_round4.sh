@@ -13,7 +13,7 @@ S="$GRAFT_REPO_ROOT/tools/summarize_prof.py"
 MC="$GRAFT_REPO_ROOT/tools/measure_configs.py"
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has bench; then
-  python3 $B --steps 5 --warmup 2 > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench done rc=$?"
+  python3 $B --steps 5 --warmup 2 --full > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench done rc=$?"
 fi
 if has trace; then
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_kt -- python3 $B --steps 2 --warmup 1 --no-cpu-baseline --no-extra-arms > $OUT/bench_under_rocprof.json 2> /tmp/p_kt.err
