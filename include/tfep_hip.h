@@ -623,6 +623,45 @@ int tfep_periodic_embedding_backward(const float* x, int64_t ldx, const int32_t*
 int tfep_diag_mfma_peak(float* scratch, int blocks, int iters, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* float64 masked linear layers (float64 modules; the float32 entry points above are unchanged)                   */
+/* ------------------------------------------------------------------------- */
+
+/* tfep_masked_weight_prepare in double: same formulas and permutations (no prefix-mask form; the mask, if any, is a
+ * double 0 / 1 array).  The weight norm is summed in double. */
+int tfep_masked_weight_prepare_f64(const double* weight_v, const double* weight_g, const double* mask,
+                                   int out_features, int in_features, const int32_t* row_of_out, const int32_t* col_of_in,
+                                   int clear, double* w_out, int n_rows_padded, int64_t ldw, void* stream);
+/* tfep_mask_k_ranges on a double mask (the same tables: per tile of tile_n packed rows). */
+int tfep_mask_k_ranges_f64(const double* mask, int out_features, int in_features, const int32_t* row_of_out,
+                           const int32_t* col_of_in, int tile_n, int tile_k, int n_tiles, int k_padded,
+                           int32_t* k_ranges, void* stream);
+/*
+ * fp64 masked GEMM on v_mfma_f64_16x16x4_f64 (fp64 products, fp64 sums):
+ *   y[b, n] (+)= act(sum_{k in range(n)} x[b, k] w[n, k] + bias[n]) * elu'(elu_grad_of[b, n])
+ * x (B, ldx) and w (n_rows_w, ldw) zero padded up to k_padded (a multiple of 16) columns, 16-byte aligned rows (even
+ * strides); rows of x past B and of w past n_rows_w read as zero.  k_ranges (or NULL = dense): [begin, end) per tile of
+ * kr_tile_n packed rows (a multiple of 128, e.g. tfep_masked_linear_tile_n()), as tfep_mask_k_ranges(_f64) writes them
+ * with tile_n = kr_tile_n: ceil(N / kr_tile_n) pairs.  act: 0 identity, 1 ELU.
+ * accumulate != 0: y += value.  elu_grad_of (or NULL): the saved ELU output h, the value is multiplied by
+ * (h > 0 ? 1 : h + 1) (same indexing as y, row stride ld_elu_grad_of).
+ */
+int tfep_masked_linear_gemm_f64(const double* x, int64_t ldx, const double* w, int64_t ldw, const double* bias,
+                                const int32_t* k_ranges, int kr_tile_n, double* y, int64_t ldy, int B, int N, int n_rows_w,
+                                int k_padded, int act, int accumulate, const double* elu_grad_of, int64_t ld_elu_grad_of,
+                                void* stream);
+/* tfep_transpose / tfep_column_sums / tfep_weight_norm_backward in double. */
+int tfep_transpose_f64(const double* in, int64_t ld_in, int R, int C, double* out, int64_t ld_out, void* stream);
+int tfep_column_sums_f64(const double* in, int64_t ld, int R, int C, double* out, int accumulate, void* stream);
+int tfep_weight_norm_backward_f64(const double* gw_packed, int64_t ldw, const double* weight_v,
+                                  const double* weight_g, const double* mask, int out_features, int in_features,
+                                  const int32_t* row_of_out, const int32_t* col_of_in,
+                                  double* grad_v, double* grad_g, void* stream);
+/* Diagnostic (not on the path): `iters` x 64 register-only v_mfma_f64_16x16x4_f64 per wave (16 accumulator tiles, as
+ * the fp64 GEMM) on `blocks` workgroups of 256 threads.  scratch: blocks*256 doubles.
+ * flops = blocks * 4 waves * iters * 64 * 2048. */
+int tfep_diag_mfma_f64_peak(double* scratch, int blocks, int iters, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* TFEP reductions (tfep/loss.py, tfep/analysis/estimator.py)                 */
 /* ------------------------------------------------------------------------- */
 

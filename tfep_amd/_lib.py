@@ -212,6 +212,14 @@ _SIGNATURES = {
     'tfep_radial_expansion': (c_int, [_P, c_int64, _P, _P, c_int, c_float, c_int, c_int, _P, _P]),
     'tfep_segment_sum': (c_int, [_P, _P, c_int64, c_int, c_int64, _P, _P]),
     'tfep_ode_axpy': (c_int, [_P, POINTER(c_void_p), POINTER(c_float), c_int, c_int64, _P, _P]),
+    'tfep_masked_weight_prepare_f64': (c_int, [_P, _P, _P, c_int, c_int, _P, _P, c_int, _P, c_int, c_int64, _P]),
+    'tfep_mask_k_ranges_f64': (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    'tfep_masked_linear_gemm_f64': (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int, _P, c_int64, c_int, c_int, c_int,
+                                            c_int, c_int, c_int, _P, c_int64, _P]),
+    'tfep_transpose_f64': (c_int, [_P, c_int64, c_int, c_int, _P, c_int64, _P]),
+    'tfep_column_sums_f64': (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P]),
+    'tfep_weight_norm_backward_f64': (c_int, [_P, c_int64, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    'tfep_diag_mfma_f64_peak': (c_int, [_P, c_int, c_int, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
@@ -298,9 +306,9 @@ def check_device_tensor(t, name, dtype=torch.float32):
     return t
 
 
-def rows(t, name):
-    """A 2-D float32 HIP tensor with unit column stride (copied if needed); returns (tensor, row stride)."""
-    check_device_tensor(t, name)
+def rows(t, name, dtype=torch.float32):
+    """A 2-D float32 (or ``dtype``) HIP tensor with unit column stride (copied if needed); returns (tensor, row stride)."""
+    check_device_tensor(t, name, dtype)
     if t.dim() != 2:
         raise ValueError(f'{name} must be 2-D (batch, features), got shape {tuple(t.shape)}')
     B, D = t.shape

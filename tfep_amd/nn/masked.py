@@ -58,6 +58,16 @@ class MaskedLinearFunc(torch.autograd.Function):
         n_out, k = weight.shape
         tm, tn, tk = ops.tile_sizes()
         k_pad, n_pad = ops.round_up(k, tk), ops.round_up(n_out, tk)
+        if weight.dtype == torch.float64:        # float64 parameters: the fp64-MFMA GEMM, float64 input required
+            w = ops.masked_weight_prepare_f64(weight.detach(), None if weight_g is None else weight_g.detach(), mask,
+                                              n_rows_padded=n_pad, k_padded=k_pad)
+            xp = ops.pad_columns(x2, k_pad, torch.float64)
+            y = ops.masked_linear_f64(xp, w, None if bias is None else bias.detach(), n_out,
+                                      k_ranges=ops.masked_k_ranges_f64(mask, n_pad, k_pad))
+            ctx.save_for_backward(xp, w, weight, mask, weight_g)
+            ctx.has_bias = bias is not None
+            ctx.in_shape = input.shape
+            return y.reshape(*input.shape[:-1], n_out)
         w = ops.masked_weight_prepare(weight.detach(), None if weight_g is None else weight_g.detach(), mask,
                                       n_rows_padded=n_pad, k_padded=k_pad)
         xp = ops.pad_columns(x2, k_pad)
@@ -74,6 +84,13 @@ class MaskedLinearFunc(torch.autograd.Function):
         xp, w, weight, mask, weight_g = ctx.saved_tensors
         n_out, k = weight.shape
         n_pad, k_pad = w.shape
+        if weight.dtype == torch.float64:
+            want_w = ctx.needs_input_grad[1] or (weight_g is not None and ctx.needs_input_grad[4])
+            gi, gv, gg, gb = ops.masked_linear_backward_f64(
+                ops._f64(grad_output, 'grad_output'), xp, w, weight.detach(),
+                None if weight_g is None else weight_g.detach(), mask, n_out, k, want_input=ctx.needs_input_grad[0],
+                want_weight=want_w, want_bias=ctx.has_bias and ctx.needs_input_grad[2])
+            return (None if gi is None else gi.reshape(ctx.in_shape)), gv, gb, None, gg
         tm, tn, tk = ops.tile_sizes()
         f32 = dict(dtype=torch.float32, device=xp.device)
         g2 = grad_output.reshape(-1, n_out).float()
@@ -108,8 +125,14 @@ def masked_linear(input, weight, bias=None, mask=None):
 
     ``input`` may have extra leading dimensions ``(batch, *, in_features)``.
     """
-    ops.check_device_tensor(input, 'input')
+    ops.check_device_tensor(input, 'input', _input_dtype(weight))
     return torch.ops.tfep.masked_linear(input, weight, bias, mask, None)
+
+
+def _input_dtype(weight):
+    """The input dtype a layer with this weight takes: float64 for float64 parameters, float32 otherwise (mixed
+    dtypes are a TypeError, as in ``F.linear``)."""
+    return torch.float64 if weight.dtype == torch.float64 else torch.float32
 
 
 # =============================================================================
@@ -164,7 +187,7 @@ class MaskedLinear(torch.nn.Linear):
         return super().__getattr__(name)
 
     def forward(self, input):
-        ops.check_device_tensor(input, 'input')
+        ops.check_device_tensor(input, 'input', _input_dtype(self.weight_v if self.has_weight_norm else self._parameters['weight']))
         if self.has_weight_norm:
             return torch.ops.tfep.masked_linear(input, self.weight_v, self.bias, self.mask, self.weight_g)
         return torch.ops.tfep.masked_linear(input, self._parameters['weight'], self.bias, self.mask, None)

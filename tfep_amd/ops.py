@@ -176,9 +176,10 @@ def round_up(n, m):
     return (n + m - 1) // m * m
 
 
-def pad_columns(x, k_padded):
-    """Return ``x`` as a (B, k_padded) buffer with zero padding (GEMM operand contract)."""
-    x, _ = rows(x, 'x')
+def pad_columns(x, k_padded, dtype=torch.float32):
+    """Return ``x`` as a (B, k_padded) buffer with zero padding (GEMM operand contract).  ``dtype``: what ``x`` must be
+    (float32, or float64 for the float64 GEMM)."""
+    x, _ = rows(x, 'x', dtype)
     B, K = x.shape
     if K == k_padded and x.stride(0) == K and x.data_ptr() % 16 == 0:
         return x
@@ -193,6 +194,11 @@ def masked_weight_prepare(weight_v, weight_g=None, mask=None, row_of_out=None, c
     prefix mask rows (see ``masked_weight_prepare_split``); ``clear=False``: ``out`` was zeroed once and always holds the
     same layer, so its padding needs no clearing.  With ``col_cut``, ``clear=False`` and ``in_of_col`` (the inverse of
     ``col_of_in``) long rows take the LDS-staged prefix kernel, which writes only the live prefix of each packed row."""
+    if isinstance(weight_v, torch.Tensor) and weight_v.dtype == torch.float64:
+        if col_cut is not None:
+            raise ValueError('masked_weight_prepare: the prefix-mask form (col_cut) is float32-only')
+        return masked_weight_prepare_f64(weight_v, weight_g, mask, row_of_out, col_of_in, n_rows_padded, k_padded, out,
+                                         clear)
     check_device_tensor(weight_v, 'weight')
     N, K = weight_v.shape
     tk = tile_sizes()[2]
@@ -216,6 +222,8 @@ def masked_weight_prepare(weight_v, weight_g=None, mask=None, row_of_out=None, c
 
 
 def mask_k_ranges(mask, tile_n, n_tiles, k_padded, row_of_out=None, col_of_in=None):
+    if isinstance(mask, torch.Tensor) and mask.dtype == torch.float64:
+        return mask_k_ranges_f64(mask, tile_n, n_tiles, k_padded, row_of_out, col_of_in)
     check_device_tensor(mask, 'mask')
     N, K = mask.shape
     out = torch.empty(n_tiles, 2, dtype=torch.int32, device=mask.device)
@@ -286,6 +294,11 @@ def masked_linear_packed(x_padded, w_packed, bias, n_out, k_ranges=None, col_map
                          out_cols=None, tile_order=None):
     """y = act(x W^T + b) on packed operands (reference masked.py:265-277 + made.py:320).  Small products (cfg1-sized
     layers: a handful of 256 x 256 tiles) run on the 32-column tile instead, dense: more workgroups, shorter chains."""
+    if x_padded.dtype == torch.float64:
+        if col_map is not None:
+            raise ValueError('masked_linear_packed: col_map is float32-only')
+        # (tile_order only orders the launch of the float32 kernel; the float64 kernel's tiles all take similar time)
+        return masked_linear_f64(x_padded, w_packed, bias, n_out, k_ranges=k_ranges, act=act, out=out, out_cols=out_cols)
     B = x_padded.shape[0]
     n_rows_w, k_padded = w_packed.shape
     if out is None:
@@ -313,6 +326,154 @@ def gemm_slice(x_padded, w_packed, row0, n_rows, bias, k_ranges, kr_offset, out,
          ctypes.c_void_p(k_ranges.data_ptr() + kr_offset * 2 * 4), None, None,
          ctypes.c_void_p(out.data_ptr() + col0 * esz), out.shape[1], B, n_rows, n_rows, k_padded, int(act),
          _lib.load().tfep_masked_linear_narrow_tile_n(), stream_of(x_padded))
+
+
+# ----------------------------------------------------------------------------- float64 masked linear
+
+_F64 = torch.float64
+
+
+def _f64(t, name):
+    return None if t is None else check_device_tensor(t, name, _F64)
+
+
+def _mask_f64(mask):
+    """The mask as float64 (a 0 / 1 array: exact in any float type; a float32 mask on a float64 layer is converted)."""
+    if mask is None:
+        return None
+    check_device_tensor(mask, 'mask', mask.dtype if mask.is_floating_point() else _F64)
+    return mask.to(_F64).contiguous()
+
+
+def masked_weight_prepare_f64(weight_v, weight_g=None, mask=None, row_of_out=None, col_of_in=None, n_rows_padded=None,
+                              k_padded=None, out=None, clear=True):
+    """``masked_weight_prepare`` for float64 parameters (``tfep_masked_weight_prepare_f64``)."""
+    _f64(weight_v, 'weight')
+    _f64(weight_g, 'weight_g')
+    N, K = weight_v.shape
+    n_rows_padded = N if n_rows_padded is None else n_rows_padded
+    k_padded = round_up(K, tile_sizes()[2]) if k_padded is None else k_padded
+    if out is None:
+        out = torch.empty(n_rows_padded, k_padded, dtype=_F64, device=weight_v.device)
+    _f64(out, 'out')
+    v_c = weight_v.contiguous()
+    g_c = None if weight_g is None else weight_g.contiguous()
+    m_c = _mask_f64(mask)
+    call('tfep_masked_weight_prepare_f64', ptr(v_c), ptr(g_c), ptr(m_c), N, K, ptr(row_of_out), ptr(col_of_in),
+         int(bool(clear)), ptr(out), n_rows_padded, out.shape[1], stream_of(weight_v))
+    return out
+
+
+def mask_k_ranges_f64(mask, tile_n, n_tiles, k_padded, row_of_out=None, col_of_in=None):
+    m_c = _mask_f64(mask)
+    N, K = m_c.shape
+    out = torch.empty(n_tiles, 2, dtype=torch.int32, device=mask.device)
+    call('tfep_mask_k_ranges_f64', ptr(m_c), N, K, ptr(row_of_out), ptr(col_of_in), tile_n, tile_sizes()[2], n_tiles,
+         k_padded, ptr(out), stream_of(mask))
+    return out
+
+
+def masked_linear_f64(x_padded, w_packed, bias, n_out, k_ranges=None, act=0, accumulate=0, elu_grad_of=None, out=None,
+                      out_cols=None, kr_tile_n=None):
+    """``y (+)= act(x W^T + b) [* elu'(elu_grad_of)]`` on packed float64 operands, every product on the fp64-MFMA GEMM
+    (``tfep_masked_linear_gemm_f64``).  ``k_ranges``: per tile of ``kr_tile_n`` rows of ``w_packed`` (default: the wide
+    tile, 256; any multiple of 128), as ``mask_k_ranges(mask, kr_tile_n, ...)`` makes them -- a table of another
+    granularity is an error, not a silently wrong range."""
+    if kr_tile_n is None:
+        kr_tile_n = tile_sizes()[1]
+    if k_ranges is not None and tuple(k_ranges.shape) != ((n_out + kr_tile_n - 1) // kr_tile_n, 2):
+        raise ValueError(f'masked_linear_f64: k_ranges has shape {tuple(k_ranges.shape)}, expected '
+                         f'({(n_out + kr_tile_n - 1) // kr_tile_n}, 2) for {n_out} outputs in tiles of {kr_tile_n}')
+    _f64(x_padded, 'x')
+    _f64(w_packed, 'weight')
+    _f64(bias, 'bias')
+    _f64(elu_grad_of, 'elu_grad_of')
+    B = x_padded.shape[0]
+    n_rows_w, k_padded = w_packed.shape
+    if out is None:
+        out = torch.empty(B, n_out if out_cols is None else out_cols, dtype=_F64, device=x_padded.device)
+    _f64(out, 'out')
+    call('tfep_masked_linear_gemm_f64', ptr(x_padded), x_padded.stride(0) if B > 1 else x_padded.shape[1], ptr(w_packed),
+         k_padded, ptr(bias), ptr(k_ranges), int(kr_tile_n), ptr(out), out.shape[1], B, n_out, n_rows_w, k_padded, int(act),
+         int(accumulate), ptr(elu_grad_of), 0 if elu_grad_of is None else elu_grad_of.shape[1], stream_of(x_padded))
+    return out
+
+
+def masked_k_ranges_f64(mask, n_pad, k_pad):
+    """k-ranges (per wide tile) of a float64 layer's mask for ``masked_linear_f64``, or None without a mask.  Each range
+    bounds the non-zero columns of its 256 rows: a degree-sorted (block-triangular) mask skips its zero k-tiles, any
+    other mask is still exact (the range then covers whatever its rows touch)."""
+    if mask is None:
+        return None
+    tn = tile_sizes()[1]
+    return mask_k_ranges_f64(mask, tn, (n_pad + tn - 1) // tn, k_pad)
+
+
+def transpose_f64(src, n_rows, n_cols, out):
+    """out (cols_pad x rows_pad, zero filled by the caller) <- src[:n_rows, :n_cols]^T (``tfep_transpose_f64``)."""
+    _f64(src, 'src')
+    _f64(out, 'out')
+    call('tfep_transpose_f64', ptr(src), src.shape[1], n_rows, n_cols, ptr(out), out.shape[1], stream_of(src))
+    return out
+
+
+def column_sums_f64(x, n_rows, n_cols, out=None):
+    """out[c] = sum_{r < n_rows} x[r, c] for c < n_cols (``tfep_column_sums_f64``)."""
+    _f64(x, 'x')
+    if out is None:
+        out = torch.empty(n_cols, dtype=_F64, device=x.device)
+    call('tfep_column_sums_f64', ptr(x), x.shape[1], n_rows, n_cols, ptr(out), 0, stream_of(x))
+    return out
+
+
+def weight_norm_backward_f64(gw_packed, weight_v, weight_g=None, mask=None, row_of_out=None, col_of_in=None):
+    """``(grad_v, grad_g)`` of the masked (weight-normalised) parametrisation from the gradient of the packed weight
+    (``tfep_weight_norm_backward_f64``); ``grad_g`` is None without weight norm."""
+    _f64(gw_packed, 'gw_packed')
+    _f64(weight_v, 'weight')
+    _f64(weight_g, 'weight_g')
+    N, K = weight_v.shape
+    v_c = weight_v.contiguous()
+    g_c = None if weight_g is None else weight_g.contiguous()
+    m_c = _mask_f64(mask)
+    grad_v = torch.empty(N, K, dtype=_F64, device=weight_v.device)
+    grad_g = None if weight_g is None else torch.empty(weight_g.shape, dtype=_F64, device=weight_v.device)
+    call('tfep_weight_norm_backward_f64', ptr(gw_packed), gw_packed.shape[1], ptr(v_c), ptr(g_c), ptr(m_c), N, K,
+         ptr(row_of_out), ptr(col_of_in), ptr(grad_v), ptr(grad_g), stream_of(weight_v))
+    return grad_v, grad_g
+
+
+def masked_linear_backward_f64(grad_output, x_padded, w_packed, weight, weight_g, mask, n_out, k, want_input=True,
+                               want_weight=True, want_bias=True):
+    """The analytic backward of a float64 masked linear layer (reference masked.py:220-302, :351-404) from its packed
+    operands: ``(grad_input (B, k), grad_v, grad_g, grad_bias)``, None where not wanted.  Every product runs on the fp64
+    GEMM: ``grad_input = g W`` and ``grad_W = g^T x`` (operands transposed so that both stay K-contiguous)."""
+    n_pad, k_pad = w_packed.shape
+    tk = tile_sizes()[2]
+    f64 = dict(dtype=_F64, device=x_padded.device)
+    g2 = grad_output.reshape(-1, n_out)
+    B = g2.shape[0]
+    gp = pad_columns(g2, n_pad, _F64)
+    grad_input = grad_v = grad_g = grad_bias = None
+    if want_input:
+        wt = transpose_f64(w_packed, n_pad, k_pad, zeros(k_pad, n_pad, **f64))
+        grad_input = masked_linear_f64(gp, wt, None, k_pad, out=torch.empty(B, k_pad, **f64))[:, :k]
+    if want_weight:
+        Bp = round_up(max(B, 1), tk)
+        gT = transpose_f64(gp, B, n_pad, zeros(n_pad, Bp, **f64))
+        xT = transpose_f64(x_padded, B, k_pad, zeros(k_pad, Bp, **f64))
+        gw = masked_linear_f64(gT, xT, None, k_pad, out=torch.empty(n_pad, k_pad, **f64))
+        grad_v, grad_g = weight_norm_backward_f64(gw, weight, weight_g, mask)
+    if want_bias:
+        grad_bias = column_sums_f64(gp, B, n_out)
+    return grad_input, grad_v, grad_g, grad_bias
+
+
+def diag_mfma_f64_peak(blocks, iters, device=None):
+    """Run the register-only f64 MFMA loop (``tfep_diag_mfma_f64_peak``); returns its flop count."""
+    scratch = torch.empty(blocks * 256, dtype=_F64, device=device)
+    call('tfep_diag_mfma_f64_peak', ptr(scratch), int(blocks), int(iters), stream_of(scratch))
+    return blocks * 4 * iters * 64 * 2048
 
 
 # ----------------------------------------------------------------------------- split-precision operands

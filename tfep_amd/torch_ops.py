@@ -212,6 +212,11 @@ def masked_linear(input: Tensor, weight: Tensor, bias: Optional[Tensor], mask: O
         raise RuntimeError(f'masked_linear: weight_g has {weight_g.numel()} entries for {n_out} output features')
     tm, tn, tk = ops.tile_sizes()
     k_pad, n_pad = ops.round_up(k, tk), ops.round_up(n_out, tk)
+    if weight.dtype == torch.float64:        # the fp64-MFMA GEMM (float64 input and parameters, else TypeError)
+        w = ops.masked_weight_prepare_f64(weight, weight_g, mask, n_rows_padded=n_pad, k_padded=k_pad)
+        y = ops.masked_linear_f64(ops.pad_columns(x2, k_pad, torch.float64), w, bias, n_out,
+                                  k_ranges=ops.masked_k_ranges_f64(mask, n_pad, k_pad))
+        return y.reshape(*input.shape[:-1], n_out)
     w = ops.masked_weight_prepare(weight, weight_g, mask, n_rows_padded=n_pad, k_padded=k_pad)
     y = ops.masked_linear_packed(ops.pad_columns(x2, k_pad), w, bias, n_out)
     return y.reshape(*input.shape[:-1], n_out)
@@ -230,6 +235,13 @@ def masked_linear_backward(grad_output: Tensor, input: Tensor, weight: Tensor, m
     n_out, k = weight.shape
     tm, tn, tk = ops.tile_sizes()
     k_pad, n_pad = ops.round_up(k, tk), ops.round_up(n_out, tk)
+    if weight.dtype == torch.float64:
+        w = ops.masked_weight_prepare_f64(weight, weight_g, mask, n_rows_padded=n_pad, k_padded=k_pad)
+        xp = ops.pad_columns(input.reshape(-1, k), k_pad, torch.float64)
+        gi, gv, gg, gb = ops.masked_linear_backward_f64(ops._f64(grad_output, 'grad_output'), xp, w, weight, weight_g,
+                                                         mask, n_out, k)
+        gg = gg.reshape(n_out, 1) if weight_g is not None else weight.new_empty((0,))
+        return gi.reshape(input.shape).contiguous(), gv, gb, gg
     f32 = dict(dtype=torch.float32, device=input.device)
     w = ops.masked_weight_prepare(weight, weight_g, mask, n_rows_padded=n_pad, k_padded=k_pad)
     xp = ops.pad_columns(input.reshape(-1, k), k_pad)
