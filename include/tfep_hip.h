@@ -662,6 +662,67 @@ int tfep_weight_norm_backward_f64(const double* gw_packed, int64_t ldw, const do
 int tfep_diag_mfma_f64_peak(double* scratch, int blocks, int iters, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* float64 transformers (float64 flows; the float32 entry points above are unchanged)                              */
+/* ------------------------------------------------------------------------- */
+
+/* The float32 transformer entry points above on double tensors: x / params / y / gradients are float64, log_det_J is (B,)
+ * float64, layouts and conventions as above.  All arithmetic in fp64 with the library exp / log / log1p / sqrt and IEEE
+ * divisions; one wavefront per sample row, the log-det summed without atomics (results do not depend on the batch). */
+int tfep_affine_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout,
+                            double* y, int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream);
+int tfep_affine_inverse_f64(const double* y, int64_t ldy, const double* params, tfep_param_layout layout,
+                            double* x, int64_t ldx, double* log_det_J, int accumulate, int B, int D, void* stream);
+int tfep_affine_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout,
+                             const double* gy, int64_t ldgy, const double* g_log_det_J,
+                             double* gparams, tfep_param_layout glayout, double* gx, int64_t ldgx,
+                             int B, int D, void* stream);
+/* periodic wrap with Python `%` semantics in fp64: y = (x + sign b) % (upper - lower) + lower on the periodic features. */
+int tfep_volume_preserving_shift_f64(const double* x, int64_t ldx, const double* shift, int64_t ldp,
+                                     const int32_t* periodic_mask, double lower, double upper, int sign,
+                                     double* y, int64_t ldy, int B, int D, void* stream);
+
+/* The spline descriptor with float64 domain arrays and minimum sizes; validated like the float32 one. */
+typedef struct tfep_spline_desc_f64 {
+    const double* x0;
+    const double* xf;
+    const double* y0;
+    const double* yf;
+    int32_t n_bins;                   /* 1 .. 32 */
+    int32_t circular;
+    int32_t identity_boundary_slopes;
+    int32_t learn_lower_bound;
+    int32_t learn_upper_bound;
+    double min_bin_size;
+    double min_slope;
+} tfep_spline_desc_f64;
+
+/* Parameters per feature of a float64 descriptor (or a negative status for an invalid one). */
+int tfep_spline_n_parameters_per_feature_f64(const tfep_spline_desc_f64* desc);
+int tfep_spline_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout,
+                            const tfep_spline_desc_f64* desc, double* y, int64_t ldy,
+                            double* log_det_J, int accumulate, int B, int D, void* stream);
+int tfep_spline_inverse_f64(const double* y, int64_t ldy, const double* params, tfep_param_layout layout,
+                            const tfep_spline_desc_f64* desc, double* x, int64_t ldx,
+                            double* log_det_J, int accumulate, int B, int D, void* stream);
+int tfep_spline_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout,
+                             const tfep_spline_desc_f64* desc, const double* gy, int64_t ldgy,
+                             const double* g_log_det_J, double* gparams, tfep_param_layout glayout,
+                             double* gx, int64_t ldgx, int B, int D, void* stream);
+
+int tfep_periodic_embedding_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
+                                const int32_t* nonperiodic_indices, int n_nonperiodic,
+                                double lower, double upper, double* out, int64_t ldo, int B, void* stream);
+/* gx must be zeroed by the caller where no feature maps (as in the float32 version). */
+int tfep_periodic_embedding_backward_f64(const double* x, int64_t ldx, const int32_t* periodic_indices,
+                                         int n_periodic, const int32_t* nonperiodic_indices, int n_nonperiodic,
+                                         double lower, double upper, const double* gout, int64_t ldg,
+                                         double* gx, int64_t ldgx, int B, void* stream);
+int tfep_gather_columns_f64(const double* src, int64_t lds, const int32_t* idx, int n_idx,
+                            double* dst, int64_t ldd, int B, void* stream);
+int tfep_scatter_columns_f64(const double* src, int64_t lds, const int32_t* idx, int n_idx,
+                             double* dst, int64_t ldd, int B, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* TFEP reductions (tfep/loss.py, tfep/analysis/estimator.py)                 */
 /* ------------------------------------------------------------------------- */
 
@@ -682,6 +743,10 @@ int tfep_tfep_reduce(const float* target_potentials, const float* log_det_J,
                      float kT, int ignore_nan, int N, double* workspace, double* out, void* stream);
 /* Size (in doubles) of the device workspace tfep_tfep_reduce needs for N samples. */
 int tfep_tfep_reduce_workspace_doubles(int N);
+/* The same 9 statistics from float64 inputs, r_i formed in fp64 (same workspace size). */
+int tfep_tfep_reduce_f64(const double* target_potentials, const double* log_det_J,
+                         const double* ref_potentials, const double* log_weights, const double* bias,
+                         double kT, int ignore_nan, int N, double* workspace, double* out, void* stream);
 
 /*
  * Bootstrap distribution of fep_estimator (analysis/bootstrap.py:185-262 with statistic = fep_estimator,

@@ -7,7 +7,7 @@ which is what makes ``tensor.data_ptr()`` and the current stream valid on our si
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
 
 import torch
 
@@ -71,6 +71,13 @@ class SplineDesc(Structure):
                 ('n_bins', c_int32), ('circular', c_int32), ('identity_boundary_slopes', c_int32),
                 ('learn_lower_bound', c_int32), ('learn_upper_bound', c_int32),
                 ('min_bin_size', c_float), ('min_slope', c_float)]
+
+
+class SplineDescF64(Structure):
+    _fields_ = [('x0', c_void_p), ('xf', c_void_p), ('y0', c_void_p), ('yf', c_void_p),
+                ('n_bins', c_int32), ('circular', c_int32), ('identity_boundary_slopes', c_int32),
+                ('learn_lower_bound', c_int32), ('learn_upper_bound', c_int32),
+                ('min_bin_size', c_double), ('min_slope', c_double)]
 
 
 class EgnnLayerParams(Structure):
@@ -220,6 +227,26 @@ _SIGNATURES = {
     'tfep_column_sums_f64': (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P]),
     'tfep_weight_norm_backward_f64': (c_int, [_P, c_int64, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     'tfep_diag_mfma_f64_peak': (c_int, [_P, c_int, c_int, _P]),
+    'tfep_affine_forward_f64': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+    'tfep_affine_inverse_f64': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+    'tfep_affine_backward_f64': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, _P, ParamLayout, _P, c_int64,
+                                         c_int, c_int, _P]),
+    'tfep_volume_preserving_shift_f64': (c_int, [_P, c_int64, _P, c_int64, _P, c_double, c_double, c_int,
+                                                 _P, c_int64, c_int, c_int, _P]),
+    'tfep_spline_n_parameters_per_feature_f64': (c_int, [POINTER(SplineDescF64)]),
+    'tfep_spline_forward_f64': (c_int, [_P, c_int64, _P, ParamLayout, POINTER(SplineDescF64), _P, c_int64,
+                                        _P, c_int, c_int, c_int, _P]),
+    'tfep_spline_inverse_f64': (c_int, [_P, c_int64, _P, ParamLayout, POINTER(SplineDescF64), _P, c_int64,
+                                        _P, c_int, c_int, c_int, _P]),
+    'tfep_spline_backward_f64': (c_int, [_P, c_int64, _P, ParamLayout, POINTER(SplineDescF64), _P, c_int64, _P, _P,
+                                         ParamLayout, _P, c_int64, c_int, c_int, _P]),
+    'tfep_periodic_embedding_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double,
+                                            _P, c_int64, c_int, _P]),
+    'tfep_periodic_embedding_backward_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double, _P, c_int64,
+                                                     _P, c_int64, c_int, _P]),
+    'tfep_gather_columns_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, _P]),
+    'tfep_scatter_columns_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, _P]),
+    'tfep_tfep_reduce_f64': (c_int, [_P, _P, _P, _P, _P, c_double, c_int, c_int, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))

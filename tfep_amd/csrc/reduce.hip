@@ -128,16 +128,18 @@ __device__ inline void block_reduce_and_store(Stats st, double* out) {
     }
 }
 
-__global__ void __launch_bounds__(256) tfep_reduce_partial_kernel(const float* __restrict__ uB,
-                                                                  const float* __restrict__ ldj,
-                                                                  const float* __restrict__ uA,
-                                                                  const float* __restrict__ lw,
-                                                                  const float* __restrict__ bias, double inv_kT,
+// T = float: r in float32 arithmetic, like the reference's float32 tensors; T = double: float64 flows (r in fp64).
+template <typename T>
+__global__ void __launch_bounds__(256) tfep_reduce_partial_kernel(const T* __restrict__ uB,
+                                                                  const T* __restrict__ ldj,
+                                                                  const T* __restrict__ uA,
+                                                                  const T* __restrict__ lw,
+                                                                  const T* __restrict__ bias, double inv_kT,
                                                                   int ignore_nan, int N, double* __restrict__ partial) {
     Stats st = stats_identity();
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-        // float32 arithmetic for r, like the reference tensors (loss.py:125-129)
-        float rf = uB[i];
+        // arithmetic for r in the type of the inputs, like the reference tensors (loss.py:125-129)
+        T rf = uB[i];
         if (ldj) rf = rf - ldj[i];
         if (uA) rf = rf - uA[i];
         const double r = (double)rf;
@@ -290,10 +292,26 @@ int tfep_tfep_reduce(const float* target_potentials, const float* log_det_J, con
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
     hipStream_t s = (hipStream_t)stream;
-    tfep_reduce_partial_kernel<<<blocks, 256, 0, s>>>(target_potentials, log_det_J, ref_potentials, log_weights, bias,
-                                                      1.0 / (double)kT, ignore_nan, N, workspace);
+    tfep_reduce_partial_kernel<float><<<blocks, 256, 0, s>>>(target_potentials, log_det_J, ref_potentials, log_weights, bias,
+                                                             1.0 / (double)kT, ignore_nan, N, workspace);
     tfep_reduce_final_kernel<<<1, 256, 0, s>>>(workspace, blocks, out);
     return check_launch("tfep_reduce");
+}
+
+int tfep_tfep_reduce_f64(const double* target_potentials, const double* log_det_J, const double* ref_potentials,
+                         const double* log_weights, const double* bias, double kT, int ignore_nan, int N,
+                         double* workspace, double* out, void* stream) {
+    TFEP_REQUIRE(target_potentials && out && workspace, "tfep_reduce_f64: NULL pointer");
+    TFEP_REQUIRE(N >= 0, "tfep_reduce_f64: negative N");
+    TFEP_REQUIRE(kT > 0.0, "tfep_reduce_f64: kT must be positive");
+    int blocks = (N + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    if (blocks < 1) blocks = 1;
+    hipStream_t s = (hipStream_t)stream;
+    tfep_reduce_partial_kernel<double><<<blocks, 256, 0, s>>>(target_potentials, log_det_J, ref_potentials, log_weights,
+                                                              bias, 1.0 / kT, ignore_nan, N, workspace);
+    tfep_reduce_final_kernel<<<1, 256, 0, s>>>(workspace, blocks, out);
+    return check_launch("tfep_reduce_f64");
 }
 
 int tfep_bootstrap_fep(const float* work, const float* bias, const int64_t* indices, const float* weights,

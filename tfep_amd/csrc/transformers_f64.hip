@@ -1,0 +1,719 @@
+// float64 transformer kernels: affine, volume-preserving shift, RQ spline (forward, inverse and VJPs), periodic embedding and
+// column gather / scatter on double tensors -- the twins of transformers.hip / backward.hip for float64 flows.  Same launch
+// shape: one wavefront per sample row, its 64 lanes walk the features with unit stride, the log-derivative is summed with the
+// wave butterfly (no atomics: bit-reproducible and independent of the batch the row sits in).
+//
+// Numerics: everything in fp64 from double parameters, with the library exp / log / log1p / sqrt and IEEE divisions (no
+// polynomial exponentials, no hardware-seeded reciprocals: the float32 kernels' shortcuts are accurate to ~1e-11, which is
+// coarse next to the float64 reference).  The spline follows the reference's rules: strict '>' in the bin search, linear
+// continuation along the boundary slope outside the domain (transformers/spline.py:567-650).
+#include "common.h"
+
+namespace tfep {
+namespace {
+
+constexpr int RPB = 4;   // rows (waves) per block of 256 threads
+
+inline unsigned row_blocks64(int B) { return (unsigned)((B + RPB - 1) / RPB); }
+
+__device__ inline void store_ldj64(double* ldj, int b, double total, int accumulate) {
+    if ((threadIdx.x & 63) == 0) ldj[b] = accumulate ? ldj[b] + total : total;
+}
+
+// ---------------------------------------------------------------- affine (affine.py:321-323, :361-363)
+template <bool INVERSE>
+__global__ void __launch_bounds__(256) affine64_kernel(const double* __restrict__ x, int64_t ldx,
+                                                       const double* __restrict__ params, tfep_param_layout L,
+                                                       double* __restrict__ y, int64_t ldy, double* __restrict__ ldj,
+                                                       int accumulate, int B, int D) {
+    const int b = blockIdx.x * RPB + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const double* xr = x + (int64_t)b * ldx;
+    const double* pr = params + (int64_t)b * L.ld;
+    double* yr = y + (int64_t)b * ldy;
+    double acc = 0.0;
+    for (int f = lane; f < D; f += 64) {
+        const double shift = pr[f * L.stride_f];
+        const double ls = pr[L.stride_p + f * L.stride_f];
+        const double v = xr[f];
+        yr[f] = INVERSE ? (v - shift) * exp(-ls) : v * exp(ls) + shift;
+        acc += ls;
+    }
+    acc = wave_sum(acc);
+    if (ldj) store_ldj64(ldj, b, INVERSE ? -acc : acc, accumulate);
+}
+
+__global__ void __launch_bounds__(256) affine64_backward_kernel(const double* __restrict__ x, int64_t ldx,
+                                                                const double* __restrict__ params, tfep_param_layout L,
+                                                                const double* __restrict__ gy, int64_t ldgy,
+                                                                const double* __restrict__ gldj,
+                                                                double* __restrict__ gparams, tfep_param_layout GL,
+                                                                double* __restrict__ gx, int64_t ldgx, int B, int D) {
+    const int b = blockIdx.x * RPB + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const double gl = gldj ? gldj[b] : 0.0;
+    for (int f = lane; f < D; f += 64) {
+        const double ls = params[(int64_t)b * L.ld + L.stride_p + f * L.stride_f];
+        const double g = gy[(int64_t)b * ldgy + f];
+        const double e = exp(ls);
+        const double xv = x[(int64_t)b * ldx + f];
+        gparams[(int64_t)b * GL.ld + f * GL.stride_f] = g;                                   // d/d shift
+        gparams[(int64_t)b * GL.ld + GL.stride_p + f * GL.stride_f] = g * xv * e + gl;       // d/d log_scale
+        gx[(int64_t)b * ldgx + f] = g * e;
+    }
+}
+
+// ---------------------------------------------------------------- volume preserving shift (affine.py:366-456)
+__global__ void __launch_bounds__(256) volpres64_kernel(const double* __restrict__ x, int64_t ldx,
+                                                        const double* __restrict__ shift, int64_t ldp,
+                                                        const int32_t* __restrict__ periodic, double lower, double upper,
+                                                        double sign, double* __restrict__ y, int64_t ldy, int B, int D) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)B * D) return;
+    const int b = (int)(i / D), f = (int)(i % D);
+    double v = x[(int64_t)b * ldx + f] + sign * shift[(int64_t)b * ldp + f];
+    if (periodic && periodic[f]) v = py_mod(v, upper - lower) + lower;      // Python `%`, then + lower (affine.py:409, :454)
+    y[(int64_t)b * ldy + f] = v;
+}
+
+// ---------------------------------------------------------------- RQ spline (spline.py)
+struct Spline64 {
+    const double *x0, *xf, *y0, *yf;
+    int K, P;
+    bool circular, identity, learn_lower, learn_upper;
+    double min_bin, min_slope, slope_offset;   // slope_offset = log(exp(1 - min_slope) - 1), spline.py:414
+};
+
+// Parameter position of the raw slope of knot j (spline.py:359-380); -1: the constant 0 of an identity boundary slope.
+__host__ __device__ inline int slope_param64(int j, int K, bool circular, bool identity) {
+    if (identity) {
+        if (j == 0 || j == K) return -1;
+        return 2 * K + j - 1;
+    }
+    if (circular && j == K) return 2 * K;
+    return 2 * K + j;
+}
+
+__host__ __device__ inline int n_params64(int K, bool circular, bool identity, bool ll, bool lu) {
+    int n = 3 * K + 1;          // spline.py:165-182
+    if (ll) n += 1;
+    if (lu) n += 1;
+    if (identity) n -= circular ? 1 : 2;
+    return n;
+}
+
+// torch softplus (beta 1, threshold 20) and its derivative
+__device__ inline double softplus64(double z) { return z > 20.0 ? z : log1p(exp(z)); }
+__device__ inline double softplus64_grad(double z) {
+    if (z > 20.0) return 1.0;
+    if (z >= 0.0) return 1.0 / (1.0 + exp(-z));
+    const double e = exp(z);
+    return e / (1.0 + e);
+}
+
+// The P parameters of one element, expanded: K raw widths, K raw heights, K + 1 raw knot slopes, `last` / `last2` =
+// parameters P - 1 / P - 2 (circular shift; log-scale and shift of a learnable domain), 0 where unused.
+template <int KMAX>
+__device__ inline void load_element64(const double* pf, int64_t sp, const Spline64& a, double (&w)[KMAX],
+                                      double (&h)[KMAX], double (&sraw)[KMAX + 1], double& last, double& last2) {
+    const int K = a.K;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        w[k] = 0.0;
+        h[k] = 0.0;
+        if (k < K) {
+            w[k] = pf[k * sp];
+            h[k] = pf[(K + k) * sp];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j <= KMAX; ++j) {
+        sraw[j] = 0.0;
+        if (j <= K) {
+            const int pi = slope_param64(j, K, a.circular, a.identity);
+            if (pi >= 0) sraw[j] = pf[pi * sp];
+        }
+    }
+    last = (a.circular || a.learn_lower || a.learn_upper) ? pf[(a.P - 1) * sp] : 0.0;
+    last2 = (a.learn_lower && a.learn_upper) ? pf[(a.P - 2) * sp] : 0.0;
+}
+
+// Domain of the element after the learnable bounds (spline.py:384-410).
+__device__ inline void domain64(const Spline64& a, double last, double last2, double x0f, double xff, double y0f, double yff,
+                                double& x0, double& y0, double& W, double& H) {
+    const double mi = a.K * a.min_bin;
+    x0 = x0f;
+    y0 = y0f;
+    W = xff - x0f - mi;
+    H = yff - y0f - mi;
+    if (a.learn_lower || a.learn_upper) {
+        const double scale = exp(last);
+        W *= scale;
+        H *= scale;
+        if (a.learn_lower && a.learn_upper) {
+            x0 += last2;
+            y0 += last2;
+        } else if (a.learn_lower) {
+            x0 = xff - W - mi;
+            y0 = yff - H - mi;
+        }
+    }
+}
+
+// softmax in place: p[k] = exp(u[k] - max) / sum (spline.py:394-395)
+template <int KMAX>
+__device__ inline void softmax64(double (&u)[KMAX], int K) {
+    double m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+        if (k < K) m = fmax(m, u[k]);
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        u[k] = k < K ? exp(u[k] - m) : 0.0;
+        s += u[k];
+    }
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) u[k] = u[k] / s;
+}
+
+// One element of the forward (INVERSE = false) or inverse map; w / h are overwritten by their softmax.  Returns the mapped
+// value; *logd receives log(dy/dx) of the FORWARD map at the point (the caller negates it for the inverse).
+template <int KMAX, bool INVERSE>
+__device__ inline double rq_spline_element_f64(double (&w)[KMAX], double (&h)[KMAX], const double (&sraw)[KMAX + 1],
+                                               double last, double last2, const Spline64& a, double x0f, double xff,
+                                               double y0f, double yff, double vin, double* logd) {
+    const int K = a.K;
+    const double mb = a.min_bin;
+    double x0, y0, W, H;
+    domain64(a, last, last2, x0f, xff, y0f, yff, x0, y0, W, H);
+    double v = vin;
+    if (a.circular && !INVERSE) v = py_mod(v - x0 + last, xff - x0) + x0;      // spline.py:236-238
+    softmax64(w, K);
+    softmax64(h, K);
+
+    // bin search: strict '>' (spline.py:622-625); v <= first knot -> lower tail, past the last knot -> upper tail
+    double kx = x0, ky = y0, bw = 0.0, bh = 0.0, rs0 = sraw[0], rs1 = sraw[0], rs_last = sraw[0];
+    bool found = false;
+    const bool lower_tail = !(v > (INVERSE ? y0 : x0));
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        if (k < K) {
+            const double wk = w[k] * W + mb;
+            const double hk = h[k] * H + mb;
+            if (!found) {
+                const double upper = INVERSE ? ky + hk : kx + wk;
+                if (v > upper) {
+                    kx += wk;
+                    ky += hk;
+                } else {
+                    found = true;
+                    bw = wk;
+                    bh = hk;
+                    rs0 = sraw[k];
+                    rs1 = sraw[k + 1];
+                }
+            }
+            if (k == K - 1) rs_last = sraw[k + 1];
+        }
+    }
+
+    double out, ld;
+    if (lower_tail || !found) {
+        // linear continuation along the boundary slope (the reference's sentinel knots, spline.py:599-614)
+        const double d = softplus64((lower_tail ? sraw[0] : rs_last) + a.slope_offset) + a.min_slope;
+        const double bx = lower_tail ? x0 : kx, by = lower_tail ? y0 : ky;
+        out = INVERSE ? bx + (v - by) / d : by + d * (v - bx);
+        ld = log(d);
+    } else {
+        const double dk = softplus64(rs0 + a.slope_offset) + a.min_slope;
+        const double dk1 = softplus64(rs1 + a.slope_offset) + a.min_slope;
+        const double s = bh / bw;                                  // spline.py:643
+        const double t = dk1 + dk - 2.0 * s;
+        double eps;
+        if (INVERSE) {                                             // spline.py:521-536
+            const double ym = v - ky;
+            const double qa = bh * (s - dk) + ym * t;
+            const double qb = bh * dk - ym * t;
+            const double qc = -s * ym;
+            eps = 2.0 * qc / (-qb - sqrt(qb * qb - 4.0 * qa * qc));
+            out = eps * bw + kx;
+        } else {                                                   // spline.py:485-494
+            eps = (v - kx) / bw;
+            const double e1 = eps * (1.0 - eps);
+            out = ky + bh * (s * eps * eps + dk * e1) / (s + t * e1);
+        }
+        const double e1 = eps * (1.0 - eps);                       // spline.py:556-558
+        const double om = 1.0 - eps;
+        const double num = s * s * (dk1 * eps * eps + 2.0 * s * e1 + dk * om * om);
+        const double den = s + t * e1;
+        ld = log(num / (den * den));
+    }
+    if (a.circular && INVERSE) out = py_mod(out - x0 - last, xff - x0) + x0;   // spline.py:257-259
+    *logd = ld;
+    return out;
+}
+
+template <int KMAX, bool INVERSE>
+__global__ void __launch_bounds__(256) spline64_kernel(const double* __restrict__ x, int64_t ldx,
+                                                       const double* __restrict__ params, tfep_param_layout L, Spline64 a,
+                                                       double* __restrict__ y, int64_t ldy, double* __restrict__ ldj,
+                                                       int accumulate, int B, int D) {
+    const int b = blockIdx.x * RPB + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const double* xr = x + (int64_t)b * ldx;
+    const double* pr = params + (int64_t)b * L.ld;
+    double* yr = y + (int64_t)b * ldy;
+    double acc = 0.0;
+    for (int f = lane; f < D; f += 64) {
+        double w[KMAX], h[KMAX], sraw[KMAX + 1], last, last2, ld;
+        load_element64<KMAX>(pr + f * L.stride_f, L.stride_p, a, w, h, sraw, last, last2);
+        yr[f] = rq_spline_element_f64<KMAX, INVERSE>(w, h, sraw, last, last2, a, a.x0[f], a.xf[f], a.y0[f], a.yf[f], xr[f],
+                                                     &ld);
+        acc += ld;
+    }
+    acc = wave_sum(acc);
+    if (ldj) store_ldj64(ldj, b, INVERSE ? -acc : acc, accumulate);
+}
+
+// Reverse mode through rq_spline_element_f64<KMAX, false> (FORWARD map), every layout.  The same derivation as the float32
+// VJP (backward.hip: rq_spline_backward) in IEEE fp64 arithmetic.  Writes the gradients of the raw widths / heights / knot
+// slopes, of `last` / `last2` and of the input.
+template <int KMAX>
+__device__ inline void rq_spline_backward_f64(double (&pw)[KMAX], double (&ph)[KMAX], const double (&sraw)[KMAX + 1],
+                                              double last, double last2, const Spline64& a, double x0f, double xff,
+                                              double y0f, double yff, double vin, double gy, double gl,
+                                              double (&guw)[KMAX], double (&guh)[KMAX], double (&gus)[KMAX + 1],
+                                              double* glast, double* glast2, double* gxin) {
+    const int K = a.K;
+    const double mb = a.min_bin;
+    const bool learn = a.learn_lower || a.learn_upper;
+    double x0, y0, W, H;
+    domain64(a, last, last2, x0f, xff, y0f, yff, x0, y0, W, H);
+    double gx0 = 0.0, gy0 = 0.0, gWt = 0.0, gHt = 0.0;   // grads w.r.t. x0', y0' and direct terms of W, H
+    double v = vin;
+    if (a.circular) v = py_mod(v - x0 + last, xff - x0) + x0;
+    softmax64(pw, K);
+    softmax64(ph, K);
+
+    double kx = x0, ky = y0, bw = 0.0, bh = 0.0;
+    int kbin = -1;
+    bool found = false;
+    const bool lower_tail = !(v > x0);
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+        if (k < K && !found) {
+            const double wk = pw[k] * W + mb, hk = ph[k] * H + mb;
+            if (v > kx + wk) {
+                kx += wk;
+                ky += hk;
+            } else {
+                found = true;
+                bw = wk;
+                bh = hk;
+                kbin = k;
+            }
+        }
+
+    double gw[KMAX], gh[KMAX], gd[KMAX + 1];      // grads w.r.t. bin widths, heights, knot slopes (values)
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        gw[k] = 0.0;
+        gh[k] = 0.0;
+        gd[k] = 0.0;
+    }
+    gd[KMAX] = 0.0;
+    double gv;
+    int ja = -1, jb2 = -1;                         // the (at most two) knots whose slope enters the element
+    double sga = 0.0, sgb = 0.0;                   // and the derivatives of their softplus
+    if (lower_tail || !found) {
+        // y = y_b + d (v - x_b), ld = log d
+        double rs = sraw[0];
+        int jb = 0;
+        if (!lower_tail) {
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k)
+                if (k == K - 1) rs = sraw[k + 1];
+            jb = K;
+        }
+        const double d = softplus64(rs + a.slope_offset) + a.min_slope;
+        const double bx = lower_tail ? x0 : kx;
+        const double gdb = gy * (v - bx) + gl / d;
+        ja = jb;
+        sga = softplus64_grad(rs + a.slope_offset);
+        // boundary knot: (x0', y0') below, (x0' + W + K mb, y0' + H + K mb) above
+        gx0 = -gy * d;
+        gy0 = gy;
+        if (!lower_tail) {
+            gWt = -gy * d;
+            gHt = gy;
+        }
+#pragma unroll
+        for (int j = 0; j <= KMAX; ++j)
+            if (j == jb) gd[j] = gdb;
+        gv = gy * d;
+    } else {
+        double rs0 = sraw[0], rs1 = sraw[0];
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k == kbin) {
+                rs0 = sraw[k];
+                rs1 = sraw[k + 1];
+            }
+        const double dk = softplus64(rs0 + a.slope_offset) + a.min_slope;
+        const double dk1 = softplus64(rs1 + a.slope_offset) + a.min_slope;
+        ja = kbin;
+        jb2 = kbin + 1;
+        sga = softplus64_grad(rs0 + a.slope_offset);
+        sgb = softplus64_grad(rs1 + a.slope_offset);
+        const double s = bh / bw, t = dk1 + dk - 2.0 * s;
+        const double eps = (v - kx) / bw, om = 1.0 - eps, e1 = eps * om;
+        const double A = s * eps * eps + dk * e1;
+        const double Dn = s + t * e1;
+        const double Q = dk1 * eps * eps + 2.0 * s * e1 + dk * om * om;
+        const double dy_dA = bh / Dn, dy_dDn = -bh * A / (Dn * Dn);
+        const double gs = gy * (dy_dA * eps * eps + dy_dDn * (1.0 - 2.0 * e1)) +
+                          gl * (2.0 / s + 2.0 * e1 / Q - 2.0 * (1.0 - 2.0 * e1) / Dn);
+        const double geps = gy * (dy_dA * (2.0 * s * eps + dk * (1.0 - 2.0 * eps)) + dy_dDn * t * (1.0 - 2.0 * eps)) +
+                            gl * ((2.0 * dk1 * eps + 2.0 * s * (1.0 - 2.0 * eps) - 2.0 * dk * om) / Q -
+                                  2.0 * t * (1.0 - 2.0 * eps) / Dn);
+        const double gdk = gy * (dy_dA * e1 + dy_dDn * e1) + gl * (om * om / Q - 2.0 * e1 / Dn);
+        const double gdk1 = gy * (dy_dDn * e1) + gl * (eps * eps / Q - 2.0 * e1 / Dn);
+        const double gh_bin = gy * A / Dn + gs / bw;
+        const double gw_bin = -gs * s / bw - geps * eps / bw;
+        const double gxk = -geps / bw;
+        gv = geps / bw;
+        gx0 = gxk;
+        gy0 = gy;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            if (k < kbin) {
+                gw[k] = gxk;
+                gh[k] = gy;
+            } else if (k == kbin) {
+                gw[k] = gw_bin;
+                gh[k] = gh_bin;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j <= KMAX; ++j) {
+            if (j == kbin) gd[j] = gdk;
+            if (j == kbin + 1) gd[j] = gdk1;
+        }
+    }
+
+    // softmax backward: w_k = p_k W + mb
+    double dotw = 0.0, doth = 0.0;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        dotw += pw[k] * gw[k];
+        doth += ph[k] * gh[k];
+    }
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        guw[k] = pw[k] * W * (gw[k] - dotw);
+        guh[k] = ph[k] * H * (gh[k] - doth);
+    }
+    // softplus backward
+#pragma unroll
+    for (int j = 0; j <= KMAX; ++j) gus[j] = j == ja ? gd[j] * sga : (j == jb2 ? gd[j] * sgb : 0.0);
+    *glast = a.circular ? gv : 0.0;
+    *glast2 = 0.0;
+    if (learn) {
+        // W = W0 e^last, H = H0 e^last; w_k = p_k W + mb
+        double gW = dotw + gWt, gH = doth + gHt;
+        if (a.learn_lower && a.learn_upper) {
+            *glast2 = gx0 + gy0;
+        } else if (a.learn_lower) {      // x0' = xf - W - K mb, y0' = yf - H - K mb
+            gW -= gx0;
+            gH -= gy0;
+        }
+        *glast = gW * W + gH * H;
+    }
+    *gxin = gv;
+}
+
+template <int KMAX>
+__global__ void __launch_bounds__(256) spline64_backward_kernel(const double* __restrict__ x, int64_t ldx,
+                                                                const double* __restrict__ params, tfep_param_layout L,
+                                                                Spline64 a, const double* __restrict__ gy, int64_t ldgy,
+                                                                const double* __restrict__ gldj,
+                                                                double* __restrict__ gparams, tfep_param_layout GL,
+                                                                double* __restrict__ gx, int64_t ldgx, int B, int D) {
+    const int b = blockIdx.x * RPB + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const int K = a.K, P = a.P;
+    const double gl = gldj ? gldj[b] : 0.0;
+    for (int f = lane; f < D; f += 64) {
+        const double* pf = params + (int64_t)b * L.ld + f * L.stride_f;
+        double* gp = gparams + (int64_t)b * GL.ld + f * GL.stride_f;
+        const int64_t gsp = GL.stride_p;
+        double w[KMAX], h[KMAX], sraw[KMAX + 1], last, last2;
+        load_element64<KMAX>(pf, L.stride_p, a, w, h, sraw, last, last2);
+        double guw[KMAX], guh[KMAX], gus[KMAX + 1], glast, glast2, gxin;
+        rq_spline_backward_f64<KMAX>(w, h, sraw, last, last2, a, a.x0[f], a.xf[f], a.y0[f], a.yf[f], x[(int64_t)b * ldx + f],
+                                     gy[(int64_t)b * ldgy + f], gl, guw, guh, gus, &glast, &glast2, &gxin);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                gp[k * gsp] = guw[k];
+                gp[(K + k) * gsp] = guh[k];
+            }
+        // knot K of a circular spline shares the parameter of knot 0; identity boundary slopes have no parameter
+        double g0 = gus[0];
+#pragma unroll
+        for (int j = 0; j <= KMAX; ++j)
+            if (j == K && a.circular && !a.identity) g0 += gus[j];
+#pragma unroll
+        for (int j = 0; j <= KMAX; ++j) {
+            if (j > K) continue;
+            if (a.circular && !a.identity && j == K) continue;
+            const int pi = slope_param64(j, K, a.circular, a.identity);
+            if (pi >= 0) gp[pi * gsp] = j == 0 ? g0 : gus[j];
+        }
+        if (a.circular || a.learn_lower || a.learn_upper) gp[(P - 1) * gsp] = glast;
+        if (a.learn_lower && a.learn_upper) gp[(P - 2) * gsp] = glast2;
+        gx[(int64_t)b * ldgx + f] = gxin;
+    }
+}
+
+// ---------------------------------------------------------------- periodic embedding (mafembed.py:112-145)
+// out = [x_non..., cos t, sin t, ...], t = (x - lower) * scale; backward: gx[p] = (-sin t g_cos + cos t g_sin) * scale
+template <bool BACKWARD>
+__global__ void __launch_bounds__(256) periodic_embedding64_kernel(const double* __restrict__ x, int64_t ldx,
+                                                                   const int32_t* __restrict__ pidx, int n_per,
+                                                                   const int32_t* __restrict__ nidx, int n_non,
+                                                                   double lower, double scale,
+                                                                   const double* __restrict__ gout, int64_t ldg,
+                                                                   double* __restrict__ out, int64_t ldo, int B) {
+    const int n_src = n_non + n_per;     // one thread per (row, source feature)
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)B * n_src) return;
+    const int b = (int)(i / n_src), j = (int)(i % n_src);
+    if (j < n_non) {
+        if (BACKWARD)
+            out[(int64_t)b * ldo + nidx[j]] = gout[(int64_t)b * ldg + j];
+        else
+            out[(int64_t)b * ldo + j] = x[(int64_t)b * ldx + nidx[j]];
+    } else {
+        const int q = j - n_non;
+        const double t = (x[(int64_t)b * ldx + pidx[q]] - lower) * scale;
+        double s, c;
+        sincos(t, &s, &c);
+        if (BACKWARD) {
+            const double gc = gout[(int64_t)b * ldg + n_non + 2 * q], gs = gout[(int64_t)b * ldg + n_non + 2 * q + 1];
+            out[(int64_t)b * ldo + pidx[q]] = (-s * gc + c * gs) * scale;
+        } else {
+            out[(int64_t)b * ldo + n_non + 2 * q] = c;
+            out[(int64_t)b * ldo + n_non + 2 * q + 1] = s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- column gather / scatter
+template <bool SCATTER>
+__global__ void __launch_bounds__(256) columns64_kernel(const double* __restrict__ src, int64_t lds,
+                                                        const int32_t* __restrict__ idx, int n_idx,
+                                                        double* __restrict__ dst, int64_t ldd, int B) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)B * n_idx) return;
+    const int b = (int)(i / n_idx), j = (int)(i % n_idx);
+    if (SCATTER)
+        dst[(int64_t)b * ldd + idx[j]] = src[(int64_t)b * lds + j];
+    else
+        dst[(int64_t)b * ldd + j] = src[(int64_t)b * lds + idx[j]];
+}
+
+// Host-side view and validation of a tfep_spline_desc_f64 (the rules of make_spline_args).
+int make_spline64(const tfep_spline_desc_f64* d, Spline64* a) {
+    TFEP_REQUIRE(d != nullptr, "spline descriptor is NULL");
+    TFEP_REQUIRE(d->x0 && d->xf && d->y0 && d->yf, "spline descriptor: x0/xf/y0/yf must be non-NULL");
+    TFEP_REQUIRE(d->n_bins >= 1 && d->n_bins <= 32, "spline: n_bins=%d unsupported (1..32)", d->n_bins);
+    TFEP_REQUIRE(!(d->circular && (d->learn_lower_bound || d->learn_upper_bound)),
+                 "Cannot instantiate a circular spline with learnable limits.");
+    TFEP_REQUIRE(d->min_bin_size > 0.0, "The minimum bin size should be positive.");
+    TFEP_REQUIRE(d->min_slope > 0.0 && d->min_slope < 1.0, "The minimum slope should be between 0 and 1.");
+    a->x0 = d->x0;
+    a->xf = d->xf;
+    a->y0 = d->y0;
+    a->yf = d->yf;
+    a->K = d->n_bins;
+    a->circular = d->circular != 0;
+    a->identity = d->identity_boundary_slopes != 0;
+    a->learn_lower = d->learn_lower_bound != 0;
+    a->learn_upper = d->learn_upper_bound != 0;
+    a->min_bin = d->min_bin_size;
+    a->min_slope = d->min_slope;
+    a->slope_offset = log(exp(1.0 - d->min_slope) - 1.0);
+    a->P = n_params64(a->K, a->circular, a->identity, a->learn_lower, a->learn_upper);
+    return TFEP_OK;
+}
+
+template <bool INVERSE>
+int launch_spline64(const double* x, int64_t ldx, const double* params, tfep_param_layout L, const tfep_spline_desc_f64* desc,
+                    double* y, int64_t ldy, double* ldj, int accumulate, int B, int D, void* stream) {
+    Spline64 a;
+    int rc = make_spline64(desc, &a);
+    if (rc) return rc;
+    TFEP_REQUIRE(B >= 0 && D >= 0, "spline_f64: negative size");
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && y, "spline_f64: x/params/y must be non-NULL");
+    hipStream_t s = (hipStream_t)stream;
+    if (a.K <= 8)
+        spline64_kernel<8, INVERSE><<<row_blocks64(B), 256, 0, s>>>(x, ldx, params, L, a, y, ldy, ldj, accumulate, B, D);
+    else if (a.K <= 16)
+        spline64_kernel<16, INVERSE><<<row_blocks64(B), 256, 0, s>>>(x, ldx, params, L, a, y, ldy, ldj, accumulate, B, D);
+    else
+        spline64_kernel<32, INVERSE><<<row_blocks64(B), 256, 0, s>>>(x, ldx, params, L, a, y, ldy, ldj, accumulate, B, D);
+    return check_launch("spline64_kernel");
+}
+
+}  // namespace
+}  // namespace tfep
+
+using namespace tfep;
+
+extern "C" {
+
+int tfep_affine_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, double* y,
+                            int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "affine_f64: negative size");
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && y, "affine_f64: x/params/y must be non-NULL");
+    affine64_kernel<false><<<row_blocks64(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, y, ldy, log_det_J,
+                                                                             accumulate, B, D);
+    return check_launch("affine64_kernel");
+}
+
+int tfep_affine_inverse_f64(const double* y, int64_t ldy, const double* params, tfep_param_layout layout, double* x,
+                            int64_t ldx, double* log_det_J, int accumulate, int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "affine_f64: negative size");
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && y, "affine_f64: x/params/y must be non-NULL");
+    affine64_kernel<true><<<row_blocks64(B), 256, 0, (hipStream_t)stream>>>(y, ldy, params, layout, x, ldx, log_det_J,
+                                                                            accumulate, B, D);
+    return check_launch("affine64_kernel");
+}
+
+int tfep_affine_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, const double* gy,
+                             int64_t ldgy, const double* g_log_det_J, double* gparams, tfep_param_layout glayout, double* gx,
+                             int64_t ldgx, int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "affine_backward_f64: negative size");
+    if (B == 0 || D == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && gy && gparams && gx, "affine_backward_f64: NULL pointer");
+    affine64_backward_kernel<<<row_blocks64(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, gy, ldgy, g_log_det_J,
+                                                                               gparams, glayout, gx, ldgx, B, D);
+    return check_launch("affine64_backward_kernel");
+}
+
+int tfep_volume_preserving_shift_f64(const double* x, int64_t ldx, const double* shift, int64_t ldp,
+                                     const int32_t* periodic_mask, double lower, double upper, int sign, double* y,
+                                     int64_t ldy, int B, int D, void* stream) {
+    TFEP_REQUIRE(sign == 1 || sign == -1, "volume_preserving_shift_f64: sign must be +1 or -1");
+    TFEP_REQUIRE(B >= 0 && D >= 0, "volume_preserving_shift_f64: negative size");
+    if ((int64_t)B * D == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && shift && y, "volume_preserving_shift_f64: x/shift/y must be non-NULL");
+    const int64_t n = (int64_t)B * D;
+    volpres64_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, ldx, shift, ldp, periodic_mask, lower,
+                                                                                   upper, (double)sign, y, ldy, B, D);
+    return check_launch("volpres64_kernel");
+}
+
+int tfep_spline_n_parameters_per_feature_f64(const tfep_spline_desc_f64* d) {
+    Spline64 a;
+    int rc = make_spline64(d, &a);
+    return rc ? rc : a.P;
+}
+
+int tfep_spline_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout,
+                            const tfep_spline_desc_f64* desc, double* y, int64_t ldy, double* log_det_J, int accumulate,
+                            int B, int D, void* stream) {
+    return launch_spline64<false>(x, ldx, params, layout, desc, y, ldy, log_det_J, accumulate, B, D, stream);
+}
+
+int tfep_spline_inverse_f64(const double* y, int64_t ldy, const double* params, tfep_param_layout layout,
+                            const tfep_spline_desc_f64* desc, double* x, int64_t ldx, double* log_det_J, int accumulate,
+                            int B, int D, void* stream) {
+    return launch_spline64<true>(y, ldy, params, layout, desc, x, ldx, log_det_J, accumulate, B, D, stream);
+}
+
+int tfep_spline_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout,
+                             const tfep_spline_desc_f64* desc, const double* gy, int64_t ldgy, const double* g_log_det_J,
+                             double* gparams, tfep_param_layout glayout, double* gx, int64_t ldgx, int B, int D,
+                             void* stream) {
+    Spline64 a;
+    int rc = make_spline64(desc, &a);
+    if (rc) return rc;
+    TFEP_REQUIRE(B >= 0 && D >= 0, "spline_backward_f64: negative size");
+    if (B == 0 || D == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && gy && gparams && gx, "spline_backward_f64: NULL pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (a.K <= 8)
+        spline64_backward_kernel<8><<<row_blocks64(B), 256, 0, s>>>(x, ldx, params, layout, a, gy, ldgy, g_log_det_J, gparams,
+                                                                    glayout, gx, ldgx, B, D);
+    else if (a.K <= 16)
+        spline64_backward_kernel<16><<<row_blocks64(B), 256, 0, s>>>(x, ldx, params, layout, a, gy, ldgy, g_log_det_J, gparams,
+                                                                     glayout, gx, ldgx, B, D);
+    else
+        spline64_backward_kernel<32><<<row_blocks64(B), 256, 0, s>>>(x, ldx, params, layout, a, gy, ldgy, g_log_det_J, gparams,
+                                                                     glayout, gx, ldgx, B, D);
+    return check_launch("spline64_backward_kernel");
+}
+
+int tfep_periodic_embedding_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
+                                const int32_t* nonperiodic_indices, int n_nonperiodic, double lower, double upper,
+                                double* out, int64_t ldo, int B, void* stream) {
+    TFEP_REQUIRE(B >= 0 && n_periodic >= 0 && n_nonperiodic >= 0, "periodic_embedding_f64: negative size");
+    TFEP_REQUIRE(B == 0 || (x && out), "periodic_embedding_f64: x/out must be non-NULL");
+    TFEP_REQUIRE(n_periodic == 0 || periodic_indices, "periodic_embedding_f64: periodic_indices is NULL");
+    TFEP_REQUIRE(n_nonperiodic == 0 || nonperiodic_indices, "periodic_embedding_f64: nonperiodic_indices is NULL");
+    TFEP_REQUIRE(upper != lower, "periodic_embedding_f64: empty period");
+    const int64_t n = (int64_t)B * (n_periodic + n_nonperiodic);
+    if (n == 0) return TFEP_OK;
+    const double scale = 2.0 * 3.14159265358979323846 / (upper - lower);
+    periodic_embedding64_kernel<false><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        x, ldx, periodic_indices, n_periodic, nonperiodic_indices, n_nonperiodic, lower, scale, nullptr, 0, out, ldo, B);
+    return check_launch("periodic_embedding64_kernel");
+}
+
+int tfep_periodic_embedding_backward_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
+                                         const int32_t* nonperiodic_indices, int n_nonperiodic, double lower, double upper,
+                                         const double* gout, int64_t ldg, double* gx, int64_t ldgx, int B, void* stream) {
+    TFEP_REQUIRE(B >= 0 && n_periodic >= 0 && n_nonperiodic >= 0, "periodic_embedding_backward_f64: negative size");
+    TFEP_REQUIRE(upper != lower, "periodic_embedding_backward_f64: empty period");
+    const int64_t n = (int64_t)B * (n_periodic + n_nonperiodic);
+    if (n == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && gout && gx, "periodic_embedding_backward_f64: NULL pointer");
+    TFEP_REQUIRE(n_periodic == 0 || periodic_indices, "periodic_embedding_backward_f64: periodic_indices is NULL");
+    TFEP_REQUIRE(n_nonperiodic == 0 || nonperiodic_indices, "periodic_embedding_backward_f64: nonperiodic_indices is NULL");
+    const double scale = 2.0 * 3.14159265358979323846 / (upper - lower);
+    periodic_embedding64_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        x, ldx, periodic_indices, n_periodic, nonperiodic_indices, n_nonperiodic, lower, scale, gout, ldg, gx, ldgx, B);
+    return check_launch("periodic_embedding64_kernel");
+}
+
+int tfep_gather_columns_f64(const double* src, int64_t lds, const int32_t* idx, int n_idx, double* dst, int64_t ldd, int B,
+                            void* stream) {
+    TFEP_REQUIRE(B >= 0 && n_idx >= 0, "gather_columns_f64: negative size");
+    const int64_t n = (int64_t)B * n_idx;
+    if (n == 0) return TFEP_OK;
+    TFEP_REQUIRE(src && dst && idx, "gather_columns_f64: NULL pointer");
+    columns64_kernel<false><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, lds, idx, n_idx, dst, ldd, B);
+    return check_launch("gather_columns_f64");
+}
+
+int tfep_scatter_columns_f64(const double* src, int64_t lds, const int32_t* idx, int n_idx, double* dst, int64_t ldd, int B,
+                             void* stream) {
+    TFEP_REQUIRE(B >= 0 && n_idx >= 0, "scatter_columns_f64: negative size");
+    const int64_t n = (int64_t)B * n_idx;
+    if (n == 0) return TFEP_OK;
+    TFEP_REQUIRE(src && dst && idx, "scatter_columns_f64: NULL pointer");
+    columns64_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, lds, idx, n_idx, dst, ldd, B);
+    return check_launch("scatter_columns_f64");
+}
+
+}  // extern "C"

@@ -55,7 +55,7 @@ class BoltzmannKLDivLoss(torch.nn.Module):
 def reduce_stats(target_potentials, log_det_J=None, ref_potentials=None, log_weights=None, bias=None, kT=1.0,
                  ignore_nan=False):
     """The 9 float64 sufficient statistics of the batch: ``torch.ops.tfep.tfep_reduce`` (``tfep_tfep_reduce``)."""
-    ops.check_device_tensor(target_potentials, 'target_potentials')
+    ops.check_device_tensor(target_potentials, 'target_potentials', ops._dtype(target_potentials))   # float32 or float64
     return torch.ops.tfep.tfep_reduce(target_potentials, log_det_J, ref_potentials, log_weights, bias, float(kT),
                                       bool(ignore_nan))
 

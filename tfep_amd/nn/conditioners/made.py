@@ -178,6 +178,16 @@ class MADE(Conditioner):
         """The total number of (unmasked) parameters."""
         return sum(l.n_parameters() for l in self.layers[::2])
 
+    @property
+    def dtype(self) -> torch.dtype:
+        """float32, or float64 after ``.double()`` / when built under ``torch.set_default_dtype(torch.float64)``: a float64
+        MADE runs its three products on the fp64-MFMA GEMM (``masked_linear_f64``) and takes float64 inputs only."""
+        return self.layers[-1].bias.dtype
+
+    def _check_input_dtype(self, x):
+        if x.dtype != self.dtype:
+            raise TypeError(f'MADE: a {self.dtype} conditioner takes {self.dtype} inputs, got {x.dtype}')
+
     def set_output(self, output: torch.Tensor):
         """Make the conditioner return ``output`` for any input (reference made.py:358-364)."""
         last = self.layers[-1]
@@ -362,6 +372,8 @@ class MADE(Conditioner):
             v, g = lin.weight_v.detach(), lin.weight_g.detach()
         else:
             v, g = lin._parameters['weight'].detach(), None
+        if v.dtype == torch.float64:
+            return self._pack_layer_f64(plan, li, lin, v, g, row_of_out, n_rows)
         # one buffer per (layer, row order): zeroed once -- the kernel rewrites every mapped entry and never touches the
         # padding, so later packs skip the clear (a 4.5 GB write for the cfg2 output layer)
         key = ('w', li, n_rows, None if row_of_out is None else row_of_out.data_ptr())
@@ -385,8 +397,28 @@ class MADE(Conditioner):
             plan[ckey] = (buf, bias[0])
         return buf, bias[0]
 
+    def _pack_layer_f64(self, plan, li, lin, v, g, row_of_out, n_rows):
+        """``_pack_layer`` of a float64 layer: ``masked_weight_prepare_f64`` with the plan's permutations into a float64
+        buffer (no prefix-mask form: the mask is read)."""
+        key = ('w', li, n_rows, None if row_of_out is None else row_of_out.data_ptr())
+        ckey = ('packed',) + key[1:]
+        keep = self._keep_packed(plan)
+        if keep and ckey in plan:
+            return plan[ckey]
+        entry = plan.get(key)
+        if entry is None:
+            entry = plan[key] = (ops.zeros(n_rows, plan['k_pad'][li], dtype=torch.float64, device=v.device), row_of_out)
+        buf = entry[0]
+        ops.masked_weight_prepare_f64(v, g, lin.mask, row_of_out, plan['col_of_in'][li], n_rows, plan['k_pad'][li], out=buf,
+                                      clear=False)
+        bias = self._pack_bias(lin, row_of_out, n_rows)
+        if keep:
+            plan[ckey] = (buf, bias)
+        return buf, bias
+
     def _pack_bias(self, lin, row_of_out, n_rows):
-        bias = ops.zeros(1, n_rows, dtype=torch.float32, device=lin.bias.device)
+        bias = ops.zeros(1, n_rows, dtype=lin.bias.dtype if lin.bias.dtype == torch.float64 else torch.float32,
+                         device=lin.bias.device)
         if row_of_out is None:
             bias[0, :lin.out_features] = lin.bias.detach()
         else:
@@ -398,7 +430,7 @@ class MADE(Conditioner):
         parameters (``tfep_masked_weight_prepare_split_both``) -- inside ``frozen_weights()`` / with ``cache_packed_weights``,
         for a layer whose mask rows are prefixes and whose rows hold 8192 .. 16 384 weights; otherwise nothing happens and the
         two methods pack on their own.  The blocked inverse wants both forms of every layer."""
-        if not self._keep_packed(plan) or not (8192 <= lin.in_features <= 16384):
+        if self.dtype == torch.float64 or not self._keep_packed(plan) or not (8192 <= lin.in_features <= 16384):
             return False
         row_of_out = plan['row_of_out'][li] if row_of_out is None else row_of_out
         n_rows = plan['n_pad'][li] if n_rows is None else n_rows
@@ -560,7 +592,7 @@ class MADE(Conditioner):
         plan = self.plan(device)
         lins = self._linears()
         self._packed_ahead = None
-        if self.cache_packed_weights and not self._frozen:
+        if self.cache_packed_weights and not self._frozen or self.dtype == torch.float64:
             return                                 # the cache already holds (or the forward will fill) the packed weights
         stream.wait_stream(torch.cuda.current_stream(device))
         items = {}
@@ -592,13 +624,15 @@ class MADE(Conditioner):
         """Run every layer but the last; returns the last hidden activations (zero padded,
         units sorted by degree) and the plan.  ``split``: the GEMMs take split-f16 operands
         (``csrc/split_gemm.hip``); the activations returned are fp32 either way."""
-        ops.check_device_tensor(x, 'x')
+        ops.check_device_tensor(x, 'x', self.dtype)
         x = self._embed(x)
         if x.shape[1] != self.dimension_in:
             raise ValueError(f'expected {self.dimension_in} input features, got {x.shape[1]}')
         plan = self.plan(x.device)
         lins = self._linears()
-        h = ops.pad_columns(x, plan['k_pad'][0])
+        if self.dtype == torch.float64:
+            split = False                   # (the split-f16 GEMMs are float32-only)
+        h = ops.pad_columns(x, plan['k_pad'][0], self.dtype)
         for li, lin in enumerate(lins[:-1]):
             if split:
                 ws, w_inv, b, _ = self._pack_layer_split(plan, li, lin)
@@ -660,6 +694,9 @@ class MADE(Conditioner):
         """Transformer parameters ``(..., n_out)`` (reference made.py:355).  ``split``: run the GEMMs on split-f16
         operands (fp32-equivalent, ``csrc/split_gemm.hip``); None = the ``TFEP_SPLIT_GEMM`` default."""
         self.begin_call()
+        self._check_input_dtype(x)
+        if self.dtype == torch.float64:
+            split = False                   # float64: three fp64-MFMA GEMMs, the ELU fused in the first two
         lead = x.shape[:-1]
         hint = getattr(x, '_tfep_split', None) if x.dim() == 2 else None      # (a reshape makes a new tensor object)
         if hint is not None and hint[2] != x._version:

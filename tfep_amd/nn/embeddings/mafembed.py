@@ -76,7 +76,7 @@ class PeriodicEmbedding(MAFEmbedding):
         return self._i32[key]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        ops.check_device_tensor(x, 'x')
+        ops.check_device_tensor(x, 'x', ops._dtype(x))             # float32, or float64 (the float64 kernels)
         per, non = self.device_indices(x.device)
         if torch.is_grad_enabled() and x.requires_grad:
             return _PeriodicEmbeddingFn.apply(x, per, non, *self.host_limits())
@@ -100,12 +100,13 @@ class _PeriodicEmbeddingFn(torch.autograd.Function):
     def backward(ctx, g):
         from ... import _lib
         x, per, non = ctx.saved_tensors
-        x, ldx = _lib.rows(x.detach(), 'x')
-        g = g.contiguous()
+        dt = ops._dtype(x)
+        x, ldx = _lib.rows(x.detach(), 'x', dt)
+        g = _lib.check_device_tensor(g.contiguous(), 'grad', dt)
         B, D = x.shape
-        gx = torch.zeros(B, D, dtype=torch.float32, device=x.device)
+        gx = torch.zeros(B, D, dtype=dt, device=x.device)
         if B > 0:
-            _lib.call('tfep_periodic_embedding_backward', _lib.ptr(x), ldx, _lib.ptr(per), per.numel(), _lib.ptr(non),
+            _lib.call('tfep_periodic_embedding_backward' + ops._sfx(dt), _lib.ptr(x), ldx, _lib.ptr(per), per.numel(), _lib.ptr(non),
                       non.numel(), *ctx.limits, _lib.ptr(g), g.shape[1], _lib.ptr(gx), D, B, _lib.stream_of(x))
         return gx, None, None, None, None
 

@@ -71,7 +71,7 @@ def _transformer_supported(tr):
 
 
 def _voidp(t, offset_elems=0):
-    return ctypes.c_void_p(t.data_ptr() + 4 * offset_elems)
+    return ctypes.c_void_p(t.data_ptr() + t.element_size() * offset_elems)
 
 
 def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, layout=None, order=None):
@@ -94,6 +94,23 @@ def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, 
     # layout: (row stride, stride between parameters, stride between features); default = reference layout.
     # `order`: the features are given in this permutation (slot order), so per-feature constants follow it.
     lay = _lib.ParamLayout(*layout) if layout is not None else _lib.ParamLayout(ld_theta, D, 1)
+    if x.dtype == torch.float64:
+        # float64 layers: the float64 VJP kernels (reference layout; every tensor float64, else TypeError)
+        for t, n in ((x, 'x'), (theta, 'theta'), (gy, 'grad_y'), (gl, 'grad_log_det_J'), (gtheta, 'grad_theta'), (gx, 'gx')):
+            _lib.check_device_tensor(t, n, torch.float64)
+        if type(tr) is NeuralSplineTransformer:
+            cfg = tr.config(dev, torch.float64)
+            _lib.call('tfep_spline_backward_f64', _lib.ptr(x), D, th, lay, ctypes.byref(cfg.desc), _lib.ptr(gy), D,
+                      _lib.ptr(gl), gth, lay, _lib.ptr(gx), D, B, D, stream)
+        elif type(tr) is AffineTransformer:
+            _lib.call('tfep_affine_backward_f64', _lib.ptr(x), D, th, lay, _lib.ptr(gy), D, _lib.ptr(gl), gth, lay,
+                      _lib.ptr(gx), D, B, D, stream)
+        elif type(tr) is VolumePreservingShiftTransformer:
+            gtheta[:, th_off:th_off + D].copy_(gy)     # y = x + b: the cotangent passes to b and to x unchanged
+            gx.copy_(gy)
+        else:
+            raise TypeError(f'{type(tr).__name__}: float64 is not supported for this transformer yet (float32 only)')
+        return
     if type(tr) is NeuralSplineTransformer:
         cfg = _slot_config(tr, dev, order)
         _lib.call('tfep_spline_backward', _lib.ptr(x), D, th, lay, ctypes.byref(cfg.desc), _lib.ptr(gy), D,
@@ -208,7 +225,7 @@ class TransformerFunction(torch.autograd.Function):
     def backward(ctx, gy, gldj):
         x, theta = ctx.saved_tensors
         B, D = x.shape
-        f32 = dict(dtype=torch.float32, device=x.device)
+        f32 = dict(dtype=torch.float64 if x.dtype == torch.float64 else torch.float32, device=x.device)   # (or float64)
         gy = ops.zeros(B, D, **f32) if gy is None else gy.contiguous()
         gl = ops.zeros(B, **f32) if gldj is None else gldj.contiguous()
         gtheta = ops.zeros(*theta.shape, **f32)
@@ -289,7 +306,7 @@ class TransformerInverseFunction(torch.autograd.Function):
     def backward(ctx, gx, gldj):
         x, theta = ctx.saved_tensors
         B, D = x.shape
-        f32 = dict(dtype=torch.float32, device=x.device)
+        f32 = dict(dtype=torch.float64 if x.dtype == torch.float64 else torch.float32, device=x.device)   # (or float64)
         stream = _lib.stream_of(x)
         gx = ops.zeros(B, D, **f32) if gx is None else gx.contiguous()
         gl = ops.zeros(B, **f32) if gldj is None else gldj.contiguous()

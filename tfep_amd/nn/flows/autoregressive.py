@@ -21,7 +21,7 @@ from ...utils.misc import ensure_tensor_sequence
 from ..conditioners.made import MADE
 from ..embeddings.mafembed import PeriodicEmbedding
 from ..transformers.affine import AffineTransformer, VolumePreservingShiftTransformer
-from ..transformers.mixed import MixedTransformer
+from ..transformers.mixed import MixedTransformer, check_float64_members
 from ..transformers.moebius import MoebiusTransformer
 from ..transformers.spline import NeuralSplineTransformer
 from .sequential import _side_stream
@@ -185,6 +185,8 @@ class AutoregressiveFlow(torch.nn.Module):
     def prepack_async(self, device, stream, batch=None):
         """Start packing this layer's weights on ``stream`` for its next forward pass (called by SequentialFlow while
         the previous layer computes).  Only for the fused split-f16 path; a no-op otherwise."""
+        if self.is_float64:
+            return
         kind = self._fused_kind()
         if kind is None or not self._use_split_gemm(batch) or not isinstance(self._conditioner, MADE):
             return
@@ -203,6 +205,8 @@ class AutoregressiveFlow(torch.nn.Module):
         the conditioner is large enough for the operand conversions to pay (``MADE.split_worthwhile``: >= 4 M weights, or
         enough weight x row products at the given batch) -- smaller problems are launch bound and stay on the exact-fp32
         kernel."""
+        if self.is_float64:
+            return False                           # (the split-f16 GEMMs are float32-only)
         if self.split_gemm is not None:
             return bool(self.split_gemm)
         if self._guard_exact:                      # this call's data failed the range guard (``_range_guard``)
@@ -419,6 +423,8 @@ class AutoregressiveFlow(torch.nn.Module):
         call is recorded as ONE graph node whose backward runs on the HIP kernels
         (``flows/_backward.py``); otherwise it is the plain forward.
         """
+        if self.is_float64 or ops._dtype(x) == torch.float64:
+            return self._forward_f64(x)
         ops.check_device_tensor(x, 'x')
         self._check_features(x, 'x')
         self._sync_conditioner()
@@ -434,6 +440,54 @@ class AutoregressiveFlow(torch.nn.Module):
                         return _backward.generic_forward(self, x)          # conditioner by autograd, transformer VJP kernel
                     return _backward.UnsupportedBackward.apply(self, x, *params)
             return self._forward_impl(x)
+
+    # ------------------------------------------------------------------ float64
+    @property
+    def is_float64(self):
+        """True for a float64 layer (``.double()``, or built under ``torch.set_default_dtype(torch.float64)``): the dtype of
+        the conditioner's parameters.  A float64 layer always takes the generic path -- conditioner (three fp64-MFMA GEMMs
+        for a MADE), float64 transformer kernel, column scatter -- and its inverse the reference's pass per degree; the
+        float32 switches (``fused``, ``split_gemm``, ``layer_kernel``, ``blocked_inverse``, the ``TFEP_*`` variables)
+        do not apply to it."""
+        f64 = self._dev.get('float64')               # (the cache goes with every .to() / .double() / load_state_dict)
+        if f64 is None:
+            f64 = next((p.dtype == torch.float64 for p in self._conditioner.parameters() if p.is_floating_point()), False)
+            self._dev['float64'] = f64
+        return f64
+
+    def _check_float64(self, x, name):
+        """The dtype contract of float64 layers: float64 inputs on float64 layers only, and the parts that have float64
+        kernels (TypeError otherwise, before any launch)."""
+        ops.check_device_tensor(x, name, torch.float64 if self.is_float64 else torch.float32)
+        self._check_features(x, name)
+        tr = self._transformer
+        if type(tr) is MoebiusTransformer:
+            raise TypeError(f'{type(self).__name__}: float64 is not supported for the Moebius transformer yet (float32 only)')
+        if type(tr) is MixedTransformer:
+            check_float64_members(tr)
+        emb = getattr(self._conditioner, 'embedding', None)
+        if emb is not None and type(emb) is not PeriodicEmbedding:
+            raise TypeError(f'{type(self).__name__}: float64 is not supported for the {type(emb).__name__} embedding yet '
+                            '(float64 layers take a PeriodicEmbedding or none)')
+
+    def _forward_f64(self, x):
+        self._check_float64(x, 'x')
+        self._sync_conditioner()
+        if torch.is_grad_enabled():
+            from . import _backward
+            if x.requires_grad or any(p.requires_grad for p in self._conditioner.parameters()):
+                return _backward.generic_forward(self, x)          # conditioner by autograd, transformer VJP kernel
+        return self._forward_values_f64(x)
+
+    def _forward_values_f64(self, x):
+        parameters = self.get_transformer_parameters(x)
+        if self.has_fixed_indices:
+            t = self._tables(x.device)
+            y = x.clone()                               # fixed features propagate unchanged
+            y_tr, log_det_J = self._transformer(ops.gather_columns(x, t['tr']), parameters)
+            ops.scatter_columns(y_tr, t['tr'], y)
+            return y, log_det_J
+        return self._transformer(x, parameters)
 
     def _check_features(self, x, name):
         """The kernels index ``x`` by the layer's own feature tables: a tensor of another width must never reach them
@@ -503,7 +557,10 @@ class AutoregressiveFlow(torch.nn.Module):
         ``blocked_inverse=False``): one full conditioner pass per degree, like the reference; the
         last pass' log-det is the total.
         """
-        ops.check_device_tensor(y, 'y')
+        if self.is_float64 or ops._dtype(y) == torch.float64:
+            self._check_float64(y, 'y')
+        else:
+            ops.check_device_tensor(y, 'y')
         self._check_features(y, 'y')
         self._sync_conditioner()
         if torch.is_grad_enabled():
@@ -522,6 +579,8 @@ class AutoregressiveFlow(torch.nn.Module):
         host synchronisation per call, on a path that takes tens of milliseconds -- and where they span more than 2^19 the call is
         repeated on the exact-fp32 kernels (``last_split_guard`` says so), the arithmetic a guarded forward of that x uses."""
         x, log_det_J = self._inverse_values(y)
+        if self.is_float64:
+            return x, log_det_J                         # (no split-f16 arithmetic to guard)
         on = self.split_guard if self.split_guard is not None else os.environ.get('TFEP_SPLIT_GUARD', '1') != '0'
         if on and self.split_gemm is None and not self._guard_exact and y.shape[0] > 0 and self._use_split_gemm(y.shape[0]):
             if torch.cuda.is_current_stream_capturing():
@@ -581,7 +640,7 @@ class AutoregressiveFlow(torch.nn.Module):
     # ------------------------------------------------------------------ blocked inverse
     def _blocked_ok(self):
         made = self._conditioner
-        if not self.blocked_inverse or not isinstance(made, MADE) or len(self._conditioner_indices) > 0:
+        if not self.blocked_inverse or not isinstance(made, MADE) or len(self._conditioner_indices) > 0 or self.is_float64:
             return False
         if not made._degrees_ok:            # masks that no degree assignment reproduces: the reference's pass per degree
             return False

@@ -16,11 +16,11 @@ class AffineTransformer(MAFTransformer):
     n_parameters_per_feature = 2
 
     def forward(self, x, parameters):
-        ops.check_device_tensor(x, 'x')
+        ops.check_device_tensor(x, 'x', ops._dtype(x))                     # float32, or float64 (the float64 kernels)
         return tuple(torch.ops.tfep.affine_forward(x, parameters))        # differentiable (tfep::affine_backward)
 
     def inverse(self, y, parameters):
-        ops.check_device_tensor(y, 'y')
+        ops.check_device_tensor(y, 'y', ops._dtype(y))
         return tuple(torch.ops.tfep.affine_inverse(y, parameters))
 
     def get_identity_parameters(self, n_features: int) -> torch.Tensor:

@@ -8,6 +8,14 @@ from ...utils.misc import ensure_tensor_sequence
 from .transformer import MAFTransformer
 
 
+def check_float64_members(tr):
+    """A float64 mixed transformer runs its members on the float64 kernels; the Moebius transformer has none yet."""
+    from .moebius import MoebiusTransformer
+    if any(isinstance(t, MoebiusTransformer) for t in tr._transformers):
+        raise TypeError('MixedTransformer: float64 is not supported for a mixed transformer with a Moebius member yet '
+                        '(float32 only)')
+
+
 class MixedTransformer(MAFTransformer):
     """Apply different transformers to different groups of features.
 
@@ -63,7 +71,9 @@ class MixedTransformer(MAFTransformer):
         return self._run(y, parameters, inverse=True)
 
     def _run(self, x, parameters, inverse):
-        ops.check_device_tensor(x, 'x')
+        ops.check_device_tensor(x, 'x', ops._dtype(x))
+        if x.dtype == torch.float64:
+            check_float64_members(self)
         key = str(x.device)
         if key not in self._i32:
             self._i32[key] = [ind.to(device=x.device, dtype=torch.int32) for ind in self._indices]

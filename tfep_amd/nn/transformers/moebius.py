@@ -5,6 +5,11 @@ from ... import ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.tfe
 from .transformer import MAFTransformer
 
 
+def _float32_only(x):
+    if isinstance(x, torch.Tensor) and x.dtype == torch.float64:
+        raise TypeError('MoebiusTransformer: float64 is not supported for the Moebius transformer yet (float32 only)')
+
+
 class MoebiusTransformer(MAFTransformer):
     r""":math:`y = \frac{\|x\|^2 - \|w\|^2}{\|x - w\|^2}(x - w) - w` on ``dimension``-vectors.
 
@@ -19,11 +24,13 @@ class MoebiusTransformer(MAFTransformer):
         self.unit_sphere = unit_sphere
 
     def forward(self, x, parameters):
+        _float32_only(x)
         ops.check_device_tensor(x, 'x')
         return tuple(torch.ops.tfep.moebius_forward(x, parameters, int(self.dimension), float(self.max_radius),
                                                     bool(self.unit_sphere)))                   # differentiable
 
     def inverse(self, y, parameters):
+        _float32_only(y)
         ops.check_device_tensor(y, 'y')
         return tuple(torch.ops.tfep.moebius_inverse(y, parameters, int(self.dimension), float(self.max_radius),
                                                     bool(self.unit_sphere)))

@@ -87,37 +87,49 @@ class NeuralSplineTransformer(MAFTransformer):
 
     def _apply(self, fn, *args, **kwargs):
         self._cfg = None
+        self.__dict__.pop('_cfg64', None)
         self.__dict__.pop('_host_cache', None)
         return super()._apply(fn, *args, **kwargs)
 
     def _load_from_state_dict(self, *args, **kwargs):
         self._cfg = None
+        self.__dict__.pop('_cfg64', None)
         self.__dict__.pop('_host_cache', None)
         return super()._load_from_state_dict(*args, **kwargs)
 
-    def config(self, device):
-        """Device descriptor handed to the kernels (rebuilt after .to() / load_state_dict)."""
+    def config(self, device, dtype=torch.float32):
+        """Device descriptor handed to the kernels (rebuilt after .to() / load_state_dict).  ``dtype``: float32 (the
+        float32 kernels; the domain arrays are rounded to float32 whatever their dtype) or float64 (a float64 descriptor
+        for the float64 kernels, which the transformer asks for on float64 inputs: the domain of a ``.double()`` transformer
+        or one built under ``torch.set_default_dtype(torch.float64)`` is then used as it is)."""
+        if dtype == torch.float64:
+            cfg = self.__dict__.get('_cfg64')
+            if cfg is None or cfg.x0.device != device:
+                cfg = self.__dict__['_cfg64'] = self._make_config(device, torch.float64)
+            return cfg
         if self._cfg is None or self._cfg.x0.device != device:
-            h = self.host()
-            f32 = dict(device=device, dtype=torch.float32)
-            self._cfg = ops.SplineConfig(
-                self.x0.to(**f32), self.xf.to(**f32), self._y0.to(**f32), self._yf.to(**f32),
-                h['n_bins'], h['circular'], h['identity'], h['learn_lower'], h['learn_upper'],
-                h['min_bin'], h['min_slope'])
+            self._cfg = self._make_config(device, torch.float32)
         return self._cfg
 
-    def _op_args(self, device):
-        cfg, h = self.config(device), self.host()
+    def _make_config(self, device, dtype):
+        h = self.host()
+        kw = dict(device=device, dtype=dtype)
+        return ops.SplineConfig(self.x0.to(**kw), self.xf.to(**kw), self._y0.to(**kw), self._yf.to(**kw),
+                                h['n_bins'], h['circular'], h['identity'], h['learn_lower'], h['learn_upper'],
+                                h['min_bin'], h['min_slope'], dtype=dtype)
+
+    def _op_args(self, device, dtype=torch.float32):
+        cfg, h = self.config(device, dtype), self.host()
         return (cfg.x0, cfg.xf, cfg.y0, cfg.yf, h['n_bins'], h['circular'], h['identity'], h['learn_lower'],
                 h['learn_upper'], h['min_bin'], h['min_slope'])
 
     def forward(self, x, parameters):
-        ops.check_device_tensor(x, 'x')
-        return tuple(torch.ops.tfep.spline_forward(x, parameters, *self._op_args(x.device)))   # differentiable
+        ops.check_device_tensor(x, 'x', ops._dtype(x))             # float32, or float64 (the float64 kernels)
+        return tuple(torch.ops.tfep.spline_forward(x, parameters, *self._op_args(x.device, x.dtype)))   # differentiable
 
     def inverse(self, y, parameters):
-        ops.check_device_tensor(y, 'y')
-        return tuple(torch.ops.tfep.spline_inverse(y, parameters, *self._op_args(y.device)))
+        ops.check_device_tensor(y, 'y', ops._dtype(y))
+        return tuple(torch.ops.tfep.spline_inverse(y, parameters, *self._op_args(y.device, y.dtype)))
 
     def get_identity_parameters(self, n_features: int) -> torch.Tensor:
         """Zeros: equal bins, unit slopes, zero shift, unit domain scale (reference spline.py:263-297)."""

@@ -10,21 +10,31 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ParamLayout, SplineDesc, call, check_device_tensor, ptr, rows, stream_of
+from ._lib import ParamLayout, SplineDesc, SplineDescF64, call, check_device_tensor, ptr, rows, stream_of
 
 
-def _ldj_out(log_det_J, B, like):
+def _dtype(x):
+    """The kernel family of an input: float64 tensors take the float64 kernels, anything else the float32 ones (whose checks
+    reject what is not float32)."""
+    return torch.float64 if isinstance(x, torch.Tensor) and x.dtype == torch.float64 else torch.float32
+
+
+def _sfx(dtype):
+    return '_f64' if dtype == torch.float64 else ''
+
+
+def _ldj_out(log_det_J, B, like, dtype=torch.float32):
     """Return (tensor, accumulate flag): accumulate into ``log_det_J`` if given."""
     if log_det_J is None:
-        return torch.empty(B, dtype=torch.float32, device=like.device), 0
-    check_device_tensor(log_det_J, 'log_det_J')
+        return torch.empty(B, dtype=dtype, device=like.device), 0
+    check_device_tensor(log_det_J, 'log_det_J', dtype)
     if log_det_J.shape != (B,) or not log_det_J.is_contiguous():
         raise ValueError('log_det_J must be a contiguous (batch,) tensor')
     return log_det_J, 1
 
 
-def _check_params(parameters, B, n, name='parameters'):
-    parameters, ld = rows(parameters, name)
+def _check_params(parameters, B, n, name='parameters', dtype=torch.float32):
+    parameters, ld = rows(parameters, name, dtype)
     if parameters.shape[0] != B or parameters.shape[1] != n:
         raise ValueError(f'{name} must have shape ({B}, {n}), got {tuple(parameters.shape)}')
     return parameters, ld
@@ -39,26 +49,28 @@ def _layout(ld, D, layout=None):
 # ----------------------------------------------------------------------------- affine
 
 def affine(x, parameters, inverse=False, log_det_J=None):
-    """AffineTransformer.forward / .inverse (reference affine.py:51-106)."""
-    x, ldx = rows(x, 'x')
+    """AffineTransformer.forward / .inverse (reference affine.py:51-106).  float64 tensors run on the float64 kernels."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
     B, D = x.shape
-    parameters, ldp = _check_params(parameters, B, 2 * D)
+    parameters, ldp = _check_params(parameters, B, 2 * D, dtype=dt)
     y = torch.empty(B, D, dtype=x.dtype, device=x.device)
-    ldj, acc = _ldj_out(log_det_J, B, x)
-    fn = 'tfep_affine_inverse' if inverse else 'tfep_affine_forward'
+    ldj, acc = _ldj_out(log_det_J, B, x, dt)
+    fn = ('tfep_affine_inverse' if inverse else 'tfep_affine_forward') + _sfx(dt)
     call(fn, ptr(x), ldx, ptr(parameters), _layout(ldp, D), ptr(y), max(D, 1), ptr(ldj), acc, B, D, stream_of(x))
     return y, ldj
 
 
 def volume_preserving_shift(x, shift, periodic_mask=None, limits=(0.0, 1.0), inverse=False):
     """VolumePreservingShiftTransformer (reference affine.py:366-456); log-det is zero."""
-    x, ldx = rows(x, 'x')
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
     B, D = x.shape
-    shift, lds = _check_params(shift, B, D, 'shift')
+    shift, lds = _check_params(shift, B, D, 'shift', dt)
     y = torch.empty(B, D, dtype=x.dtype, device=x.device)
     if periodic_mask is not None:
         check_device_tensor(periodic_mask, 'periodic_mask', torch.int32)
-    call('tfep_volume_preserving_shift', ptr(x), ldx, ptr(shift), lds,
+    call('tfep_volume_preserving_shift' + _sfx(dt), ptr(x), ldx, ptr(shift), lds,
          ptr(periodic_mask), float(limits[0]), float(limits[1]), -1 if inverse else 1,
          ptr(y), max(D, 1), B, D, stream_of(x))
     return y, zeros(B, dtype=x.dtype, device=x.device)
@@ -67,30 +79,46 @@ def volume_preserving_shift(x, shift, periodic_mask=None, limits=(0.0, 1.0), inv
 # ----------------------------------------------------------------------------- spline
 
 class SplineConfig:
-    """Host mirror of tfep_spline_desc; keeps the (D,) device arrays alive."""
+    """Host mirror of tfep_spline_desc (float32 domain arrays) or, with ``dtype=torch.float64``, of tfep_spline_desc_f64
+    (float64 domain arrays and minimum sizes; validated here, before any launch); keeps the (D,) device arrays alive."""
 
     def __init__(self, x0, xf, y0, yf, n_bins, circular=False, identity_boundary_slopes=False,
-                 learn_lower_bound=False, learn_upper_bound=False, min_bin_size=1e-4, min_slope=1e-4):
-        self.x0, self.xf, self.y0, self.yf = (check_device_tensor(t.contiguous(), n)
+                 learn_lower_bound=False, learn_upper_bound=False, min_bin_size=1e-4, min_slope=1e-4,
+                 dtype=torch.float32):
+        self.dtype = dtype
+        self.x0, self.xf, self.y0, self.yf = (check_device_tensor(t.contiguous(), n, dtype)
                                               for t, n in ((x0, 'x0'), (xf, 'xf'), (y0, 'y0'), (yf, 'yf')))
+        lib = _lib.load()
+        if dtype == torch.float64:
+            self.desc = SplineDescF64(self.x0.data_ptr(), self.xf.data_ptr(), self.y0.data_ptr(), self.yf.data_ptr(),
+                                      int(n_bins), int(bool(circular)), int(bool(identity_boundary_slopes)),
+                                      int(bool(learn_lower_bound)), int(bool(learn_upper_bound)),
+                                      float(min_bin_size), float(min_slope))
+            n = lib.tfep_spline_n_parameters_per_feature_f64(ctypes.byref(self.desc))
+            if n < 0:
+                raise ValueError(lib.tfep_last_error().decode())
+            self.n_parameters_per_feature = n
+            return
         self.desc = SplineDesc(self.x0.data_ptr(), self.xf.data_ptr(), self.y0.data_ptr(), self.yf.data_ptr(),
                                int(n_bins), int(bool(circular)), int(bool(identity_boundary_slopes)),
                                int(bool(learn_lower_bound)), int(bool(learn_upper_bound)),
                                float(min_bin_size), float(min_slope))
-        self.n_parameters_per_feature = _lib.load().tfep_spline_n_parameters_per_feature(ctypes.byref(self.desc))
+        self.n_parameters_per_feature = lib.tfep_spline_n_parameters_per_feature(ctypes.byref(self.desc))
 
 
 def spline(x, parameters, cfg, inverse=False, log_det_J=None, layout=None):
-    """NeuralSplineTransformer.forward / .inverse (reference spline.py:184-261)."""
-    x, ldx = rows(x, 'x')
+    """NeuralSplineTransformer.forward / .inverse (reference spline.py:184-261).  The kernels are those of ``cfg.dtype``:
+    ``x`` and ``parameters`` must be of that dtype."""
+    dt = cfg.dtype
+    x, ldx = rows(x, 'x', dt)
     B, D = x.shape
     P = cfg.n_parameters_per_feature
     if cfg.x0.numel() != D:
         raise ValueError(f'spline domain has {cfg.x0.numel()} features, input has {D}')
-    parameters, ldp = _check_params(parameters, B, P * D)
+    parameters, ldp = _check_params(parameters, B, P * D, dtype=dt)
     y = torch.empty(B, D, dtype=x.dtype, device=x.device)
-    ldj, acc = _ldj_out(log_det_J, B, x)
-    fn = 'tfep_spline_inverse' if inverse else 'tfep_spline_forward'
+    ldj, acc = _ldj_out(log_det_J, B, x, dt)
+    fn = ('tfep_spline_inverse' if inverse else 'tfep_spline_forward') + _sfx(dt)
     call(fn, ptr(x), ldx, ptr(parameters), _layout(ldp, D, layout), ctypes.byref(cfg.desc),
          ptr(y), max(D, 1), ptr(ldj), acc, B, D, stream_of(x))
     return y, ldj
@@ -133,30 +161,35 @@ def moebius_split_out(x, parameters, max_radius, cols_padded):
 
 def periodic_embedding(x, periodic_indices, nonperiodic_indices, lower, upper):
     """PeriodicEmbedding.forward (reference mafembed.py:112-145)."""
-    x, ldx = rows(x, 'x')
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
     B = x.shape[0]
     n_per, n_non = periodic_indices.numel(), nonperiodic_indices.numel()
     out = torch.empty(B, n_non + 2 * n_per, dtype=x.dtype, device=x.device)
-    call('tfep_periodic_embedding', ptr(x), ldx, ptr(periodic_indices), n_per, ptr(nonperiodic_indices), n_non,
+    call('tfep_periodic_embedding' + _sfx(dt), ptr(x), ldx, ptr(periodic_indices), n_per, ptr(nonperiodic_indices), n_non,
          float(lower), float(upper), ptr(out), n_non + 2 * n_per, B, stream_of(x))
     return out
 
 
 def gather_columns(src, idx):
-    src, lds = rows(src, 'src')
+    dt = _dtype(src)
+    src, lds = rows(src, 'src', dt)
     B, n = src.shape[0], idx.numel()
     dst = torch.empty(B, n, dtype=src.dtype, device=src.device)
-    call('tfep_gather_columns', ptr(src), lds, ptr(idx), n, ptr(dst), n, B, stream_of(src))
+    call('tfep_gather_columns' + _sfx(dt), ptr(src), lds, ptr(idx), n, ptr(dst), n, B, stream_of(src))
     return dst
 
 
 def scatter_columns(src, idx, dst):
     """dst[:, idx[j]] = src[:, j] (in place on ``dst``, which the caller owns)."""
-    src, lds = rows(src, 'src')
+    dt = _dtype(src)
+    src, lds = rows(src, 'src', dt)
     B, n = src.shape[0], idx.numel()
     if not dst.is_contiguous():
         raise ValueError('dst must be contiguous')
-    call('tfep_scatter_columns', ptr(src), lds, ptr(idx), n, ptr(dst), dst.shape[1], B, stream_of(src))
+    if torch.float64 in (dt, dst.dtype):
+        check_device_tensor(dst, 'dst', dt)
+    call('tfep_scatter_columns' + _sfx(dt), ptr(src), lds, ptr(idx), n, ptr(dst), dst.shape[1], B, stream_of(src))
     return dst
 
 
@@ -633,20 +666,22 @@ def masked_linear_split(x_split, x_inv_scale, w_split, w_inv_scale, bias, n_out,
 
 def tfep_reduce(target_potentials, log_det_J=None, ref_potentials=None, log_weights=None, bias=None,
                 kT=1.0, ignore_nan=False):
-    """The 9 float64 sufficient statistics of the TFEP loss / estimator (see tfep_hip.h)."""
-    t = check_device_tensor(target_potentials.contiguous(), 'target_potentials')
+    """The 9 float64 sufficient statistics of the TFEP loss / estimator (see tfep_hip.h).  float64 inputs (all of them)
+    take ``tfep_tfep_reduce_f64``, which forms the residuals in fp64."""
+    dt = _dtype(target_potentials)
+    t = check_device_tensor(target_potentials.contiguous(), 'target_potentials', dt)
     N = t.numel()
     opt = []
     for v, n in ((log_det_J, 'log_det_J'), (ref_potentials, 'ref_potentials'), (log_weights, 'log_weights'),
                  (bias, 'bias')):
         if v is not None:
-            v = check_device_tensor(v.contiguous(), n)
+            v = check_device_tensor(v.contiguous(), n, dt)
             if v.numel() != N:
                 raise ValueError(f'{n} must have {N} elements')
         opt.append(v)
     nws = _lib.load().tfep_tfep_reduce_workspace_doubles(N)
     ws = torch.empty(nws, dtype=torch.float64, device=t.device)
     out = torch.empty(9, dtype=torch.float64, device=t.device)
-    call('tfep_tfep_reduce', ptr(t), ptr(opt[0]), ptr(opt[1]), ptr(opt[2]), ptr(opt[3]), float(kT),
+    call('tfep_tfep_reduce' + _sfx(dt), ptr(t), ptr(opt[0]), ptr(opt[1]), ptr(opt[2]), ptr(opt[3]), float(kT),
          int(bool(ignore_nan)), N, ptr(ws), ptr(out), stream_of(t))
     return out

@@ -31,6 +31,14 @@ def _pair_like(x):
     return x.new_empty(x.shape), x.new_empty((x.shape[0],))
 
 
+def _vjp_dtype(x, *others):
+    """The dtype of a VJP launch: every tensor float32, or every tensor float64 (the float64 kernels); else TypeError."""
+    dt = ops._dtype(x)
+    for t, n in others:
+        _lib.check_device_tensor(t, n, dt)
+    return dt
+
+
 # ============================================================================= affine
 
 @custom_op('tfep::affine_forward', mutates_args=(), device_types=_DEV)
@@ -48,11 +56,12 @@ def affine_backward(x: Tensor, parameters: Tensor, grad_y: Tensor, grad_log_det_
     # (contiguous copies are held in locals until the launch is queued: a temporary freed inside the argument list
     # hands its block back to the caching allocator, and the NEXT temporary may be written over it)
     x, parameters, gy, gl = x.contiguous(), parameters.contiguous(), grad_y.contiguous(), grad_log_det_J.contiguous()
+    dt = _vjp_dtype(x, (x, 'x'), (parameters, 'parameters'), (gy, 'grad_y'), (gl, 'grad_log_det_J'))
     B, D = x.shape
     gx = torch.empty_like(x)
-    gp = ops.zeros(*parameters.shape, dtype=torch.float32, device=x.device)
+    gp = ops.zeros(*parameters.shape, dtype=dt, device=x.device)
     lay = _lib.ParamLayout(parameters.shape[1], D, 1)
-    _lib.call('tfep_affine_backward', _lib.ptr(x), D, _lib.ptr(parameters), lay, _lib.ptr(gy), D,
+    _lib.call('tfep_affine_backward' + ops._sfx(dt), _lib.ptr(x), D, _lib.ptr(parameters), lay, _lib.ptr(gy), D,
               _lib.ptr(gl), _lib.ptr(gp), lay, _lib.ptr(gx), D, B, D, _lib.stream_of(x))
     return gx, gp
 
@@ -87,7 +96,10 @@ affine_forward.register_autograd(_affine_bwd, setup_context=_save_xp)
 # ============================================================================= rational-quadratic spline
 
 def _spline_cfg(x0, xf, y0, yf, n_bins, circular, identity, learn_lower, learn_upper, min_bin, min_slope):
-    return ops.SplineConfig(x0, xf, y0, yf, n_bins, circular, identity, learn_lower, learn_upper, min_bin, min_slope)
+    """The descriptor of the domain arrays' dtype: float64 arrays select the float64 kernels (and then x and the parameters
+    must be float64 too)."""
+    return ops.SplineConfig(x0, xf, y0, yf, n_bins, circular, identity, learn_lower, learn_upper, min_bin, min_slope,
+                            dtype=ops._dtype(x0))
 
 
 @custom_op('tfep::spline_forward', mutates_args=(), device_types=_DEV)
@@ -116,11 +128,13 @@ def spline_backward(x: Tensor, parameters: Tensor, grad_y: Tensor, grad_log_det_
     cfg = _spline_cfg(x0, xf, y0, yf, n_bins, circular, identity_boundary_slopes, learn_lower_bound, learn_upper_bound,
                       min_bin_size, min_slope)
     x, parameters, gy, gl = x.contiguous(), parameters.contiguous(), grad_y.contiguous(), grad_log_det_J.contiguous()
+    dt = cfg.dtype
+    _vjp_dtype(x0, (x, 'x'), (parameters, 'parameters'), (gy, 'grad_y'), (gl, 'grad_log_det_J'))
     B, D = x.shape
     gx = torch.empty_like(x)
-    gp = ops.zeros(*parameters.shape, dtype=torch.float32, device=x.device)
+    gp = ops.zeros(*parameters.shape, dtype=dt, device=x.device)
     lay = _lib.ParamLayout(parameters.shape[1], D, 1)
-    _lib.call('tfep_spline_backward', _lib.ptr(x), D, _lib.ptr(parameters), lay, ctypes.byref(cfg.desc),
+    _lib.call('tfep_spline_backward' + ops._sfx(dt), _lib.ptr(x), D, _lib.ptr(parameters), lay, ctypes.byref(cfg.desc),
               _lib.ptr(gy), D, _lib.ptr(gl), _lib.ptr(gp), lay, _lib.ptr(gx), D, B, D, _lib.stream_of(x))
     return gx, gp
 
