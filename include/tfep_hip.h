@@ -194,6 +194,14 @@ int tfep_affine_inverse(const float* y, int64_t ldy, const float* params, tfep_p
                         float* x, int64_t ldx, float* log_det_J, int accumulate,
                         int B, int D, void* stream);
 
+/* Sum-of-squares polynomial transformer (sos.py:26-265): K = n_polynomials squared linear polynomials per feature,
+ * P = 2 K + 1 parameters -- parameter 0 = a0, 1 + 2k = a_k0, 2 + 2k = a_k1 (sos.py:96-99, :275-290):
+ *   y = a0 + x sum a_k0^2 + x^2 sum a_k0 a_k1 + x^3 sum a_k1^2 / 3,   ldj = sum_f log(dy/dx),
+ *   dy/dx = sum_k (a_k0 + a_k1 x)^2  (evaluated as the sum of squares: never negative).
+ * Any n_polynomials >= 1 (the module requires >= 2).  There is no inverse (sos.py:117-120). */
+int tfep_sos_forward(const float* x, int64_t ldx, const float* params, tfep_param_layout layout, int n_polynomials,
+                     float* y, int64_t ldy, float* log_det_J, int accumulate, int B, int D, void* stream);
+
 /* y = x + b with optional periodic wrap, ldj = 0  (affine.py:366-456).
  * periodic_mask: (D) int32, non-zero for wrapped features, or NULL.
  * sign = +1 forward, -1 inverse. */
@@ -265,18 +273,20 @@ int tfep_scatter_columns(const float* src, int64_t lds, const int32_t* idx, int 
 
 typedef enum tfep_fused_kind {
     TFEP_FUSED_AFFINE = 0,   /* P = 2                                         */
-    TFEP_FUSED_SPLINE = 1    /* RQ spline of 8, 5 or 4 bins: see tfep_fused_supported */
+    TFEP_FUSED_SPLINE = 1,   /* RQ spline of 8, 5 or 4 bins: see tfep_fused_supported */
+    TFEP_FUSED_SOS = 3       /* SOS polynomial of K = desc->n_bins = 2 or 3 polynomials (P = 2 K + 1; every other field of
+                                desc is ignored and its arrays may be NULL) */
 } tfep_fused_kind;
 
 /* Feature slots per 16-wide MFMA column group (16). */
 int tfep_fused_tile_features(void);
 /* 1 if (kind, desc) is supported by the fused kernel: the affine transformer; RQ splines of 8, 5 or 4 bins, plain or
  * circular, with or without identity boundary slopes and learnable bounds (11 .. 27 parameters per feature: every layout
- * of spline.py:165-182 at these bin numbers). */
+ * of spline.py:165-182 at these bin numbers); the SOS polynomial transformer of 2 or 3 polynomials. */
 int tfep_fused_supported(int kind, const tfep_spline_desc* desc);
 /* Packed weight rows per column tile of the fused kernel (= tile_n for tfep_mask_k_ranges):
  * P * FT * 16 where FT feature groups of 16 slots share a tile (spline: P = parameters per feature, FT = 1;
- * affine: 2*8*16).
+ * affine: 2*8*16; SOS: 5*3*16 for K = 2, 7*2*16 for K = 3).
  * Packed row of (slot s, parameter p):  tile = s / (16*FT), ft = (s / 16) % FT, j = s % 16,
  *   row = tile * (P*FT*16) + (ft * P + p) * 16 + j. */
 int tfep_fused_tile_columns(int kind, const tfep_spline_desc* desc);
@@ -583,6 +593,12 @@ int tfep_spline_backward(const float* x, int64_t ldx, const float* params, tfep_
                          const float* g_log_det_J, float* gparams, tfep_param_layout glayout,
                          float* gx, int64_t ldgx, int B, int D, void* stream);
 
+/* VJP of tfep_sos_forward (sos.py:226-257): gparams (every parameter of every feature) and gx = gy dy/dx.  There is no
+ * g_log_det_J: the reference marks the SOS log-det non-differentiable (sos.py:222) and its backward ignores that cotangent. */
+int tfep_sos_backward(const float* x, int64_t ldx, const float* params, tfep_param_layout layout, int n_polynomials,
+                      const float* gy, int64_t ldgy, float* gparams, tfep_param_layout glayout, float* gx, int64_t ldgx,
+                      int B, int D, void* stream);
+
 /* VJP of tfep_moebius_forward (moebius.py:374-478): gparams / gx (B, D), same `sign` as the forward. */
 int tfep_moebius_backward(const float* x, int64_t ldx, const float* params, int64_t ldp,
                           int dimension, float max_radius, int unit_sphere, int sign,
@@ -676,6 +692,11 @@ int tfep_affine_backward_f64(const double* x, int64_t ldx, const double* params,
                              const double* gy, int64_t ldgy, const double* g_log_det_J,
                              double* gparams, tfep_param_layout glayout, double* gx, int64_t ldgx,
                              int B, int D, void* stream);
+int tfep_sos_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, int n_polynomials,
+                         double* y, int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream);
+int tfep_sos_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, int n_polynomials,
+                          const double* gy, int64_t ldgy, double* gparams, tfep_param_layout glayout, double* gx,
+                          int64_t ldgx, int B, int D, void* stream);
 /* periodic wrap with Python `%` semantics in fp64: y = (x + sign b) % (upper - lower) + lower on the periodic features. */
 int tfep_volume_preserving_shift_f64(const double* x, int64_t ldx, const double* shift, int64_t ldp,
                                      const int32_t* periodic_mask, double lower, double upper, int sign,

@@ -131,6 +131,9 @@ _SIGNATURES = {
     'tfep_masked_linear_tile_m': (c_int, []),
     'tfep_affine_forward': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
     'tfep_affine_inverse': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+    'tfep_sos_forward': (c_int, [_P, c_int64, _P, ParamLayout, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+    'tfep_sos_backward': (c_int, [_P, c_int64, _P, ParamLayout, c_int, _P, c_int64, _P, ParamLayout, _P, c_int64,
+                                  c_int, c_int, _P]),
     'tfep_volume_preserving_shift': (c_int, [_P, c_int64, _P, c_int64, _P, c_float, c_float, c_int,
                                              _P, c_int64, c_int, c_int, _P]),
     'tfep_spline_n_parameters_per_feature': (c_int, [POINTER(SplineDesc)]),
@@ -231,6 +234,9 @@ _SIGNATURES = {
     'tfep_affine_inverse_f64': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
     'tfep_affine_backward_f64': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, _P, ParamLayout, _P, c_int64,
                                          c_int, c_int, _P]),
+    'tfep_sos_forward_f64': (c_int, [_P, c_int64, _P, ParamLayout, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+    'tfep_sos_backward_f64': (c_int, [_P, c_int64, _P, ParamLayout, c_int, _P, c_int64, _P, ParamLayout, _P, c_int64,
+                                      c_int, c_int, _P]),
     'tfep_volume_preserving_shift_f64': (c_int, [_P, c_int64, _P, c_int64, _P, c_double, c_double, c_int,
                                                  _P, c_int64, c_int, c_int, _P]),
     'tfep_spline_n_parameters_per_feature_f64': (c_int, [POINTER(SplineDescF64)]),

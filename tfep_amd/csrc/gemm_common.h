@@ -4,6 +4,7 @@
 
 #include "common.h"
 #include "spline.h"
+#include "sos.h"
 
 #include <stdlib.h>
 
@@ -13,7 +14,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // EPI_SPLINE_IDB: the RQ-spline epilogue for identity boundary slopes with BOTH bounds learnable -- the one layout whose
 // parameter count (3 K + 1) does not tell it apart from the plain one
-enum Epilogue { EPI_LINEAR = 0, EPI_ELU = 1, EPI_AFFINE = 2, EPI_SPLINE = 3, EPI_ELU_SPLIT = 4, EPI_SPLINE_IDB = 5 };
+// EPI_SOS: the sum-of-squares polynomial transformer, KSPL = K polynomials, P = 2 K + 1
+enum Epilogue { EPI_LINEAR = 0, EPI_ELU = 1, EPI_AFFINE = 2, EPI_SPLINE = 3, EPI_ELU_SPLIT = 4, EPI_SPLINE_IDB = 5, EPI_SOS = 6 };
 constexpr bool epi_is_spline(int epi) { return epi == EPI_SPLINE || epi == EPI_SPLINE_IDB; }
 
 struct FusedArgs {
@@ -180,6 +182,13 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[NR
                             const float ls = acc[ft * P + 1][m][i] + bias_p[1];
                             out = xv * expf(ls) + shift;           // affine.py:321-323
                             ld = (double)ls;
+                        } else if constexpr (EPI == EPI_SOS) {
+                            static_assert(P == 2 * KSPL + 1, "SOS: P = 2 K + 1");
+                            float d;
+                            out = sos_element<KSPL, float>(KSPL, [&](int p) __attribute__((always_inline)) {
+                                return acc[ft * P + p][m][i] + bias_p[p];
+                            }, xv, &d);                                // sos.py:198-224
+                            ld = (double)logf(d);
                         } else {
                             float w[KSPL], h[KSPL], sraw[KSPL + 1], lastp, last2;
                             const SplineFlags sf = spline_flags_of_layout<KSPL, P, EPI == EPI_SPLINE_IDB>(fu.sf);

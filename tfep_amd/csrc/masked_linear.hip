@@ -615,6 +615,7 @@ static int desc_n_params(const tfep_spline_desc* d) {
 
 int tfep_fused_supported(int kind, const tfep_spline_desc* d) {
     if (kind == TFEP_FUSED_AFFINE) return 1;
+    if (kind == TFEP_FUSED_SOS) return d && (d->n_bins == 2 || d->n_bins == 3);        // (n_bins = K polynomials)
     if (kind == TFEP_FUSED_SPLINE && d) {
         if (d->n_bins != 8 && d->n_bins != 5 && d->n_bins != 4) return 0;
         if (d->circular && (d->learn_lower_bound || d->learn_upper_bound)) return 0;       // (not a valid spline)
@@ -626,6 +627,8 @@ int tfep_fused_supported(int kind, const tfep_spline_desc* d) {
 
 int tfep_fused_tile_columns(int kind, const tfep_spline_desc* d) {
     if (kind == TFEP_FUSED_AFFINE) return 16 * 16;      // P = 2, FT = 8
+    if (kind == TFEP_FUSED_SOS && tfep_fused_supported(kind, d))
+        return d->n_bins == 2 ? 16 * 15 : 16 * 14;      // K = 2: P = 5, FT = 3; K = 3: P = 7, FT = 2
     if (kind == TFEP_FUSED_SPLINE && tfep_fused_supported(kind, d)) return 16 * desc_n_params(d);   // FT = 1
     return fail(TFEP_ERR_UNSUPPORTED, "fused: unsupported transformer configuration");
 }
@@ -661,6 +664,19 @@ static int fused_forward(const float* h, int64_t ldh, const float* w, int64_t ld
         g.N = n_feature_slots * P;
         rc = split ? launch_split_fused(g, n_rows_w, kind, n_groups / FT, s)
                    : launch_gemm<2, P * FT, EPI_AFFINE, P, 1>(g, n_rows_w, n_groups / FT, s);
+    } else if (kind == TFEP_FUSED_SOS) {
+        // as many feature groups of P = 2 K + 1 parameters as fit in 16 column groups
+        const int KP = desc->n_bins, P = 2 * KP + 1, FT = 16 / P;
+        TFEP_REQUIRE(n_groups % FT == 0, "fused sos: feature slots must be a multiple of %d", FT * 16);
+        TFEP_REQUIRE(n_rows_w >= n_feature_slots * P, "fused: weight has too few rows");
+        g.N = n_feature_slots * P;
+        g.fu.sf.K = KP;
+        if (split)
+            rc = launch_split_fused(g, n_rows_w, kind, n_groups / FT, s);
+        else if (KP == 2)
+            rc = launch_gemm<2, 15, EPI_SOS, 5, 2>(g, n_rows_w, n_groups / FT, s);
+        else
+            rc = launch_gemm<2, 14, EPI_SOS, 7, 3>(g, n_rows_w, n_groups / FT, s);
     } else {
         const int KS = desc->n_bins, P = desc_n_params(desc);
         TFEP_REQUIRE(feat_tr && desc->x0 && desc->xf && desc->y0 && desc->yf, "fused spline: NULL descriptor arrays");

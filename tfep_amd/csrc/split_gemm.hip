@@ -580,6 +580,12 @@ int launch_split_fused(const GemmArgs& g, int n_rows_w, int kind, int n_col_tile
     int rc = check_split_operands(g);
     if (rc) return rc;
     if (kind == TFEP_FUSED_AFFINE) return launch_split<16, EPI_AFFINE, 2, 1>(g, n_rows_w, n_col_tiles, s);
+    // SOS: 3 (K = 2) or 2 (K = 3) feature groups of 2 K + 1 parameters per column tile (g.fu.sf.K = K)
+    if (kind == TFEP_FUSED_SOS) {
+        if (g.fu.sf.K == 2) return launch_split<15, EPI_SOS, 5, 2>(g, n_rows_w, n_col_tiles, s);
+        if (g.fu.sf.K == 3) return launch_split<14, EPI_SOS, 7, 3>(g, n_rows_w, n_col_tiles, s);
+        return fail(TFEP_ERR_UNSUPPORTED, "fused split: no SOS kernel for %d polynomials", g.fu.sf.K);
+    }
     // one feature group (16 features x P parameters) per column tile: 8, 5 or 4 bins; P = 3 K + 1 for the plain and the
     // circular layout (here); 3 K - 1 .. 3 K + 3 with identity boundary slopes and / or learnable bounds
     // (spline_n_params; split_gemm_layouts.hip, also for identity slopes + both bounds, whose count is 3 K + 1 again)

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "spline.h"
 #include "moebius.h"
+#include "sos.h"
 
 #include <stdarg.h>
 
@@ -195,6 +196,48 @@ __global__ void __launch_bounds__(256) moebius_kernel(const float* __restrict__ 
     if (ldj) store_ldj(ldj, b, acc, accumulate);
 }
 
+// ---------------------------------------------------------------- SOS polynomial (sos.py:198-265; sos.h)
+// K runtime; the log of the sum-of-squares derivative per element, summed in fp64 with the wave butterfly like the others.
+__global__ void __launch_bounds__(256) sos_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ params,
+                                                  tfep_param_layout L, int K, float* __restrict__ y, int64_t ldy,
+                                                  float* __restrict__ ldj, int accumulate, int B, int D) {
+    const int b = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const float* xr = x + (int64_t)b * ldx;
+    const float* pr = params + (int64_t)b * L.ld;
+    float* yr = y + (int64_t)b * ldy;
+    double acc = 0.0;
+    for (int f = lane; f < D; f += 64) {
+        const float* pf = pr + f * L.stride_f;
+        float d;
+        yr[f] = sos_element<0, float>(K, [&](int p) { return pf[p * L.stride_p]; }, xr[f], &d);
+        acc += (double)logf(d);
+    }
+    acc = wave_sum(acc);
+    if (ldj) store_ldj(ldj, b, acc, accumulate);
+}
+
+// VJP: every parameter of every feature and the direct g_x; no log-det cotangent (non-differentiable in the reference).
+__global__ void __launch_bounds__(256) sos_backward_kernel(const float* __restrict__ x, int64_t ldx,
+                                                           const float* __restrict__ params, tfep_param_layout L, int K,
+                                                           const float* __restrict__ gy, int64_t ldgy,
+                                                           float* __restrict__ gparams, tfep_param_layout GL,
+                                                           float* __restrict__ gx, int64_t ldgx, int B, int D) {
+    const int b = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const float* pr = params + (int64_t)b * L.ld;
+    float* gpr = gparams + (int64_t)b * GL.ld;
+    for (int f = lane; f < D; f += 64) {
+        const float* pf = pr + f * L.stride_f;
+        float* gpf = gpr + f * GL.stride_f;
+        gx[(int64_t)b * ldgx + f] = sos_vjp_element<float>(
+            K, [&](int p) { return pf[p * L.stride_p]; }, [&](int p, float v) { gpf[p * GL.stride_p] = v; },
+            x[(int64_t)b * ldx + f], gy[(int64_t)b * ldgy + f]);
+    }
+}
+
 // ---------------------------------------------------------------- periodic embedding (mafembed.py:112-145)
 __global__ void __launch_bounds__(256) periodic_embedding_kernel(const float* __restrict__ x, int64_t ldx,
                                                                  const int32_t* __restrict__ pidx, int n_per,
@@ -280,6 +323,29 @@ int tfep_affine_inverse(const float* y, int64_t ldy, const float* params, tfep_p
     affine_kernel<true><<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(y, ldy, params, layout, x, ldx, log_det_J,
                                                                         accumulate, B, D);
     return check_launch("affine_kernel");
+}
+
+int tfep_sos_forward(const float* x, int64_t ldx, const float* params, tfep_param_layout layout, int n_polynomials,
+                     float* y, int64_t ldy, float* log_det_J, int accumulate, int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "sos: negative size");
+    TFEP_REQUIRE(n_polynomials >= 1, "sos: n_polynomials=%d must be positive", n_polynomials);
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && y, "sos: x/params/y must be non-NULL");
+    sos_kernel<<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, n_polynomials, y, ldy, log_det_J,
+                                                                accumulate, B, D);
+    return check_launch("sos_kernel");
+}
+
+int tfep_sos_backward(const float* x, int64_t ldx, const float* params, tfep_param_layout layout, int n_polynomials,
+                      const float* gy, int64_t ldgy, float* gparams, tfep_param_layout glayout, float* gx, int64_t ldgx,
+                      int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "sos_backward: negative size");
+    TFEP_REQUIRE(n_polynomials >= 1, "sos_backward: n_polynomials=%d must be positive", n_polynomials);
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && gy && gparams && gx, "sos_backward: NULL pointer");
+    sos_backward_kernel<<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, n_polynomials, gy, ldgy,
+                                                                         gparams, glayout, gx, ldgx, B, D);
+    return check_launch("sos_backward_kernel");
 }
 
 int tfep_volume_preserving_shift(const float* x, int64_t ldx, const float* shift, int64_t ldp,

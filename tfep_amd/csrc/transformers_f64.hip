@@ -8,6 +8,7 @@
 // coarse next to the float64 reference).  The spline follows the reference's rules: strict '>' in the bin search, linear
 // continuation along the boundary slope outside the domain (transformers/spline.py:567-650).
 #include "common.h"
+#include "sos.h"
 
 namespace tfep {
 namespace {
@@ -62,6 +63,47 @@ __global__ void __launch_bounds__(256) affine64_backward_kernel(const double* __
         gparams[(int64_t)b * GL.ld + f * GL.stride_f] = g;                                   // d/d shift
         gparams[(int64_t)b * GL.ld + GL.stride_p + f * GL.stride_f] = g * xv * e + gl;       // d/d log_scale
         gx[(int64_t)b * ldgx + f] = g * e;
+    }
+}
+
+// ---------------------------------------------------------------- SOS polynomial (sos.py:198-265; sos.h)
+__global__ void __launch_bounds__(256) sos64_kernel(const double* __restrict__ x, int64_t ldx,
+                                                    const double* __restrict__ params, tfep_param_layout L, int K,
+                                                    double* __restrict__ y, int64_t ldy, double* __restrict__ ldj,
+                                                    int accumulate, int B, int D) {
+    const int b = blockIdx.x * RPB + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const double* xr = x + (int64_t)b * ldx;
+    const double* pr = params + (int64_t)b * L.ld;
+    double* yr = y + (int64_t)b * ldy;
+    double acc = 0.0;
+    for (int f = lane; f < D; f += 64) {
+        const double* pf = pr + f * L.stride_f;
+        double d;
+        yr[f] = sos_element<0, double>(K, [&](int p) { return pf[p * L.stride_p]; }, xr[f], &d);
+        acc += log(d);
+    }
+    acc = wave_sum(acc);
+    if (ldj) store_ldj64(ldj, b, acc, accumulate);
+}
+
+__global__ void __launch_bounds__(256) sos64_backward_kernel(const double* __restrict__ x, int64_t ldx,
+                                                             const double* __restrict__ params, tfep_param_layout L, int K,
+                                                             const double* __restrict__ gy, int64_t ldgy,
+                                                             double* __restrict__ gparams, tfep_param_layout GL,
+                                                             double* __restrict__ gx, int64_t ldgx, int B, int D) {
+    const int b = blockIdx.x * RPB + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const double* pr = params + (int64_t)b * L.ld;
+    double* gpr = gparams + (int64_t)b * GL.ld;
+    for (int f = lane; f < D; f += 64) {
+        const double* pf = pr + f * L.stride_f;
+        double* gpf = gpr + f * GL.stride_f;
+        gx[(int64_t)b * ldgx + f] = sos_vjp_element<double>(
+            K, [&](int p) { return pf[p * L.stride_p]; }, [&](int p, double v) { gpf[p * GL.stride_p] = v; },
+            x[(int64_t)b * ldx + f], gy[(int64_t)b * ldgy + f]);
     }
 }
 
@@ -578,6 +620,29 @@ int launch_spline64(const double* x, int64_t ldx, const double* params, tfep_par
 using namespace tfep;
 
 extern "C" {
+
+int tfep_sos_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, int n_polynomials,
+                         double* y, int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "sos_f64: negative size");
+    TFEP_REQUIRE(n_polynomials >= 1, "sos_f64: n_polynomials=%d must be positive", n_polynomials);
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && y, "sos_f64: x/params/y must be non-NULL");
+    sos64_kernel<<<row_blocks64(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, n_polynomials, y, ldy, log_det_J,
+                                                                    accumulate, B, D);
+    return check_launch("sos64_kernel");
+}
+
+int tfep_sos_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, int n_polynomials,
+                          const double* gy, int64_t ldgy, double* gparams, tfep_param_layout glayout, double* gx,
+                          int64_t ldgx, int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "sos_backward_f64: negative size");
+    TFEP_REQUIRE(n_polynomials >= 1, "sos_backward_f64: n_polynomials=%d must be positive", n_polynomials);
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && gy && gparams && gx, "sos_backward_f64: NULL pointer");
+    sos64_backward_kernel<<<row_blocks64(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, n_polynomials, gy, ldgy,
+                                                                             gparams, glayout, gx, ldgx, B, D);
+    return check_launch("sos64_backward_kernel");
+}
 
 int tfep_affine_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, double* y,
                             int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream) {

@@ -6,7 +6,7 @@ The reference differentiates the flow with eager autograd plus ``MaskedLinearFun
 
   1. recomputes the hidden activations and the transformer parameters for a chunk of the batch
      (so the ``(B, P*D)`` parameter tensor only ever exists for a chunk),
-  2. runs the transformer VJP kernel (``tfep_affine_backward`` / ``tfep_spline_backward``),
+  2. runs the transformer VJP kernel (``tfep_affine_backward`` / ``tfep_spline_backward`` / ``tfep_sos_backward``),
   3. walks the three masked linears backwards with the SAME fp32-MFMA GEMM kernel:
      ``grad_input = g W`` on a transposed packed weight (ELU derivative fused in the epilogue),
      ``grad_weight += g^T x`` on transposed activations, skipping output tiles that the block-triangular
@@ -29,6 +29,7 @@ from ..embeddings.mafembed import MAFEmbedding, PeriodicEmbedding
 from ..transformers.affine import AffineTransformer, VolumePreservingShiftTransformer
 from ..transformers.mixed import MixedTransformer
 from ..transformers.moebius import MoebiusTransformer
+from ..transformers.sos import SOSPolynomialTransformer
 from ..transformers.spline import NeuralSplineTransformer
 
 # bytes of transformer parameters per batch chunk of the backward (TFEP_BACKWARD_CHUNK_GIB, default 8:
@@ -61,7 +62,7 @@ def _embedding_params(layer):
 
 
 def _transformer_supported(tr):
-    if type(tr) in (AffineTransformer, MoebiusTransformer, VolumePreservingShiftTransformer):
+    if type(tr) in (AffineTransformer, MoebiusTransformer, VolumePreservingShiftTransformer, SOSPolynomialTransformer):
         return True
     if type(tr) is NeuralSplineTransformer:
         return True
@@ -76,7 +77,8 @@ def _voidp(t, offset_elems=0):
 
 def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, layout=None, order=None):
     """VJP of ``tr.forward(x, theta[:, th_off:th_off + n_par])``: writes the matching block of ``gtheta`` and
-    ``gx`` (contiguous (B, D)).  ``theta`` / ``gtheta`` have row stride ``ld_theta``."""
+    ``gx`` (contiguous (B, D)).  ``theta`` / ``gtheta`` have row stride ``ld_theta``.  The SOS transformer ignores ``gl``:
+    its log-det is non-differentiable in the reference (sos.py:222), so no gradient flows through it."""
     B, D = x.shape
     dev = x.device
     if type(tr) is MixedTransformer:
@@ -105,6 +107,9 @@ def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, 
         elif type(tr) is AffineTransformer:
             _lib.call('tfep_affine_backward_f64', _lib.ptr(x), D, th, lay, _lib.ptr(gy), D, _lib.ptr(gl), gth, lay,
                       _lib.ptr(gx), D, B, D, stream)
+        elif type(tr) is SOSPolynomialTransformer:
+            _lib.call('tfep_sos_backward_f64', _lib.ptr(x), D, th, lay, int(tr.n_polynomials), _lib.ptr(gy), D, gth, lay,
+                      _lib.ptr(gx), D, B, D, stream)
         elif type(tr) is VolumePreservingShiftTransformer:
             gtheta[:, th_off:th_off + D].copy_(gy)     # y = x + b: the cotangent passes to b and to x unchanged
             gx.copy_(gy)
@@ -117,6 +122,9 @@ def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, 
                   _lib.ptr(gl), gth, lay, _lib.ptr(gx), D, B, D, stream)
     elif type(tr) is AffineTransformer:
         _lib.call('tfep_affine_backward', _lib.ptr(x), D, th, lay, _lib.ptr(gy), D, _lib.ptr(gl), gth, lay,
+                  _lib.ptr(gx), D, B, D, stream)
+    elif type(tr) is SOSPolynomialTransformer:
+        _lib.call('tfep_sos_backward', _lib.ptr(x), D, th, lay, int(tr.n_polynomials), _lib.ptr(gy), D, gth, lay,
                   _lib.ptr(gx), D, B, D, stream)
     elif type(tr) is MoebiusTransformer:
         _lib.call('tfep_moebius_backward', _lib.ptr(x), D, th, ld_theta, int(tr.dimension), float(tr.max_radius),
@@ -236,7 +244,7 @@ class TransformerFunction(torch.autograd.Function):
 
 
 _HIP_TRANSFORMERS = (AffineTransformer, MoebiusTransformer, VolumePreservingShiftTransformer, NeuralSplineTransformer,
-                     MixedTransformer)
+                     MixedTransformer, SOSPolynomialTransformer)
 
 
 def generic_supported(layer):
@@ -276,7 +284,7 @@ def generic_forward(layer, x):
 
 def _elementwise(tr):
     """Transformers whose Jacobian with respect to x is diagonal (one feature in, one feature out)."""
-    if type(tr) in (AffineTransformer, NeuralSplineTransformer, VolumePreservingShiftTransformer):
+    if type(tr) in (AffineTransformer, NeuralSplineTransformer, VolumePreservingShiftTransformer, SOSPolynomialTransformer):
         return True
     return type(tr) is MixedTransformer and all(_elementwise(t) for t in tr._transformers)
 
@@ -480,8 +488,8 @@ def _transpose(src, rows, cols, out):
 def _backward_plan(layer, device):
     """Host-side plan of the backward GEMMs (built once per device).
 
-    Output-layer rows are re-packed FEATURE-MAJOR in degree-sorted feature order (row = slot*P + p) for affine
-    and spline transformers: the rows that feed a tile of hidden units are then one contiguous
+    Output-layer rows are re-packed FEATURE-MAJOR in degree-sorted feature order (row = slot*P + p) for affine,
+    spline and SOS transformers: the rows that feed a tile of hidden units are then one contiguous
     range, so ``grad_input = g W`` skips the masked half of its contraction like the forward does.
     """
     key = ('bwd', str(device))
@@ -498,7 +506,7 @@ def _backward_plan(layer, device):
     n_out = lins[-1].out_features
     P = n_out // n_tr
     i32 = dict(device=device, dtype=torch.int32)
-    bp = dict(sorted_out=type(layer._transformer) in (AffineTransformer, NeuralSplineTransformer))
+    bp = dict(sorted_out=type(layer._transformer) in (AffineTransformer, NeuralSplineTransformer, SOSPolynomialTransformer))
     k_ranges = list(mplan['k_ranges'])
     if bp['sorted_out']:
         deg_tr = made._degrees[-1][:n_tr].cpu()
@@ -826,7 +834,7 @@ def layer_backward(layer, x, gy, gldj, saved=None, need_gx=True):
         else:
             x_tr, gy_tr = xc, gyc
         if sorted_out:
-            # affine / spline: the kernel writes every parameter of every feature; only the padding columns need zeros
+            # affine / spline / SOS: the kernel writes every parameter of every feature; only the padding columns need zeros
             gtheta = torch.empty(Bc, n_out_pad, **f32)
             if n_out_pad > n_out:
                 gtheta[:, n_out:] = 0.0

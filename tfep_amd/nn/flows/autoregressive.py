@@ -5,7 +5,7 @@ Same constructor, buffers (``_transformer_indices``, ``_inverse_masks``, ``_fixe
 
 * generic: ``parameters = conditioner(x)`` then ``transformer(x, parameters)`` -- works with any
   user-supplied conditioner / transformer module (the parameter tensor goes through HBM);
-* fused (MADE conditioner + affine / supported spline transformer): the output layer of MADE
+* fused (MADE conditioner + affine / supported spline / SOS transformer): the output layer of MADE
   and the transformer run in ONE kernel (``tfep_fused_output_transformer_forward``), the
   ``(batch, P*D)`` parameter tensor lives only in MFMA accumulators.
 """
@@ -23,10 +23,12 @@ from ..embeddings.mafembed import PeriodicEmbedding
 from ..transformers.affine import AffineTransformer, VolumePreservingShiftTransformer
 from ..transformers.mixed import MixedTransformer, check_float64_members
 from ..transformers.moebius import MoebiusTransformer
+from ..transformers.sos import SOSPolynomialTransformer
 from ..transformers.spline import NeuralSplineTransformer
 from .sequential import _side_stream
 
-_FUSED_AFFINE, _FUSED_SPLINE, _FUSED_MIXED = 0, 1, 2      # (0 / 1: tfep_fused_kind; 2: one launch per group)
+# (0 / 1 / 3: tfep_fused_kind; 2: one launch per group)
+_FUSED_AFFINE, _FUSED_SPLINE, _FUSED_MIXED, _FUSED_SOS = 0, 1, 2, 3
 
 
 class AutoregressiveFlow(torch.nn.Module):
@@ -153,9 +155,11 @@ class AutoregressiveFlow(torch.nn.Module):
     @staticmethod
     def _transformer_fused_kind(tr):
         """Fused epilogue of one transformer (the rule of tfep_fused_supported): affine; RQ splines of 8, 5 or 4 bins in
-        every layout (at most 27 parameters per feature: 8 bins with both bounds learnable)."""
+        every layout (at most 27 parameters per feature: 8 bins with both bounds learnable); SOS of 2 or 3 polynomials."""
         if type(tr) is AffineTransformer:
             return _FUSED_AFFINE
+        if type(tr) is SOSPolynomialTransformer and tr.n_polynomials in (2, 3):
+            return _FUSED_SOS
         if type(tr) is NeuralSplineTransformer and tr.host()['n_bins'] in (4, 5, 8) and tr.n_parameters_per_feature <= 27:
             return _FUSED_SPLINE
         return None
@@ -270,7 +274,8 @@ class AutoregressiveFlow(torch.nn.Module):
             P_real = 1 if self._is_plain_shift(t_g) else P                       # rows the conditioner has (the shift:
             if off + P_real * n_g > last.out_features:                           # its log-scale rows stay zero)
                 raise ValueError('conditioner output does not match the transformer parameters')
-            desc = t_g.config(device).desc if k_g == _FUSED_SPLINE else None
+            desc = t_g.config(device).desc if k_g == _FUSED_SPLINE else (
+                ops.sos_fused_desc(t_g.n_polynomials) if k_g == _FUSED_SOS else None)
             tile_cols = lib.tfep_fused_tile_columns(k_g, ctypes.byref(desc) if desc is not None else None)
             FT = tile_cols // (16 * P)
             n_slots = ops.round_up(n_g, 16 * FT)
@@ -327,6 +332,8 @@ class AutoregressiveFlow(torch.nn.Module):
                 cfg, hst = grp['transformer'].config(x.device), grp['transformer'].host()
                 spl = (cfg.x0, cfg.xf, cfg.y0, cfg.yf, hst['n_bins'], hst['circular'], hst['identity'], hst['learn_lower'],
                        hst['learn_upper'], hst['min_bin'], hst['min_slope'])
+            elif grp['kind'] == _FUSED_SOS:      # (n_bins carries the number of polynomials)
+                spl = (None, None, None, None, grp['transformer'].n_polynomials, False, False, False, False, 0.0, 0.0)
             else:
                 spl = (None, None, None, None, 0, False, False, False, False, 0.0, 0.0)
             r0, r1 = grp['base'], grp['base'] + grp['n_rows']

@@ -3,3 +3,4 @@ from .affine import AffineTransformer, VolumePreservingShiftTransformer  # noqa:
 from .spline import NeuralSplineTransformer  # noqa: F401
 from .moebius import MoebiusTransformer  # noqa: F401
 from .mixed import MixedTransformer  # noqa: F401
+from .sos import SOSPolynomialTransformer  # noqa: F401

@@ -61,6 +61,29 @@ def affine(x, parameters, inverse=False, log_det_J=None):
     return y, ldj
 
 
+def sos(x, parameters, n_polynomials, log_det_J=None):
+    """SOSPolynomialTransformer.forward (reference sos.py:81-108): ``parameters`` (B, (2 K + 1) D) in the reference layout.
+    float64 tensors run on the float64 kernels."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    B, D = x.shape
+    K = int(n_polynomials)
+    if K < 1:
+        raise ValueError(f'n_polynomials must be positive, got {K}')
+    parameters, ldp = _check_params(parameters, B, (2 * K + 1) * D, dtype=dt)
+    y = torch.empty(B, D, dtype=x.dtype, device=x.device)
+    ldj, acc = _ldj_out(log_det_J, B, x, dt)
+    call('tfep_sos_forward' + _sfx(dt), ptr(x), ldx, ptr(parameters), _layout(ldp, D), K, ptr(y), max(D, 1), ptr(ldj), acc,
+         B, D, stream_of(x))
+    return y, ldj
+
+
+def sos_fused_desc(n_polynomials):
+    """The descriptor argument of the fused output-layer kernel for the SOS transformer (kind TFEP_FUSED_SOS): ``n_bins``
+    carries the number of polynomials, nothing else is read."""
+    return SplineDesc(None, None, None, None, int(n_polynomials), 0, 0, 0, 0, 0.0, 0.0)
+
+
 def volume_preserving_shift(x, shift, periodic_mask=None, limits=(0.0, 1.0), inverse=False):
     """VolumePreservingShiftTransformer (reference affine.py:366-456); log-det is zero."""
     dt = _dtype(x)

@@ -7,6 +7,7 @@ formula whose backward is itself a registered op.  There is no CPU implementatio
 in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the rest of the package.
 
   tfep::affine_forward / affine_inverse / affine_backward            reference transformers/affine.py:281-363
+  tfep::sos_forward / sos_backward                                    reference transformers/sos.py:81-265 (SOS_OPS)
   tfep::spline_forward / spline_inverse / spline_backward            reference transformers/spline.py:184-261, 424-564
   tfep::moebius_forward / moebius_inverse / moebius_backward         reference transformers/moebius.py:104-147, 374-478
   tfep::masked_linear / masked_linear_backward                       reference masked.py:220-302, 351-404
@@ -91,6 +92,48 @@ def _affine_bwd(ctx, gy, gl):
 
 
 affine_forward.register_autograd(_affine_bwd, setup_context=_save_xp)
+
+
+# ============================================================================= sum-of-squares polynomial
+
+@custom_op('tfep::sos_forward', mutates_args=(), device_types=_DEV)
+def sos_forward(x: Tensor, parameters: Tensor, n_polynomials: int) -> Tuple[Tensor, Tensor]:
+    return ops.sos(x, parameters, n_polynomials)
+
+
+@custom_op('tfep::sos_backward', mutates_args=(), device_types=_DEV)
+def sos_backward(x: Tensor, parameters: Tensor, n_polynomials: int, grad_y: Tensor) -> Tuple[Tensor, Tensor]:
+    """VJP of ``sos_forward`` for the cotangent of y; the log-det has none (non-differentiable, reference sos.py:222)."""
+    x, parameters, gy = x.contiguous(), parameters.contiguous(), grad_y.contiguous()
+    dt = _vjp_dtype(x, (x, 'x'), (parameters, 'parameters'), (gy, 'grad_y'))
+    B, D = x.shape
+    if parameters.shape != (B, (2 * n_polynomials + 1) * D) or gy.shape != x.shape:
+        raise ValueError('sos_backward: parameters must be (B, (2 K + 1) D) and grad_y of the shape of x')
+    gx = torch.empty_like(x)
+    gp = torch.empty_like(parameters)
+    lay = _lib.ParamLayout(parameters.shape[1], D, 1)
+    _lib.call('tfep_sos_backward' + ops._sfx(dt), _lib.ptr(x), D, _lib.ptr(parameters), lay, int(n_polynomials), _lib.ptr(gy),
+              D, _lib.ptr(gp), lay, _lib.ptr(gx), D, B, D, _lib.stream_of(x))
+    return gx, gp
+
+
+sos_forward.register_fake(lambda x, parameters, n_polynomials: _pair_like(x))
+sos_backward.register_fake(lambda x, parameters, n_polynomials, gy: (x.new_empty(x.shape), parameters.new_empty(parameters.shape)))
+
+
+def _sos_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1])
+    ctx.n_polynomials = inputs[2]
+    ctx.mark_non_differentiable(output[1])           # the log-det (reference sos.py:222)
+
+
+def _sos_bwd(ctx, gy, gl):
+    x, p = ctx.saved_tensors
+    gy = torch.zeros_like(x) if gy is None else gy   # (gl is ignored: the log-det carries no gradient)
+    return (*torch.ops.tfep.sos_backward(x, p, ctx.n_polynomials, gy), None)
+
+
+sos_forward.register_autograd(_sos_bwd, setup_context=_sos_setup)
 
 
 # ============================================================================= rational-quadratic spline
@@ -319,6 +362,8 @@ def _fused_launch(h, h_inv_scale, w, w_inv_scale, bias, k_ranges, tile_order, ki
     if kind == 1:
         desc = _spline_cfg(x0, xf, y0, yf, n_bins, circular, identity_boundary_slopes, learn_lower_bound,
                            learn_upper_bound, min_bin_size, min_slope).desc
+    elif kind == 3:
+        desc = ops.sos_fused_desc(n_bins)                 # SOS: n_bins = number of polynomials
     tail = (_lib.ptr(bias), _lib.ptr(k_ranges), _lib.ptr(tile_order), kind,
             ctypes.byref(desc) if desc is not None else None,
             _lib.ptr(x), ldx, _lib.ptr(y), D, _lib.ptr(feat_index), _lib.ptr(feat_tr),
@@ -338,8 +383,8 @@ def fused_output_transformer(h: Tensor, h_inv_scale: Optional[Tensor], w: Tensor
                              x0: Optional[Tensor], xf: Optional[Tensor], y0: Optional[Tensor], yf: Optional[Tensor],
                              n_bins: int, circular: bool, identity_boundary_slopes: bool, learn_lower_bound: bool,
                              learn_upper_bound: bool, min_bin_size: float, min_slope: float) -> Tuple[Tensor, Tensor]:
-    """``tfep_fused_output_transformer_forward[_split]``: the MADE output-layer GEMM with the affine (kind 0) or RQ-spline
-    (kind 1) transformer and the log-det in its epilogue.  ``h`` / ``w``: last hidden activations and packed output
+    """``tfep_fused_output_transformer_forward[_split]``: the MADE output-layer GEMM with the affine (kind 0), RQ-spline
+    (kind 1) or SOS (kind 3, ``n_bins`` = number of polynomials) transformer and the log-det in its epilogue.  ``h`` / ``w``: last hidden activations and packed output
     weights -- split-f16 rows when ``h_inv_scale`` / ``w_inv_scale`` are given, fp32 otherwise.  ``y_init``: the input
     with its fixed features (copied through), or None when every feature is transformed."""
     y = y_init.clone() if y_init is not None else torch.empty(x.shape, dtype=x.dtype, device=x.device)
@@ -389,3 +434,5 @@ def _(target_potentials, log_det_J, ref_potentials, log_weights, bias, kT, ignor
 OPS = ('affine_forward', 'affine_inverse', 'affine_backward', 'spline_forward', 'spline_inverse', 'spline_backward',
        'moebius_forward', 'moebius_inverse', 'moebius_backward', 'masked_linear', 'masked_linear_backward',
        'fused_output_transformer', 'fused_output_transformer_', 'tfep_reduce')
+# (a tuple of their own: OPS is the list the existing op tests iterate over)
+SOS_OPS = ('sos_forward', 'sos_backward')

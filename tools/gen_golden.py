@@ -1308,6 +1308,86 @@ def gen_pca():
     np.savez_compressed(os.path.join(OUT, 'pca.npz'), **out)
 
 
+# -----------------------------------------------------------------------------
+# SOS polynomial transformer: transformer, 2-layer flow, mixed SOS + spline flow
+# -----------------------------------------------------------------------------
+
+def sos_flows(D=10):
+    """The flow configurations of sos.npz: name -> constructor(dtype)."""
+    from tfep.nn.conditioners.made import generate_degrees as gd
+    from tfep.nn.transformers.sos import SOSPolynomialTransformer
+    return {
+        'flow': lambda dt: SequentialFlow(
+            MAF(degrees_in=gd(D, 'ascending'), transformer=SOSPolynomialTransformer(2), initialize_identity=False),
+            MAF(degrees_in=gd(D, 'descending'), transformer=SOSPolynomialTransformer(3), weight_norm=False,
+                initialize_identity=False)),
+        'mixed': lambda dt: SequentialFlow(
+            MAF(degrees_in=gd(D, 'ascending'),
+                transformer=MixedTransformer(
+                    transformers=[SOSPolynomialTransformer(2),
+                                  NeuralSplineTransformer(x0=torch.full((5,), -4.0).to(dt), xf=torch.full((5,), 4.0).to(dt),
+                                                          n_bins=8)],
+                    indices=[[0, 2, 4, 6, 8], [1, 3, 5, 7, 9]]),
+                initialize_identity=False)),
+    }
+
+
+def gen_sos():
+    """Reference SOSPolynomialTransformer (sos.py) at the transformer level -- y, log-det and the gradients of a weighted sum
+    of y by reference autograd, float64 and float32 -- and the flows of ``sos_flows``: forward and the gradients of
+    BoltzmannKLDivLoss(u(y), log_det_J) with u(y) = sum_f (c_f y_f^2 + d_f y_f), float64 and float32."""
+    from tfep.nn.transformers.sos import SOSPolynomialTransformer
+    out = {}
+    B = 6
+    for K in (2, 3, 5):
+        for D in (2, 5, 8):
+            name = f'tr/K{K}_D{D}'
+            g = gen(100 + 10 * K + D)
+            x = torch.randn(B, D, generator=g) * 1.5
+            par = torch.randn(B, (2 * K + 1) * D, generator=g) * 0.8
+            w = torch.randn(B, D, generator=g)
+            out[f'{name}/x'], out[f'{name}/par'], out[f'{name}/w'] = npy(x), npy(par), npy(w)
+            for tag, dt in (('f64', torch.float64), ('f32', torch.float32)):
+                xx = x.to(dt).requires_grad_(True)
+                pp = par.to(dt).requires_grad_(True)
+                y, ldj = SOSPolynomialTransformer(K)(xx, pp)
+                assert not ldj.requires_grad
+                (y * w.to(dt)).sum().backward()
+                out[f'{name}/y_{tag}'], out[f'{name}/ldj_{tag}'] = npy(y), npy(ldj)
+                out[f'{name}/gx_{tag}'], out[f'{name}/gpar_{tag}'] = npy(xx.grad), npy(pp.grad)
+
+    def quad(y, c, d):
+        return (c * y ** 2 + d * y).sum(dim=1)
+
+    D, B = 10, 32
+    for name, make in sos_flows(D).items():
+        torch.manual_seed(40)
+        f32 = make(torch.float32)
+        perturb_weight_g(f32, 41)
+        g = gen(42)
+        x = torch.randn(B, D, generator=g)
+        c = torch.rand(D, generator=g) * 0.3
+        d = torch.randn(D, generator=g) * 0.2
+        sd = {k: v.clone() for k, v in f32.state_dict().items()}
+        with f64():
+            m64 = make(torch.float64)
+            m64.load_state_dict(to_double_sd(sd))
+        for tag, m, dt in (('f64', m64, torch.float64), ('f32', f32, torch.float32)):
+            xx = x.to(dt).requires_grad_(True)
+            y, ldj = m(xx)
+            loss = BoltzmannKLDivLoss()(quad(y, c.to(dt), d.to(dt)), ldj)
+            loss.backward()
+            out[f'{name}/y_{tag}'], out[f'{name}/ldj_{tag}'] = npy(y), npy(ldj)
+            out[f'{name}/loss_{tag}'], out[f'{name}/gx_{tag}'] = npy(loss), npy(xx.grad)
+            for k, p in m.named_parameters():
+                out[f'{name}/grad_{tag}/{k}'] = npy(p.grad)
+        out[f'{name}/x'], out[f'{name}/c'], out[f'{name}/d'] = npy(x), npy(c), npy(d)
+        for k, v in sd.items():
+            if not k.endswith('.mask'):
+                out[f'{name}/sd/{k}'] = npy(v)
+    np.savez_compressed(os.path.join(OUT, 'sos.npz'), **out)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
     if len(sys.argv) > 1:
