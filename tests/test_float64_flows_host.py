@@ -82,6 +82,31 @@ def test_float64_argument_errors_before_launch():
     assert lib.tfep_scatter_columns_f64(None, 4, None, 0, None, 4, 3, None) == 0
 
 
+@pytest.mark.parametrize('sfx', ['', '_f64'])
+def test_float32_and_float64_twins_refuse_the_same_arguments(sfx):
+    # the checks the float32 entry points share with their _f64 twins; every call fails before a launch
+    def refused(match, fn, *args):
+        with pytest.raises(ValueError, match=f'{fn[5:]}{sfx}: {match}'):
+            _lib.call(fn + sfx, *args)
+
+    for B, D in ((-1, 4), (2, -4)):
+        refused('negative size', 'tfep_volume_preserving_shift', FAKE, 4, FAKE, 4, None, 0.0, 1.0, 1, FAKE, 4, B, D, None)
+    for B, n_per, n_non in ((-1, 1, 1), (2, -1, 1), (2, 1, -1)):
+        refused('negative size', 'tfep_periodic_embedding', FAKE, 4, FAKE, n_per, FAKE, n_non, 0.0, 1.0, FAKE, 4, B, None)
+        refused('negative size', 'tfep_periodic_embedding_backward', FAKE, 4, FAKE, n_per, FAKE, n_non, 0.0, 1.0, FAKE, 4,
+                FAKE, 4, B, None)
+    refused('empty period', 'tfep_periodic_embedding', FAKE, 4, FAKE, 1, None, 0, 1.0, 1.0, FAKE, 2, 2, None)
+    refused('empty period', 'tfep_periodic_embedding_backward', FAKE, 4, FAKE, 1, None, 0, 1.0, 1.0, FAKE, 2, FAKE, 4, 2,
+            None)
+    refused('periodic_indices is NULL', 'tfep_periodic_embedding_backward', FAKE, 4, None, 1, None, 0, 0.0, 1.0, FAKE, 2,
+            FAKE, 4, 2, None)
+    refused('nonperiodic_indices is NULL', 'tfep_periodic_embedding_backward', FAKE, 4, None, 0, None, 1, 0.0, 1.0, FAKE, 2,
+            FAKE, 4, 2, None)
+    for fn in ('tfep_gather_columns', 'tfep_scatter_columns'):
+        for B, n_idx in ((-1, 2), (3, -2)):
+            refused('negative size', fn, FAKE, 4, FAKE, n_idx, FAKE, 4, B, None)
+
+
 def test_float64_spline_config_validates_on_the_host():
     x0 = torch.zeros(3, dtype=torch.float64)
     with pytest.raises(_lib.TfepHipError, match='no CPU fallback'):

@@ -5,9 +5,12 @@
 //
 // Launch shape as the forward transformer kernels: one wavefront per sample row, lanes walk the
 // features (coalesced per parameter row); all derivative arithmetic in fp64.
+// Affine VJP, periodic-embedding VJP, transpose and weight-norm backward are templates on the element type: the float
+// instantiation serves the float32 entry points, the double one their _f64 twins.
 #include "common.h"
 #include "spline.h"
 #include "fp64_fast.h"
+#include "embedding.h"
 
 namespace tfep {
 
@@ -15,15 +18,16 @@ constexpr int ROWS_PER_BLOCK_B = 4;
 static inline unsigned row_blocks_b(int B) { return (unsigned)((B + ROWS_PER_BLOCK_B - 1) / ROWS_PER_BLOCK_B); }
 
 // ---------------------------------------------------------------- transpose (LDS tiled, 32 x 32)
-__global__ void __launch_bounds__(256) transpose_kernel(const float* __restrict__ in, int64_t ld_in, int R, int C,
-                                                        float* __restrict__ out, int64_t ld_out) {
-    __shared__ float tile[32][33];
+template <typename T>
+__global__ void __launch_bounds__(256) transpose_kernel(const T* __restrict__ in, int64_t ld_in, int R, int C,
+                                                        T* __restrict__ out, int64_t ld_out) {
+    __shared__ T tile[32][33];
     const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
 #pragma unroll
     for (int i = 0; i < 32; i += 8) {
         const int r = r0 + ty + i, c = c0 + tx;
-        tile[ty + i][tx] = (r < R && c < C) ? in[(int64_t)r * ld_in + c] : 0.f;
+        tile[ty + i][tx] = (r < R && c < C) ? in[(int64_t)r * ld_in + c] : T(0);
     }
     __syncthreads();
 #pragma unroll
@@ -119,21 +123,22 @@ __global__ void __launch_bounds__(CS_COLS * CS_SLICES) colsum_absmax_kernel(cons
 }
 
 // ---------------------------------------------------------------- affine backward (affine.py:321-323)
-__global__ void __launch_bounds__(256) affine_backward_kernel(const float* __restrict__ x, int64_t ldx,
-                                                              const float* __restrict__ params, tfep_param_layout L,
-                                                              const float* __restrict__ gy, int64_t ldgy,
-                                                              const float* __restrict__ gldj,
-                                                              float* __restrict__ gparams, tfep_param_layout GL,
-                                                              float* __restrict__ gx, int64_t ldgx, int B, int D) {
+template <typename T>
+__global__ void __launch_bounds__(256) affine_backward_kernel(const T* __restrict__ x, int64_t ldx,
+                                                              const T* __restrict__ params, tfep_param_layout L,
+                                                              const T* __restrict__ gy, int64_t ldgy,
+                                                              const T* __restrict__ gldj, T* __restrict__ gparams,
+                                                              tfep_param_layout GL, T* __restrict__ gx, int64_t ldgx,
+                                                              int B, int D) {
     const int b = blockIdx.x * ROWS_PER_BLOCK_B + (threadIdx.x >> 6);
     if (b >= B) return;
     const int lane = threadIdx.x & 63;
-    const float gl = gldj ? gldj[b] : 0.f;
+    const T gl = gldj ? gldj[b] : T(0);
     for (int f = lane; f < D; f += 64) {
-        const float ls = params[(int64_t)b * L.ld + L.stride_p + f * L.stride_f];
-        const float g = gy[(int64_t)b * ldgy + f];
-        const float e = expf(ls);
-        const float xv = x[(int64_t)b * ldx + f];
+        const T ls = params[(int64_t)b * L.ld + L.stride_p + f * L.stride_f];
+        const T g = gy[(int64_t)b * ldgy + f];
+        const T e = exp(ls);
+        const T xv = x[(int64_t)b * ldx + f];
         gparams[(int64_t)b * GL.ld + f * GL.stride_f] = g;                                   // d/d shift
         gparams[(int64_t)b * GL.ld + GL.stride_p + f * GL.stride_f] = g * xv * e + gl;       // d/d log_scale
         gx[(int64_t)b * ldgx + f] = g * e;
@@ -459,24 +464,24 @@ __global__ void __launch_bounds__(256, 3) spline_backward_kernel(const float* __
 //   gv[o,i] = M (g/n) gW - g v / n^3 * sum_j gW M v
 // with the reference's hooks: gv = 0 where M == 0, gg = 0 for fully-masked rows (masked.py:401-402, :429).
 // Without weight norm (g == NULL): gweight = gW o M (masked.py:293-297).
-__global__ void __launch_bounds__(256) weight_norm_backward_kernel(const float* __restrict__ gw_packed, int64_t ldw,
-                                                                   const float* __restrict__ v,
-                                                                   const float* __restrict__ g,
-                                                                   const float* __restrict__ mask, int N, int K,
+template <typename T>
+__global__ void __launch_bounds__(256) weight_norm_backward_kernel(const T* __restrict__ gw_packed, int64_t ldw,
+                                                                   const T* __restrict__ v, const T* __restrict__ g,
+                                                                   const T* __restrict__ mask, int N, int K,
                                                                    const int32_t* __restrict__ row_of_out,
                                                                    const int32_t* __restrict__ col_of_in,
-                                                                   float* __restrict__ gv, float* __restrict__ gg) {
+                                                                   T* __restrict__ gv, T* __restrict__ gg) {
     const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (o >= N) return;
     const int lane = threadIdx.x & 63;
-    const float* vr = v + (int64_t)o * K;
-    const float* mr = mask ? mask + (int64_t)o * K : nullptr;
-    const float* gr = gw_packed + (int64_t)(row_of_out ? row_of_out[o] : o) * ldw;
-    float* gvr = gv + (int64_t)o * K;
+    const T* vr = v + (int64_t)o * K;
+    const T* mr = mask ? mask + (int64_t)o * K : nullptr;
+    const T* gr = gw_packed + (int64_t)(row_of_out ? row_of_out[o] : o) * ldw;
+    T* gvr = gv + (int64_t)o * K;
     if (!g) {
         for (int i = lane; i < K; i += 64) {
-            const float gwv = gr[col_of_in ? col_of_in[i] : i];
-            gvr[i] = (mr && mr[i] == 0.f) ? 0.f : gwv;
+            const T gwv = gr[col_of_in ? col_of_in[i] : i];
+            gvr[i] = (mr && mr[i] == T(0)) ? T(0) : gwv;
         }
         return;
     }
@@ -484,7 +489,7 @@ __global__ void __launch_bounds__(256) weight_norm_backward_kernel(const float* 
     for (int i = lane; i < K; i += 64) {
         const double vv = vr[i];
         ss += vv * vv;
-        const bool live = !mr || mr[i] != 0.f;
+        const bool live = !mr || mr[i] != T(0);
         if (live) {
             dot += (double)gr[col_of_in ? col_of_in[i] : i] * vv;
             msum += 1.0;
@@ -498,12 +503,12 @@ __global__ void __launch_bounds__(256) weight_norm_backward_kernel(const float* 
     const double gg_o = dead ? 0.0 : dot / n;
     const double go = (double)g[o];
     for (int i = lane; i < K; i += 64) {
-        const bool live = !mr || mr[i] != 0.f;
+        const bool live = !mr || mr[i] != T(0);
         double out = 0.0;
         if (live && !dead) out = go / n * (double)gr[col_of_in ? col_of_in[i] : i] - go * (double)vr[i] * dot / (n * n * n);
-        gvr[i] = (float)out;
+        gvr[i] = (T)out;
     }
-    if (lane == 0) gg[o] = (float)gg_o;
+    if (lane == 0) gg[o] = (T)gg_o;
 }
 
 // The same for a layer whose mask rows are prefixes of its packed columns (col_cut, see tfep_masked_weight_prepare_split):
@@ -649,30 +654,6 @@ __global__ void __launch_bounds__(WNB_THREADS) weight_norm_backward_prefix_kerne
     if (g && tid == 0) gg[o] = (float)gg_o;
 }
 
-// ---------------------------------------------------------------- periodic embedding backward
-// out = [x_non..., cos t, sin t, ...], t = (x - lower) * scale  ->  gx[p] = (-sin t g_cos + cos t g_sin) * scale
-__global__ void __launch_bounds__(256) periodic_embedding_backward_kernel(const float* __restrict__ x, int64_t ldx,
-                                                                          const int32_t* __restrict__ pidx, int n_per,
-                                                                          const int32_t* __restrict__ nidx, int n_non,
-                                                                          float lower, float scale,
-                                                                          const float* __restrict__ gout, int64_t ldg,
-                                                                          float* __restrict__ gx, int64_t ldgx, int B) {
-    const int n_src = n_non + n_per;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * n_src) return;
-    const int b = (int)(i / n_src), j = (int)(i % n_src);
-    if (j < n_non) {
-        gx[(int64_t)b * ldgx + nidx[j]] = gout[(int64_t)b * ldg + j];
-    } else {
-        const int q = j - n_non;
-        const float t = (x[(int64_t)b * ldx + pidx[q]] - lower) * scale;
-        float sn, cs;
-        sincosf(t, &sn, &cs);
-        const float gc = gout[(int64_t)b * ldg + n_non + 2 * q], gs = gout[(int64_t)b * ldg + n_non + 2 * q + 1];
-        gx[(int64_t)b * ldgx + pidx[q]] = (-sn * gc + cs * gs) * scale;
-    }
-}
-
 // ---------------------------------------------------------------- Moebius VJP (moebius.py:374-478)
 // Reverse mode through the closed-form forward of moebius_kernel (transformers.hip); one lane per vector.
 constexpr int MOEBIUS_MAX_DIM_B = 8;
@@ -798,6 +779,57 @@ __global__ void __launch_bounds__(256) add_inplace_kernel(const float* __restric
     out[(int64_t)b * ldo + c] += in[(int64_t)b * ldi + c];
 }
 
+// Launchers shared by the float32 entry points and their _f64 twins; `who` prefixes the error messages.
+template <typename T>
+static int launch_transpose(const char* who, const T* in, int64_t ld_in, int R, int C, T* out, int64_t ld_out, void* stream) {
+    TFEP_REQUIRE(R >= 0 && C >= 0 && ld_in >= C && ld_out >= R, "%s: bad sizes", who);
+    if (R == 0 || C == 0) return TFEP_OK;
+    TFEP_REQUIRE(in && out, "%s: NULL pointer", who);
+    dim3 grid((unsigned)((C + 31) / 32), (unsigned)((R + 31) / 32));
+    transpose_kernel<T><<<grid, 256, 0, (hipStream_t)stream>>>(in, ld_in, R, C, out, ld_out);
+    return check_launch("transpose_kernel");
+}
+
+template <typename T>
+static int launch_affine_backward(const char* who, const T* x, int64_t ldx, const T* params, tfep_param_layout L, const T* gy,
+                                  int64_t ldgy, const T* gldj, T* gparams, tfep_param_layout GL, T* gx, int64_t ldgx, int B,
+                                  int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "%s: negative size", who);
+    if (B == 0 || D == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && gy && gparams && gx, "%s: NULL pointer", who);
+    affine_backward_kernel<T><<<row_blocks_b(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, L, gy, ldgy, gldj, gparams, GL,
+                                                                                 gx, ldgx, B, D);
+    return check_launch("affine_backward_kernel");
+}
+
+template <typename T>
+static int launch_weight_norm_backward(const char* who, const T* gw_packed, int64_t ldw, const T* v, const T* g,
+                                       const T* mask, int N, int K, const int32_t* row_of_out, const int32_t* col_of_in,
+                                       T* gv, T* gg, void* stream) {
+    TFEP_REQUIRE(N >= 0 && K >= 0, "%s: negative size", who);
+    if (N == 0 || K == 0) return TFEP_OK;
+    TFEP_REQUIRE(gw_packed && v && gv && (!g || gg), "%s: NULL pointer", who);
+    weight_norm_backward_kernel<T><<<(unsigned)((N + 3) / 4), 256, 0, (hipStream_t)stream>>>(gw_packed, ldw, v, g, mask, N, K,
+                                                                                            row_of_out, col_of_in, gv, gg);
+    return check_launch("weight_norm_backward_kernel");
+}
+
+template <typename T>
+static int launch_periodic_embedding_backward(const char* who, const T* x, int64_t ldx, const int32_t* pidx, int n_per,
+                                              const int32_t* nidx, int n_non, T lower, T upper, const T* gout, int64_t ldg,
+                                              T* gx, int64_t ldgx, int B, void* stream) {
+    TFEP_REQUIRE(B >= 0 && n_per >= 0 && n_non >= 0, "%s: negative size", who);
+    TFEP_REQUIRE(upper != lower, "%s: empty period", who);
+    const int64_t n = (int64_t)B * (n_per + n_non);
+    if (n == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && gout && gx, "%s: NULL pointer", who);
+    TFEP_REQUIRE(n_per == 0 || pidx, "%s: periodic_indices is NULL", who);
+    TFEP_REQUIRE(n_non == 0 || nidx, "%s: nonperiodic_indices is NULL", who);
+    periodic_embedding_kernel<T, true><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        x, ldx, pidx, n_per, nidx, n_non, lower, embedding_scale(lower, upper), gout, ldg, gx, ldgx, B);
+    return check_launch("periodic_embedding_kernel");
+}
+
 }  // namespace tfep
 
 using namespace tfep;
@@ -805,12 +837,11 @@ using namespace tfep;
 extern "C" {
 
 int tfep_transpose(const float* in, int64_t ld_in, int R, int C, float* out, int64_t ld_out, void* stream) {
-    TFEP_REQUIRE(R >= 0 && C >= 0 && ld_in >= C && ld_out >= R, "transpose: bad sizes");
-    if (R == 0 || C == 0) return TFEP_OK;
-    TFEP_REQUIRE(in && out, "transpose: NULL pointer");
-    dim3 grid((unsigned)((C + 31) / 32), (unsigned)((R + 31) / 32));
-    transpose_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(in, ld_in, R, C, out, ld_out);
-    return check_launch("transpose_kernel");
+    return launch_transpose("transpose", in, ld_in, R, C, out, ld_out, stream);
+}
+
+int tfep_transpose_f64(const double* in, int64_t ld_in, int R, int C, double* out, int64_t ld_out, void* stream) {
+    return launch_transpose("transpose_f64", in, ld_in, R, C, out, ld_out, stream);
 }
 
 int tfep_column_sums_absmax(const float* in, int64_t ld, int R, int C, float* out, int accumulate, float* absmax, void* stream) {
@@ -840,12 +871,15 @@ int tfep_add_inplace(const float* in, int64_t ld_in, float* out, int64_t ld_out,
 int tfep_affine_backward(const float* x, int64_t ldx, const float* params, tfep_param_layout layout, const float* gy,
                          int64_t ldgy, const float* g_log_det_J, float* gparams, tfep_param_layout glayout, float* gx,
                          int64_t ldgx, int B, int D, void* stream) {
-    TFEP_REQUIRE(B >= 0 && D >= 0, "affine_backward: negative size");
-    if (B == 0 || D == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && gy && gparams && gx, "affine_backward: NULL pointer");
-    affine_backward_kernel<<<row_blocks_b(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, gy, ldgy, g_log_det_J,
-                                                                            gparams, glayout, gx, ldgx, B, D);
-    return check_launch("affine_backward_kernel");
+    return launch_affine_backward("affine_backward", x, ldx, params, layout, gy, ldgy, g_log_det_J, gparams, glayout, gx, ldgx,
+                                  B, D, stream);
+}
+
+int tfep_affine_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, const double* gy,
+                             int64_t ldgy, const double* g_log_det_J, double* gparams, tfep_param_layout glayout, double* gx,
+                             int64_t ldgx, int B, int D, void* stream) {
+    return launch_affine_backward("affine_backward_f64", x, ldx, params, layout, gy, ldgy, g_log_det_J, gparams, glayout, gx,
+                                  ldgx, B, D, stream);
 }
 
 int tfep_spline_backward(const float* x, int64_t ldx, const float* params, tfep_param_layout layout,
@@ -898,12 +932,15 @@ int tfep_copy_2d(const float* src, int64_t lds, float* dst, int64_t ldd, int B, 
 int tfep_weight_norm_backward(const float* gw_packed, int64_t ldw, const float* weight_v, const float* weight_g,
                               const float* mask, int out_features, int in_features, const int32_t* row_of_out,
                               const int32_t* col_of_in, float* grad_v, float* grad_g, void* stream) {
-    TFEP_REQUIRE(out_features >= 0 && in_features >= 0, "weight_norm_backward: negative size");
-    if (out_features == 0 || in_features == 0) return TFEP_OK;
-    TFEP_REQUIRE(gw_packed && weight_v && grad_v && (!weight_g || grad_g), "weight_norm_backward: NULL pointer");
-    weight_norm_backward_kernel<<<(unsigned)((out_features + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-        gw_packed, ldw, weight_v, weight_g, mask, out_features, in_features, row_of_out, col_of_in, grad_v, grad_g);
-    return check_launch("weight_norm_backward_kernel");
+    return launch_weight_norm_backward("weight_norm_backward", gw_packed, ldw, weight_v, weight_g, mask, out_features,
+                                       in_features, row_of_out, col_of_in, grad_v, grad_g, stream);
+}
+
+int tfep_weight_norm_backward_f64(const double* gw_packed, int64_t ldw, const double* weight_v, const double* weight_g,
+                                  const double* mask, int out_features, int in_features, const int32_t* row_of_out,
+                                  const int32_t* col_of_in, double* grad_v, double* grad_g, void* stream) {
+    return launch_weight_norm_backward("weight_norm_backward_f64", gw_packed, ldw, weight_v, weight_g, mask, out_features,
+                                       in_features, row_of_out, col_of_in, grad_v, grad_g, stream);
 }
 
 int tfep_weight_norm_backward_prefix(const float* gw_packed, int64_t ldw, const float* weight_v, const float* weight_g,
@@ -923,13 +960,15 @@ int tfep_weight_norm_backward_prefix(const float* gw_packed, int64_t ldw, const 
 int tfep_periodic_embedding_backward(const float* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
                                      const int32_t* nonperiodic_indices, int n_nonperiodic, float lower, float upper,
                                      const float* gout, int64_t ldg, float* gx, int64_t ldgx, int B, void* stream) {
-    const int64_t n = (int64_t)B * (n_periodic + n_nonperiodic);
-    if (n == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && gout && gx, "periodic_embedding_backward: NULL pointer");
-    const float scale = (float)(2.0 * 3.14159265358979323846 / ((double)upper - (double)lower));
-    periodic_embedding_backward_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-        x, ldx, periodic_indices, n_periodic, nonperiodic_indices, n_nonperiodic, lower, scale, gout, ldg, gx, ldgx, B);
-    return check_launch("periodic_embedding_backward_kernel");
+    return launch_periodic_embedding_backward("periodic_embedding_backward", x, ldx, periodic_indices, n_periodic,
+                                              nonperiodic_indices, n_nonperiodic, lower, upper, gout, ldg, gx, ldgx, B, stream);
+}
+
+int tfep_periodic_embedding_backward_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
+                                         const int32_t* nonperiodic_indices, int n_nonperiodic, double lower, double upper,
+                                         const double* gout, int64_t ldg, double* gx, int64_t ldgx, int B, void* stream) {
+    return launch_periodic_embedding_backward("periodic_embedding_backward_f64", x, ldx, periodic_indices, n_periodic,
+                                              nonperiodic_indices, n_nonperiodic, lower, upper, gout, ldg, gx, ldgx, B, stream);
 }
 
 }  // extern "C"

@@ -70,5 +70,15 @@ __device__ inline double py_mod(double a, double b) {
     if (r != 0.0 && ((r < 0.0) != (b < 0.0))) r += b;
     return r;
 }
+// sincos overloaded for float too (the HIP math headers declare the double form only)
+using ::sincos;
+__device__ inline void sincos(float x, float* s, float* c) { sincosf(x, s, c); }
+
+// float32 `%`: fmodf and the same sign fix-up (the float32 volume-preserving shift, affine.py:409, :454)
+__device__ inline float py_mod(float a, float b) {
+    float r = fmodf(a, b);
+    if (r != 0.f && ((r < 0.f) != (b < 0.f))) r += b;
+    return r;
+}
 
 }  // namespace tfep

@@ -26,34 +26,35 @@ constexpr int WAVES = 8;
 constexpr int THREADS = WAVES * 64;
 
 // ------------------------------------------------------------------------------------------
-// Weight preparation (reference masked.py:369-371, :433-439, :270)
+// Weight preparation (reference masked.py:369-371, :433-439, :270); float32 and float64 (no col_cut form in float64)
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) weight_prepare_kernel(const float* __restrict__ v, const float* __restrict__ g,
-                                                             const float* __restrict__ mask, int N, int K,
+template <typename T>
+__global__ void __launch_bounds__(256) weight_prepare_kernel(const T* __restrict__ v, const T* __restrict__ g,
+                                                             const T* __restrict__ mask, int N, int K,
                                                              const int32_t* __restrict__ row_of_out,
                                                              const int32_t* __restrict__ col_of_in,
                                                              const int32_t* __restrict__ col_cut,
-                                                             float* __restrict__ w_out, int64_t ldw) {
+                                                             T* __restrict__ w_out, int64_t ldw) {
     const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (o >= N) return;
     const int lane = threadIdx.x & 63;
-    const float* vr = v + (int64_t)o * K;
+    const T* vr = v + (int64_t)o * K;
     const int cut = col_cut ? col_cut[o] : 0;         // prefix mask: packed columns [0, cut) are on, nothing to read
-    const float* mr = (mask && !col_cut) ? mask + (int64_t)o * K : nullptr;
-    float scale = 1.0f;
+    const T* mr = (mask && !col_cut) ? mask + (int64_t)o * K : nullptr;
+    T scale = T(1);
     if (g) {
-        float ss = 0.f;
+        T ss = T(0);
         for (int i = lane; i < K; i += 64) ss += vr[i] * vr[i];
         ss = wave_sum(ss);
-        scale = g[o] / sqrtf(ss);          // may be inf/NaN for a fully-masked row: never used below
+        scale = g[o] / sqrt(ss);           // may be inf/NaN for a fully-masked row: never used below
     }
     const int64_t orow = row_of_out ? row_of_out[o] : o;
-    float* wr = w_out + orow * ldw;
+    T* wr = w_out + orow * ldw;
     for (int i = lane; i < K; i += 64) {
         const int c = col_of_in ? col_of_in[i] : i;
-        float val;
-        if (col_cut ? c >= cut : (mr && mr[i] == 0.0f))
-            val = 0.0f;                    // _ApplyMask: exact zero, also where v*scale is NaN
+        T val;
+        if (col_cut ? c >= cut : (mr && mr[i] == T(0)))
+            val = T(0);                    // _ApplyMask: exact zero, also where v*scale is NaN
         else
             val = g ? vr[i] * scale : (mr ? vr[i] * mr[i] : vr[i]);
         wr[c] = val;
@@ -127,17 +128,18 @@ __global__ void __launch_bounds__(PFX32_THREADS) weight_prepare_prefix_kernel(co
 }
 
 // Bounding k-range of the mask non-zeros per tile of `tile_n` packed rows.
-__global__ void __launch_bounds__(256) mask_k_ranges_kernel(const float* __restrict__ mask, int N, int K,
+template <typename T>
+__global__ void __launch_bounds__(256) mask_k_ranges_kernel(const T* __restrict__ mask, int N, int K,
                                                             const int32_t* __restrict__ row_of_out,
                                                             const int32_t* __restrict__ col_of_in, int tile_n,
                                                             int32_t* __restrict__ lo_hi) {
     const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (o >= N) return;
     const int lane = threadIdx.x & 63;
-    const float* mr = mask + (int64_t)o * K;
+    const T* mr = mask + (int64_t)o * K;
     int lo = 0x7fffffff, hi = -1;
     for (int i = lane; i < K; i += 64) {
-        if (mr[i] != 0.0f) {
+        if (mr[i] != T(0)) {
             const int c = col_of_in ? col_of_in[i] : i;
             lo = min(lo, c);
             hi = max(hi, c);
@@ -432,16 +434,59 @@ static int check_gemm_operands(const float* a, int64_t lda, const float* w, int6
 }  // namespace tfep
 
 namespace tfep {
-// p[0 .. n) = 0 (grid-stride; see tfep_masked_weight_prepare for why not hipMemsetAsync)
-__global__ void __launch_bounds__(256) fill_zero_kernel(float* __restrict__ p, size_t n) {
-    const size_t stride = (size_t)gridDim.x * 256 * 4;
-    for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += stride) {
-        if (i + 4 <= n && ((uintptr_t)(p + i) & 15) == 0) {
+// p[0 .. n) = 0 (grid-stride, 16 bytes per thread and step; see launch_weight_prepare for why not hipMemsetAsync)
+template <typename T>
+__global__ void __launch_bounds__(256) fill_zero_kernel(T* __restrict__ p, size_t n) {
+    constexpr int V = 16 / sizeof(T);
+    const size_t stride = (size_t)gridDim.x * 256 * V;
+    for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; i < n; i += stride) {
+        if (i + V <= n && ((uintptr_t)(p + i) & 15) == 0) {
             *reinterpret_cast<float4*>(p + i) = make_float4(0.f, 0.f, 0.f, 0.f);
         } else {
-            for (size_t j = i; j < n && j < i + 4; ++j) p[j] = 0.f;
+            for (size_t j = i; j < n && j < i + V; ++j) p[j] = T(0);
         }
     }
+}
+
+// Launchers shared by the float32 entry points and their _f64 twins; `who` prefixes the error messages.
+template <typename T>
+static int launch_weight_prepare(const char* who, const T* v, const T* g, const T* mask, int N, int K,
+                                 const int32_t* row_of_out, const int32_t* col_of_in, const int32_t* col_cut, int clear,
+                                 T* w_out, int n_rows_padded, int64_t ldw, void* stream) {
+    TFEP_REQUIRE(v && w_out, "%s: NULL pointer", who);
+    TFEP_REQUIRE(N >= 0 && K >= 0, "%s: negative size", who);
+    TFEP_REQUIRE(n_rows_padded >= N && ldw >= K, "%s: output too small", who);
+    hipStream_t s = (hipStream_t)stream;
+    // Cleared by a kernel, not hipMemsetAsync: captured in a HIP graph a memset becomes a memset node, and those were seen
+    // to leave garbage behind on replay (the padding rows of this buffer read back as ~1e36 by a later kernel of the same
+    // graph, while eager runs were clean; an earlier 4-byte case was traced to the same node type).
+    const size_t n_clear = (size_t)n_rows_padded * (size_t)ldw;
+    if (clear && n_clear > 0) {
+        const size_t per_block = 256 * (16 / sizeof(T)), blocks = (n_clear + per_block - 1) / per_block;
+        fill_zero_kernel<T><<<(unsigned)(blocks < 65535 * 16 ? blocks : 65535 * 16), 256, 0, s>>>(w_out, n_clear);
+        int rc = check_launch("fill_zero_kernel");
+        if (rc) return rc;
+    }
+    if (N == 0 || K == 0) return TFEP_OK;
+    weight_prepare_kernel<T><<<(unsigned)((N + 3) / 4), 256, 0, s>>>(v, g, mask, N, K, row_of_out, col_of_in, col_cut, w_out,
+                                                                      ldw);
+    return check_launch("weight_prepare_kernel");
+}
+
+template <typename T>
+static int launch_mask_k_ranges(const char* who, const T* mask, int N, int K, const int32_t* row_of_out,
+                                const int32_t* col_of_in, int tile_n, int tile_k, int n_tiles, int k_padded,
+                                int32_t* k_ranges, void* stream) {
+    TFEP_REQUIRE(k_ranges, "%s: NULL output", who);
+    TFEP_REQUIRE(tile_n > 0 && tile_k > 0 && n_tiles >= 0, "%s: bad tile sizes", who);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_tiles == 0) return TFEP_OK;
+    TFEP_REQUIRE(mask, "%s: mask is NULL (pass k_ranges = NULL to the GEMM for dense weights)", who);
+    init_k_ranges_kernel<<<(unsigned)((n_tiles + 255) / 256), 256, 0, s>>>(k_ranges, n_tiles);
+    if (N > 0 && K > 0)
+        mask_k_ranges_kernel<T><<<(unsigned)((N + 3) / 4), 256, 0, s>>>(mask, N, K, row_of_out, col_of_in, tile_n, k_ranges);
+    finish_k_ranges_kernel<<<(unsigned)((n_tiles + 255) / 256), 256, 0, s>>>(k_ranges, n_tiles, tile_k, k_padded);
+    return check_launch(who);
 }
 }  // namespace tfep
 
@@ -461,23 +506,15 @@ int tfep_fused_tile_features(void) { return FUSED_TILE_FEATURES; }
 int tfep_masked_weight_prepare(const float* weight_v, const float* weight_g, const float* mask, int out_features,
                                int in_features, const int32_t* row_of_out, const int32_t* col_of_in, const int32_t* col_cut,
                                int clear, float* w_out, int n_rows_padded, int64_t ldw, void* stream) {
-    TFEP_REQUIRE(weight_v && w_out, "masked_weight_prepare: NULL pointer");
-    TFEP_REQUIRE(out_features >= 0 && in_features >= 0, "masked_weight_prepare: negative size");
-    TFEP_REQUIRE(n_rows_padded >= out_features && ldw >= in_features, "masked_weight_prepare: output too small");
-    hipStream_t s = (hipStream_t)stream;
-    // Cleared by a kernel, not hipMemsetAsync: captured in a HIP graph a memset becomes a memset node, and those were seen
-    // to leave garbage behind on replay (the padding rows of this buffer read back as ~1e36 by a later kernel of the same
-    // graph, while eager runs were clean; an earlier 4-byte case was traced to the same node type).
-    const size_t n_clear = (size_t)n_rows_padded * (size_t)ldw;
-    if (clear && n_clear > 0) {
-        fill_zero_kernel<<<(unsigned)((n_clear + 1023) / 1024 < 65535 * 16 ? (n_clear + 1023) / 1024 : 65535 * 16), 256, 0, s>>>(w_out, n_clear);
-        int rc = check_launch("fill_zero_kernel");
-        if (rc) return rc;
-    }
-    if (out_features == 0 || in_features == 0) return TFEP_OK;
-    weight_prepare_kernel<<<(unsigned)((out_features + 3) / 4), 256, 0, s>>>(weight_v, weight_g, mask, out_features,
-                                                                              in_features, row_of_out, col_of_in, col_cut, w_out, ldw);
-    return check_launch("weight_prepare_kernel");
+    return launch_weight_prepare("masked_weight_prepare", weight_v, weight_g, mask, out_features, in_features, row_of_out,
+                                 col_of_in, col_cut, clear, w_out, n_rows_padded, ldw, stream);
+}
+
+int tfep_masked_weight_prepare_f64(const double* weight_v, const double* weight_g, const double* mask, int out_features,
+                                   int in_features, const int32_t* row_of_out, const int32_t* col_of_in, int clear,
+                                   double* w_out, int n_rows_padded, int64_t ldw, void* stream) {
+    return launch_weight_prepare("masked_weight_prepare_f64", weight_v, weight_g, mask, out_features, in_features, row_of_out,
+                                 col_of_in, (const int32_t*)nullptr, clear, w_out, n_rows_padded, ldw, stream);
 }
 
 int tfep_masked_weight_prepare_prefix(const float* weight_v, const float* weight_g, int out_features, int in_features,
@@ -498,17 +535,15 @@ int tfep_masked_weight_prepare_prefix(const float* weight_v, const float* weight
 int tfep_mask_k_ranges(const float* mask, int out_features, int in_features, const int32_t* row_of_out,
                        const int32_t* col_of_in, int tile_n, int tile_k, int n_tiles, int k_padded,
                        int32_t* k_ranges, void* stream) {
-    TFEP_REQUIRE(k_ranges, "mask_k_ranges: NULL output");
-    TFEP_REQUIRE(tile_n > 0 && tile_k > 0 && n_tiles >= 0, "mask_k_ranges: bad tile sizes");
-    hipStream_t s = (hipStream_t)stream;
-    if (n_tiles == 0) return TFEP_OK;
-    TFEP_REQUIRE(mask, "mask_k_ranges: mask is NULL (pass k_ranges = NULL to the GEMM for dense weights)");
-    init_k_ranges_kernel<<<(unsigned)((n_tiles + 255) / 256), 256, 0, s>>>(k_ranges, n_tiles);
-    if (out_features > 0 && in_features > 0)
-        mask_k_ranges_kernel<<<(unsigned)((out_features + 3) / 4), 256, 0, s>>>(mask, out_features, in_features,
-                                                                                 row_of_out, col_of_in, tile_n, k_ranges);
-    finish_k_ranges_kernel<<<(unsigned)((n_tiles + 255) / 256), 256, 0, s>>>(k_ranges, n_tiles, tile_k, k_padded);
-    return check_launch("mask_k_ranges");
+    return launch_mask_k_ranges("mask_k_ranges", mask, out_features, in_features, row_of_out, col_of_in, tile_n, tile_k,
+                                n_tiles, k_padded, k_ranges, stream);
+}
+
+int tfep_mask_k_ranges_f64(const double* mask, int out_features, int in_features, const int32_t* row_of_out,
+                           const int32_t* col_of_in, int tile_n, int tile_k, int n_tiles, int k_padded, int32_t* k_ranges,
+                           void* stream) {
+    return launch_mask_k_ranges("mask_k_ranges_f64", mask, out_features, in_features, row_of_out, col_of_in, tile_n, tile_k,
+                                n_tiles, k_padded, k_ranges, stream);
 }
 
 int tfep_masked_linear_forward(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,

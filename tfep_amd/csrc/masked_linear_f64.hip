@@ -1,6 +1,6 @@
-// float64 masked linear layers for gfx950: masked weight preparation, mask k-ranges, the fp64-MFMA masked GEMM and the
-// helpers of its backward (transpose, column sums, weight-norm backward).  The float32 kernels (masked_linear.hip,
-// backward.hip) are separate code and untouched by this file.
+// float64 masked linear layers for gfx950: the fp64-MFMA masked GEMM, its peak probe and the column sums of its backward.
+// These differ from the float32 kernels by design.  The float64 weight preparation, mask k-ranges, transpose and
+// weight-norm backward are the float32 kernels' double instantiations (masked_linear.hip, backward.hip).
 //
 // GEMM shape:  Y[b, n] = sum_k X[b, k] * W[n, k]      (both operands K-contiguous, "NT"), fp64 products and fp64 sums.
 //
@@ -175,116 +175,10 @@ __global__ void __launch_bounds__(THREADS, 2) mfma_f64_peak_kernel(double* out, 
     out[(int64_t)blockIdx.x * THREADS + threadIdx.x] = sum;
 }
 
-// ------------------------------------------------------------------------------------------ weight preparation
-// (reference masked.py:369-371, :433-439, :270; the float32 weight_prepare_kernel in double)
-__global__ void __launch_bounds__(256) weight_prepare_kernel(const double* __restrict__ v, const double* __restrict__ g,
-                                                             const double* __restrict__ mask, int N, int K,
-                                                             const int32_t* __restrict__ row_of_out,
-                                                             const int32_t* __restrict__ col_of_in,
-                                                             double* __restrict__ w_out, int64_t ldw) {
-    const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (o >= N) return;
-    const int lane = threadIdx.x & 63;
-    const double* vr = v + (int64_t)o * K;
-    const double* mr = mask ? mask + (int64_t)o * K : nullptr;
-    double scale = 1.0;
-    if (g) {
-        double ss = 0.0;
-        for (int i = lane; i < K; i += 64) ss += vr[i] * vr[i];
-        ss = wave_sum(ss);
-        scale = g[o] / sqrt(ss);           // may be inf/NaN for a fully-masked row: never used below
-    }
-    const int64_t orow = row_of_out ? row_of_out[o] : o;
-    double* wr = w_out + orow * ldw;
-    for (int i = lane; i < K; i += 64) {
-        const int c = col_of_in ? col_of_in[i] : i;
-        double val;
-        if (mr && mr[i] == 0.0)
-            val = 0.0;                     // _ApplyMask: exact zero, also where v*scale is NaN
-        else
-            val = g ? vr[i] * scale : (mr ? vr[i] * mr[i] : vr[i]);
-        wr[c] = val;
-    }
-}
-
-__global__ void __launch_bounds__(256) fill_zero_kernel(double* __restrict__ p, size_t n) {
-    const size_t stride = (size_t)gridDim.x * 256;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) p[i] = 0.0;
-}
-
-// Bounding k-range of the mask non-zeros per tile of `tile_n` packed rows (the float32 mask_k_ranges_kernel on a
-// double mask).
-__global__ void __launch_bounds__(256) mask_k_ranges_kernel(const double* __restrict__ mask, int N, int K,
-                                                            const int32_t* __restrict__ row_of_out,
-                                                            const int32_t* __restrict__ col_of_in, int tile_n,
-                                                            int32_t* __restrict__ lo_hi) {
-    const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (o >= N) return;
-    const int lane = threadIdx.x & 63;
-    const double* mr = mask + (int64_t)o * K;
-    int lo = 0x7fffffff, hi = -1;
-    for (int i = lane; i < K; i += 64) {
-        if (mr[i] != 0.0) {
-            const int c = col_of_in ? col_of_in[i] : i;
-            lo = min(lo, c);
-            hi = max(hi, c);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = min(lo, __shfl_xor(lo, off, 64));
-        hi = max(hi, __shfl_xor(hi, off, 64));
-    }
-    if (lane == 0 && hi >= 0) {
-        const int t = (row_of_out ? row_of_out[o] : o) / tile_n;
-        atomicMin(&lo_hi[2 * t], lo);
-        atomicMax(&lo_hi[2 * t + 1], hi);
-    }
-}
-
-__global__ void init_k_ranges_kernel(int32_t* __restrict__ lo_hi, int n_tiles) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n_tiles) {
-        lo_hi[2 * t] = 0x7fffffff;
-        lo_hi[2 * t + 1] = -1;
-    }
-}
-
-__global__ void finish_k_ranges_kernel(int32_t* __restrict__ lo_hi, int n_tiles, int tile_k, int k_padded) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_tiles) return;
-    int lo = lo_hi[2 * t], hi = lo_hi[2 * t + 1];
-    if (hi < 0) {
-        lo = 0;
-        hi = 0;
-    } else {
-        lo = (lo / tile_k) * tile_k;
-        hi = min(((hi + tile_k) / tile_k) * tile_k, k_padded);
-    }
-    lo_hi[2 * t] = lo;
-    lo_hi[2 * t + 1] = hi;
-}
-
-// ------------------------------------------------------------------------------------------ backward helpers
-__global__ void __launch_bounds__(256) transpose_kernel(const double* __restrict__ in, int64_t ld_in, int R, int C,
-                                                        double* __restrict__ out, int64_t ld_out) {
-    __shared__ double tile[32][33];
-    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
-#pragma unroll
-    for (int i = 0; i < 32; i += 8) {
-        const int r = r0 + ty + i, c = c0 + tx;
-        tile[ty + i][tx] = (r < R && c < C) ? in[(int64_t)r * ld_in + c] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 32; i += 8) {
-        const int c = c0 + ty + i, r = r0 + tx;
-        if (c < C && r < R) out[(int64_t)c * ld_out + r] = tile[tx][ty + i];
-    }
-}
-
-// out[c] (+)= sum_r in[r, c]: 64 columns per workgroup, 16 contiguous row slices summed in a fixed pairwise order
+// ------------------------------------------------------------------------------------------ column sums
+// out[c] (+)= sum_r in[r, c]: 64 columns per workgroup, 16 contiguous row slices summed in a fixed pairwise order.  Each
+// slice is one summation chain; the float32 colsum_kernel (backward.hip) keeps eight partial sums per slice, an order
+// that would change the float64 results.
 constexpr int CS_COLS = 64, CS_SLICES = 16;
 __global__ void __launch_bounds__(CS_COLS * CS_SLICES) colsum_kernel(const double* __restrict__ in, int64_t ld, int R, int C,
                                                                     double* __restrict__ out, int accumulate) {
@@ -310,95 +204,12 @@ __global__ void __launch_bounds__(CS_COLS * CS_SLICES) colsum_kernel(const doubl
     }
 }
 
-// Weight-norm backward (the float32 weight_norm_backward_kernel in double):
-//   gg[o]   = sum_i gW M v / n,   gv[o,i] = M (g/n) gW - g v / n^3 * sum_j gW M v;   g == NULL: gweight = gW o M
-__global__ void __launch_bounds__(256) weight_norm_backward_kernel(const double* __restrict__ gw_packed, int64_t ldw,
-                                                                   const double* __restrict__ v,
-                                                                   const double* __restrict__ g,
-                                                                   const double* __restrict__ mask, int N, int K,
-                                                                   const int32_t* __restrict__ row_of_out,
-                                                                   const int32_t* __restrict__ col_of_in,
-                                                                   double* __restrict__ gv, double* __restrict__ gg) {
-    const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (o >= N) return;
-    const int lane = threadIdx.x & 63;
-    const double* vr = v + (int64_t)o * K;
-    const double* mr = mask ? mask + (int64_t)o * K : nullptr;
-    const double* gr = gw_packed + (int64_t)(row_of_out ? row_of_out[o] : o) * ldw;
-    double* gvr = gv + (int64_t)o * K;
-    if (!g) {
-        for (int i = lane; i < K; i += 64) {
-            const double gwv = gr[col_of_in ? col_of_in[i] : i];
-            gvr[i] = (mr && mr[i] == 0.0) ? 0.0 : gwv;
-        }
-        return;
-    }
-    double ss = 0.0, dot = 0.0, msum = 0.0;
-    for (int i = lane; i < K; i += 64) {
-        const double vv = vr[i];
-        ss += vv * vv;
-        if (!mr || mr[i] != 0.0) {
-            dot += gr[col_of_in ? col_of_in[i] : i] * vv;
-            msum += 1.0;
-        }
-    }
-    ss = wave_sum(ss);
-    dot = wave_sum(dot);
-    msum = wave_sum(msum);
-    const double n = sqrt(ss);
-    const bool dead = msum == 0.0 || n == 0.0;
-    const double go = g[o];
-    for (int i = lane; i < K; i += 64) {
-        const bool live = !mr || mr[i] != 0.0;
-        double out = 0.0;
-        if (live && !dead) out = go / n * gr[col_of_in ? col_of_in[i] : i] - go * vr[i] * dot / (n * n * n);
-        gvr[i] = out;
-    }
-    if (lane == 0) gg[o] = dead ? 0.0 : dot / n;
-}
-
 }  // namespace f64
 }  // namespace tfep
 
 using namespace tfep;
 
 extern "C" {
-
-int tfep_masked_weight_prepare_f64(const double* weight_v, const double* weight_g, const double* mask, int out_features,
-                                   int in_features, const int32_t* row_of_out, const int32_t* col_of_in, int clear,
-                                   double* w_out, int n_rows_padded, int64_t ldw, void* stream) {
-    TFEP_REQUIRE(weight_v && w_out, "masked_weight_prepare_f64: NULL pointer");
-    TFEP_REQUIRE(out_features >= 0 && in_features >= 0, "masked_weight_prepare_f64: negative size");
-    TFEP_REQUIRE(n_rows_padded >= out_features && ldw >= in_features, "masked_weight_prepare_f64: output too small");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n_clear = (size_t)n_rows_padded * (size_t)ldw;
-    if (clear && n_clear > 0) {      // (a kernel, not hipMemsetAsync: see tfep_masked_weight_prepare)
-        const size_t blocks = (n_clear + 255) / 256;
-        f64::fill_zero_kernel<<<(unsigned)(blocks < 65535 * 16 ? blocks : 65535 * 16), 256, 0, s>>>(w_out, n_clear);
-        int rc = check_launch("fill_zero_kernel_f64");
-        if (rc) return rc;
-    }
-    if (out_features == 0 || in_features == 0) return TFEP_OK;
-    f64::weight_prepare_kernel<<<(unsigned)((out_features + 3) / 4), 256, 0, s>>>(weight_v, weight_g, mask, out_features,
-                                                                                   in_features, row_of_out, col_of_in, w_out, ldw);
-    return check_launch("weight_prepare_kernel_f64");
-}
-
-int tfep_mask_k_ranges_f64(const double* mask, int out_features, int in_features, const int32_t* row_of_out,
-                           const int32_t* col_of_in, int tile_n, int tile_k, int n_tiles, int k_padded, int32_t* k_ranges,
-                           void* stream) {
-    TFEP_REQUIRE(k_ranges, "mask_k_ranges_f64: NULL output");
-    TFEP_REQUIRE(tile_n > 0 && tile_k > 0 && n_tiles >= 0, "mask_k_ranges_f64: bad tile sizes");
-    hipStream_t s = (hipStream_t)stream;
-    if (n_tiles == 0) return TFEP_OK;
-    TFEP_REQUIRE(mask, "mask_k_ranges_f64: mask is NULL (pass k_ranges = NULL to the GEMM for dense weights)");
-    f64::init_k_ranges_kernel<<<(unsigned)((n_tiles + 255) / 256), 256, 0, s>>>(k_ranges, n_tiles);
-    if (out_features > 0 && in_features > 0)
-        f64::mask_k_ranges_kernel<<<(unsigned)((out_features + 3) / 4), 256, 0, s>>>(mask, out_features, in_features,
-                                                                                       row_of_out, col_of_in, tile_n, k_ranges);
-    f64::finish_k_ranges_kernel<<<(unsigned)((n_tiles + 255) / 256), 256, 0, s>>>(k_ranges, n_tiles, tile_k, k_padded);
-    return check_launch("mask_k_ranges_f64");
-}
 
 int tfep_masked_linear_gemm_f64(const double* x, int64_t ldx, const double* w, int64_t ldw, const double* bias,
                                 const int32_t* k_ranges, int kr_tile_n, double* y, int64_t ldy, int B, int N, int n_rows_w,
@@ -431,15 +242,6 @@ int tfep_masked_linear_gemm_f64(const double* x, int64_t ldx, const double* w, i
     return check_launch("gemm_f64_kernel");
 }
 
-int tfep_transpose_f64(const double* in, int64_t ld_in, int R, int C, double* out, int64_t ld_out, void* stream) {
-    TFEP_REQUIRE(R >= 0 && C >= 0 && ld_in >= C && ld_out >= R, "transpose_f64: bad sizes");
-    if (R == 0 || C == 0) return TFEP_OK;
-    TFEP_REQUIRE(in && out, "transpose_f64: NULL pointer");
-    dim3 grid((unsigned)((C + 31) / 32), (unsigned)((R + 31) / 32));
-    f64::transpose_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(in, ld_in, R, C, out, ld_out);
-    return check_launch("transpose_kernel_f64");
-}
-
 int tfep_column_sums_f64(const double* in, int64_t ld, int R, int C, double* out, int accumulate, void* stream) {
     TFEP_REQUIRE(R >= 0 && C >= 0, "column_sums_f64: bad sizes");
     if (C == 0) return TFEP_OK;
@@ -447,17 +249,6 @@ int tfep_column_sums_f64(const double* in, int64_t ld, int R, int C, double* out
     f64::colsum_kernel<<<(unsigned)((C + f64::CS_COLS - 1) / f64::CS_COLS), f64::CS_COLS * f64::CS_SLICES, 0, (hipStream_t)stream>>>(
         in, ld, R, C, out, accumulate);
     return check_launch("colsum_kernel_f64");
-}
-
-int tfep_weight_norm_backward_f64(const double* gw_packed, int64_t ldw, const double* weight_v, const double* weight_g,
-                                  const double* mask, int out_features, int in_features, const int32_t* row_of_out,
-                                  const int32_t* col_of_in, double* grad_v, double* grad_g, void* stream) {
-    TFEP_REQUIRE(out_features >= 0 && in_features >= 0, "weight_norm_backward_f64: negative size");
-    if (out_features == 0 || in_features == 0) return TFEP_OK;
-    TFEP_REQUIRE(gw_packed && weight_v && grad_v && (!weight_g || grad_g), "weight_norm_backward_f64: NULL pointer");
-    f64::weight_norm_backward_kernel<<<(unsigned)((out_features + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-        gw_packed, ldw, weight_v, weight_g, mask, out_features, in_features, row_of_out, col_of_in, grad_v, grad_g);
-    return check_launch("weight_norm_backward_kernel_f64");
 }
 
 int tfep_diag_mfma_f64_peak(double* scratch, int blocks, int iters, void* stream) {

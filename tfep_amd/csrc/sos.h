@@ -1,5 +1,5 @@
 // Sum-of-squares polynomial transformer (reference transformers/sos.py): the element functions shared by the standalone
-// kernels (transformers.hip, transformers_f64.hip) and the fused epilogue of the MADE output GEMM (gemm_common.h).
+// kernels (transformers.hip, float and double) and the fused epilogue of the MADE output GEMM (gemm_common.h).
 //
 // K squared linear polynomials per feature, P = 2 K + 1 parameters: prm(0) = a0, prm(1 + 2k) = a_k0, prm(2 + 2k) = a_k1.
 //   y     = a0 + x (s0 + s1 x + s2 x^2),   s0 = sum a_k0^2, s1 = sum a_k0 a_k1, s2 = sum a_k1^2 / 3    (sos.py:198-219, :261-265)

@@ -1,14 +1,13 @@
-// float64 transformer kernels: affine, volume-preserving shift, RQ spline (forward, inverse and VJPs), periodic embedding and
-// column gather / scatter on double tensors -- the twins of transformers.hip / backward.hip for float64 flows.  Same launch
-// shape: one wavefront per sample row, its 64 lanes walk the features with unit stride, the log-derivative is summed with the
-// wave butterfly (no atomics: bit-reproducible and independent of the batch the row sits in).
+// float64 RQ spline kernels: forward, inverse and VJP on double tensors.  Same launch shape as the float32 spline
+// (transformers.hip / backward.hip): one wavefront per sample row, its 64 lanes walk the features with unit stride, the
+// log-derivative is summed with the wave butterfly (no atomics: bit-reproducible and independent of the batch the row sits
+// in).  The other float64 transformers are the float32 kernels' double instantiations (transformers.hip, backward.hip).
 //
 // Numerics: everything in fp64 from double parameters, with the library exp / log / log1p / sqrt and IEEE divisions (no
 // polynomial exponentials, no hardware-seeded reciprocals: the float32 kernels' shortcuts are accurate to ~1e-11, which is
 // coarse next to the float64 reference).  The spline follows the reference's rules: strict '>' in the bin search, linear
 // continuation along the boundary slope outside the domain (transformers/spline.py:567-650).
 #include "common.h"
-#include "sos.h"
 
 namespace tfep {
 namespace {
@@ -19,105 +18,6 @@ inline unsigned row_blocks64(int B) { return (unsigned)((B + RPB - 1) / RPB); }
 
 __device__ inline void store_ldj64(double* ldj, int b, double total, int accumulate) {
     if ((threadIdx.x & 63) == 0) ldj[b] = accumulate ? ldj[b] + total : total;
-}
-
-// ---------------------------------------------------------------- affine (affine.py:321-323, :361-363)
-template <bool INVERSE>
-__global__ void __launch_bounds__(256) affine64_kernel(const double* __restrict__ x, int64_t ldx,
-                                                       const double* __restrict__ params, tfep_param_layout L,
-                                                       double* __restrict__ y, int64_t ldy, double* __restrict__ ldj,
-                                                       int accumulate, int B, int D) {
-    const int b = blockIdx.x * RPB + (threadIdx.x >> 6);
-    if (b >= B) return;
-    const int lane = threadIdx.x & 63;
-    const double* xr = x + (int64_t)b * ldx;
-    const double* pr = params + (int64_t)b * L.ld;
-    double* yr = y + (int64_t)b * ldy;
-    double acc = 0.0;
-    for (int f = lane; f < D; f += 64) {
-        const double shift = pr[f * L.stride_f];
-        const double ls = pr[L.stride_p + f * L.stride_f];
-        const double v = xr[f];
-        yr[f] = INVERSE ? (v - shift) * exp(-ls) : v * exp(ls) + shift;
-        acc += ls;
-    }
-    acc = wave_sum(acc);
-    if (ldj) store_ldj64(ldj, b, INVERSE ? -acc : acc, accumulate);
-}
-
-__global__ void __launch_bounds__(256) affine64_backward_kernel(const double* __restrict__ x, int64_t ldx,
-                                                                const double* __restrict__ params, tfep_param_layout L,
-                                                                const double* __restrict__ gy, int64_t ldgy,
-                                                                const double* __restrict__ gldj,
-                                                                double* __restrict__ gparams, tfep_param_layout GL,
-                                                                double* __restrict__ gx, int64_t ldgx, int B, int D) {
-    const int b = blockIdx.x * RPB + (threadIdx.x >> 6);
-    if (b >= B) return;
-    const int lane = threadIdx.x & 63;
-    const double gl = gldj ? gldj[b] : 0.0;
-    for (int f = lane; f < D; f += 64) {
-        const double ls = params[(int64_t)b * L.ld + L.stride_p + f * L.stride_f];
-        const double g = gy[(int64_t)b * ldgy + f];
-        const double e = exp(ls);
-        const double xv = x[(int64_t)b * ldx + f];
-        gparams[(int64_t)b * GL.ld + f * GL.stride_f] = g;                                   // d/d shift
-        gparams[(int64_t)b * GL.ld + GL.stride_p + f * GL.stride_f] = g * xv * e + gl;       // d/d log_scale
-        gx[(int64_t)b * ldgx + f] = g * e;
-    }
-}
-
-// ---------------------------------------------------------------- SOS polynomial (sos.py:198-265; sos.h)
-__global__ void __launch_bounds__(256) sos64_kernel(const double* __restrict__ x, int64_t ldx,
-                                                    const double* __restrict__ params, tfep_param_layout L, int K,
-                                                    double* __restrict__ y, int64_t ldy, double* __restrict__ ldj,
-                                                    int accumulate, int B, int D) {
-    const int b = blockIdx.x * RPB + (threadIdx.x >> 6);
-    if (b >= B) return;
-    const int lane = threadIdx.x & 63;
-    const double* xr = x + (int64_t)b * ldx;
-    const double* pr = params + (int64_t)b * L.ld;
-    double* yr = y + (int64_t)b * ldy;
-    double acc = 0.0;
-    for (int f = lane; f < D; f += 64) {
-        const double* pf = pr + f * L.stride_f;
-        double d;
-        yr[f] = sos_element<0, double>(K, [&](int p) { return pf[p * L.stride_p]; }, xr[f], &d);
-        acc += log(d);
-    }
-    acc = wave_sum(acc);
-    if (ldj) store_ldj64(ldj, b, acc, accumulate);
-}
-
-__global__ void __launch_bounds__(256) sos64_backward_kernel(const double* __restrict__ x, int64_t ldx,
-                                                             const double* __restrict__ params, tfep_param_layout L, int K,
-                                                             const double* __restrict__ gy, int64_t ldgy,
-                                                             double* __restrict__ gparams, tfep_param_layout GL,
-                                                             double* __restrict__ gx, int64_t ldgx, int B, int D) {
-    const int b = blockIdx.x * RPB + (threadIdx.x >> 6);
-    if (b >= B) return;
-    const int lane = threadIdx.x & 63;
-    const double* pr = params + (int64_t)b * L.ld;
-    double* gpr = gparams + (int64_t)b * GL.ld;
-    for (int f = lane; f < D; f += 64) {
-        const double* pf = pr + f * L.stride_f;
-        double* gpf = gpr + f * GL.stride_f;
-        gx[(int64_t)b * ldgx + f] = sos_vjp_element<double>(
-            K, [&](int p) { return pf[p * L.stride_p]; }, [&](int p, double v) { gpf[p * GL.stride_p] = v; },
-            x[(int64_t)b * ldx + f], gy[(int64_t)b * ldgy + f]);
-    }
-}
-
-// ---------------------------------------------------------------- volume preserving shift (affine.py:366-456)
-__global__ void __launch_bounds__(256) volpres64_kernel(const double* __restrict__ x, int64_t ldx,
-                                                        const double* __restrict__ shift, int64_t ldp,
-                                                        const int32_t* __restrict__ periodic, double lower, double upper,
-                                                        double sign, double* __restrict__ y, int64_t ldy, int B, int D) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * D) return;
-    const int b = (int)(i / D), f = (int)(i % D);
-    double v = x[(int64_t)b * ldx + f] + sign * shift[(int64_t)b * ldp + f];
-    if (periodic && periodic[f]) v = py_mod(v, upper - lower) + lower;      // Python `%`, then + lower (affine.py:409, :454)
-    y[(int64_t)b * ldy + f] = v;
 }
 
 // ---------------------------------------------------------------- RQ spline (spline.py)
@@ -523,53 +423,6 @@ __global__ void __launch_bounds__(256) spline64_backward_kernel(const double* __
     }
 }
 
-// ---------------------------------------------------------------- periodic embedding (mafembed.py:112-145)
-// out = [x_non..., cos t, sin t, ...], t = (x - lower) * scale; backward: gx[p] = (-sin t g_cos + cos t g_sin) * scale
-template <bool BACKWARD>
-__global__ void __launch_bounds__(256) periodic_embedding64_kernel(const double* __restrict__ x, int64_t ldx,
-                                                                   const int32_t* __restrict__ pidx, int n_per,
-                                                                   const int32_t* __restrict__ nidx, int n_non,
-                                                                   double lower, double scale,
-                                                                   const double* __restrict__ gout, int64_t ldg,
-                                                                   double* __restrict__ out, int64_t ldo, int B) {
-    const int n_src = n_non + n_per;     // one thread per (row, source feature)
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * n_src) return;
-    const int b = (int)(i / n_src), j = (int)(i % n_src);
-    if (j < n_non) {
-        if (BACKWARD)
-            out[(int64_t)b * ldo + nidx[j]] = gout[(int64_t)b * ldg + j];
-        else
-            out[(int64_t)b * ldo + j] = x[(int64_t)b * ldx + nidx[j]];
-    } else {
-        const int q = j - n_non;
-        const double t = (x[(int64_t)b * ldx + pidx[q]] - lower) * scale;
-        double s, c;
-        sincos(t, &s, &c);
-        if (BACKWARD) {
-            const double gc = gout[(int64_t)b * ldg + n_non + 2 * q], gs = gout[(int64_t)b * ldg + n_non + 2 * q + 1];
-            out[(int64_t)b * ldo + pidx[q]] = (-s * gc + c * gs) * scale;
-        } else {
-            out[(int64_t)b * ldo + n_non + 2 * q] = c;
-            out[(int64_t)b * ldo + n_non + 2 * q + 1] = s;
-        }
-    }
-}
-
-// ---------------------------------------------------------------- column gather / scatter
-template <bool SCATTER>
-__global__ void __launch_bounds__(256) columns64_kernel(const double* __restrict__ src, int64_t lds,
-                                                        const int32_t* __restrict__ idx, int n_idx,
-                                                        double* __restrict__ dst, int64_t ldd, int B) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * n_idx) return;
-    const int b = (int)(i / n_idx), j = (int)(i % n_idx);
-    if (SCATTER)
-        dst[(int64_t)b * ldd + idx[j]] = src[(int64_t)b * lds + j];
-    else
-        dst[(int64_t)b * ldd + j] = src[(int64_t)b * lds + idx[j]];
-}
-
 // Host-side view and validation of a tfep_spline_desc_f64 (the rules of make_spline_args).
 int make_spline64(const tfep_spline_desc_f64* d, Spline64* a) {
     TFEP_REQUIRE(d != nullptr, "spline descriptor is NULL");
@@ -621,73 +474,6 @@ using namespace tfep;
 
 extern "C" {
 
-int tfep_sos_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, int n_polynomials,
-                         double* y, int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream) {
-    TFEP_REQUIRE(B >= 0 && D >= 0, "sos_f64: negative size");
-    TFEP_REQUIRE(n_polynomials >= 1, "sos_f64: n_polynomials=%d must be positive", n_polynomials);
-    if (B == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && y, "sos_f64: x/params/y must be non-NULL");
-    sos64_kernel<<<row_blocks64(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, n_polynomials, y, ldy, log_det_J,
-                                                                    accumulate, B, D);
-    return check_launch("sos64_kernel");
-}
-
-int tfep_sos_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, int n_polynomials,
-                          const double* gy, int64_t ldgy, double* gparams, tfep_param_layout glayout, double* gx,
-                          int64_t ldgx, int B, int D, void* stream) {
-    TFEP_REQUIRE(B >= 0 && D >= 0, "sos_backward_f64: negative size");
-    TFEP_REQUIRE(n_polynomials >= 1, "sos_backward_f64: n_polynomials=%d must be positive", n_polynomials);
-    if (B == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && gy && gparams && gx, "sos_backward_f64: NULL pointer");
-    sos64_backward_kernel<<<row_blocks64(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, n_polynomials, gy, ldgy,
-                                                                             gparams, glayout, gx, ldgx, B, D);
-    return check_launch("sos64_backward_kernel");
-}
-
-int tfep_affine_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, double* y,
-                            int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream) {
-    TFEP_REQUIRE(B >= 0 && D >= 0, "affine_f64: negative size");
-    if (B == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && y, "affine_f64: x/params/y must be non-NULL");
-    affine64_kernel<false><<<row_blocks64(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, y, ldy, log_det_J,
-                                                                             accumulate, B, D);
-    return check_launch("affine64_kernel");
-}
-
-int tfep_affine_inverse_f64(const double* y, int64_t ldy, const double* params, tfep_param_layout layout, double* x,
-                            int64_t ldx, double* log_det_J, int accumulate, int B, int D, void* stream) {
-    TFEP_REQUIRE(B >= 0 && D >= 0, "affine_f64: negative size");
-    if (B == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && y, "affine_f64: x/params/y must be non-NULL");
-    affine64_kernel<true><<<row_blocks64(B), 256, 0, (hipStream_t)stream>>>(y, ldy, params, layout, x, ldx, log_det_J,
-                                                                            accumulate, B, D);
-    return check_launch("affine64_kernel");
-}
-
-int tfep_affine_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, const double* gy,
-                             int64_t ldgy, const double* g_log_det_J, double* gparams, tfep_param_layout glayout, double* gx,
-                             int64_t ldgx, int B, int D, void* stream) {
-    TFEP_REQUIRE(B >= 0 && D >= 0, "affine_backward_f64: negative size");
-    if (B == 0 || D == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && gy && gparams && gx, "affine_backward_f64: NULL pointer");
-    affine64_backward_kernel<<<row_blocks64(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, gy, ldgy, g_log_det_J,
-                                                                               gparams, glayout, gx, ldgx, B, D);
-    return check_launch("affine64_backward_kernel");
-}
-
-int tfep_volume_preserving_shift_f64(const double* x, int64_t ldx, const double* shift, int64_t ldp,
-                                     const int32_t* periodic_mask, double lower, double upper, int sign, double* y,
-                                     int64_t ldy, int B, int D, void* stream) {
-    TFEP_REQUIRE(sign == 1 || sign == -1, "volume_preserving_shift_f64: sign must be +1 or -1");
-    TFEP_REQUIRE(B >= 0 && D >= 0, "volume_preserving_shift_f64: negative size");
-    if ((int64_t)B * D == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && shift && y, "volume_preserving_shift_f64: x/shift/y must be non-NULL");
-    const int64_t n = (int64_t)B * D;
-    volpres64_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, ldx, shift, ldp, periodic_mask, lower,
-                                                                                   upper, (double)sign, y, ldy, B, D);
-    return check_launch("volpres64_kernel");
-}
-
 int tfep_spline_n_parameters_per_feature_f64(const tfep_spline_desc_f64* d) {
     Spline64 a;
     int rc = make_spline64(d, &a);
@@ -727,58 +513,6 @@ int tfep_spline_backward_f64(const double* x, int64_t ldx, const double* params,
         spline64_backward_kernel<32><<<row_blocks64(B), 256, 0, s>>>(x, ldx, params, layout, a, gy, ldgy, g_log_det_J, gparams,
                                                                      glayout, gx, ldgx, B, D);
     return check_launch("spline64_backward_kernel");
-}
-
-int tfep_periodic_embedding_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
-                                const int32_t* nonperiodic_indices, int n_nonperiodic, double lower, double upper,
-                                double* out, int64_t ldo, int B, void* stream) {
-    TFEP_REQUIRE(B >= 0 && n_periodic >= 0 && n_nonperiodic >= 0, "periodic_embedding_f64: negative size");
-    TFEP_REQUIRE(B == 0 || (x && out), "periodic_embedding_f64: x/out must be non-NULL");
-    TFEP_REQUIRE(n_periodic == 0 || periodic_indices, "periodic_embedding_f64: periodic_indices is NULL");
-    TFEP_REQUIRE(n_nonperiodic == 0 || nonperiodic_indices, "periodic_embedding_f64: nonperiodic_indices is NULL");
-    TFEP_REQUIRE(upper != lower, "periodic_embedding_f64: empty period");
-    const int64_t n = (int64_t)B * (n_periodic + n_nonperiodic);
-    if (n == 0) return TFEP_OK;
-    const double scale = 2.0 * 3.14159265358979323846 / (upper - lower);
-    periodic_embedding64_kernel<false><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-        x, ldx, periodic_indices, n_periodic, nonperiodic_indices, n_nonperiodic, lower, scale, nullptr, 0, out, ldo, B);
-    return check_launch("periodic_embedding64_kernel");
-}
-
-int tfep_periodic_embedding_backward_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
-                                         const int32_t* nonperiodic_indices, int n_nonperiodic, double lower, double upper,
-                                         const double* gout, int64_t ldg, double* gx, int64_t ldgx, int B, void* stream) {
-    TFEP_REQUIRE(B >= 0 && n_periodic >= 0 && n_nonperiodic >= 0, "periodic_embedding_backward_f64: negative size");
-    TFEP_REQUIRE(upper != lower, "periodic_embedding_backward_f64: empty period");
-    const int64_t n = (int64_t)B * (n_periodic + n_nonperiodic);
-    if (n == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && gout && gx, "periodic_embedding_backward_f64: NULL pointer");
-    TFEP_REQUIRE(n_periodic == 0 || periodic_indices, "periodic_embedding_backward_f64: periodic_indices is NULL");
-    TFEP_REQUIRE(n_nonperiodic == 0 || nonperiodic_indices, "periodic_embedding_backward_f64: nonperiodic_indices is NULL");
-    const double scale = 2.0 * 3.14159265358979323846 / (upper - lower);
-    periodic_embedding64_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-        x, ldx, periodic_indices, n_periodic, nonperiodic_indices, n_nonperiodic, lower, scale, gout, ldg, gx, ldgx, B);
-    return check_launch("periodic_embedding64_kernel");
-}
-
-int tfep_gather_columns_f64(const double* src, int64_t lds, const int32_t* idx, int n_idx, double* dst, int64_t ldd, int B,
-                            void* stream) {
-    TFEP_REQUIRE(B >= 0 && n_idx >= 0, "gather_columns_f64: negative size");
-    const int64_t n = (int64_t)B * n_idx;
-    if (n == 0) return TFEP_OK;
-    TFEP_REQUIRE(src && dst && idx, "gather_columns_f64: NULL pointer");
-    columns64_kernel<false><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, lds, idx, n_idx, dst, ldd, B);
-    return check_launch("gather_columns_f64");
-}
-
-int tfep_scatter_columns_f64(const double* src, int64_t lds, const int32_t* idx, int n_idx, double* dst, int64_t ldd, int B,
-                             void* stream) {
-    TFEP_REQUIRE(B >= 0 && n_idx >= 0, "scatter_columns_f64: negative size");
-    const int64_t n = (int64_t)B * n_idx;
-    if (n == 0) return TFEP_OK;
-    TFEP_REQUIRE(src && dst && idx, "scatter_columns_f64: NULL pointer");
-    columns64_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, lds, idx, n_idx, dst, ldd, B);
-    return check_launch("scatter_columns_f64");
 }
 
 }  // extern "C"

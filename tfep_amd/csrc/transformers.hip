@@ -3,10 +3,14 @@
 // per-sample log|det J| reduction: one wavefront owns one sample (row), its 64 lanes walk the
 // features with unit stride (coalesced 256-B segments per parameter row) and the log-derivative
 // is summed in fp64 with a wave butterfly -- no atomics, bit-reproducible.
+// Affine, volume-preserving shift, SOS, periodic embedding and column gather / scatter are templates on the element
+// type: the float instantiation serves the float32 entry points, the double one their _f64 twins.  (The float64 RQ spline
+// has numerics of its own: spline_f64.hip.)
 #include "common.h"
 #include "spline.h"
 #include "moebius.h"
 #include "sos.h"
+#include "embedding.h"
 
 #include <stdarg.h>
 
@@ -29,36 +33,36 @@ int fail(int code, const char* fmt, ...) {
 
 constexpr int ROWS_PER_BLOCK = 4;   // 4 waves = 256 threads
 
-__device__ inline void store_ldj(float* ldj, int b, double total, int accumulate) {
+template <typename T>
+__device__ inline void store_ldj(T* ldj, int b, double total, int accumulate) {
     if ((threadIdx.x & 63) == 0) {
         if (accumulate)
-            ldj[b] = (float)((double)ldj[b] + total);
+            ldj[b] = (T)((double)ldj[b] + total);
         else
-            ldj[b] = (float)total;
+            ldj[b] = (T)total;
     }
 }
 
 // ---------------------------------------------------------------- affine (affine.py:321-323, :361-363)
-template <bool INVERSE>
-__global__ void __launch_bounds__(256) affine_kernel(const float* __restrict__ x, int64_t ldx,
-                                                     const float* __restrict__ params, tfep_param_layout L,
-                                                     float* __restrict__ y, int64_t ldy, float* __restrict__ ldj,
-                                                     int accumulate, int B, int D) {
+template <typename T, bool INVERSE>
+__global__ void __launch_bounds__(256) affine_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ params,
+                                                     tfep_param_layout L, T* __restrict__ y, int64_t ldy,
+                                                     T* __restrict__ ldj, int accumulate, int B, int D) {
     const int b = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (b >= B) return;
     const int lane = threadIdx.x & 63;
-    const float* xr = x + (int64_t)b * ldx;
-    const float* pr = params + (int64_t)b * L.ld;
-    float* yr = y + (int64_t)b * ldy;
+    const T* xr = x + (int64_t)b * ldx;
+    const T* pr = params + (int64_t)b * L.ld;
+    T* yr = y + (int64_t)b * ldy;
     double acc = 0.0;
     for (int f = lane; f < D; f += 64) {
-        const float shift = pr[f * L.stride_f];
-        const float ls = pr[L.stride_p + f * L.stride_f];
-        const float v = xr[f];
+        const T shift = pr[f * L.stride_f];
+        const T ls = pr[L.stride_p + f * L.stride_f];
+        const T v = xr[f];
         if (INVERSE)
-            yr[f] = (v - shift) * expf(-ls);
+            yr[f] = (v - shift) * exp(-ls);
         else
-            yr[f] = v * expf(ls) + shift;
+            yr[f] = v * exp(ls) + shift;
         acc += (double)ls;
     }
     acc = wave_sum(acc);
@@ -66,22 +70,16 @@ __global__ void __launch_bounds__(256) affine_kernel(const float* __restrict__ x
 }
 
 // ---------------------------------------------------------------- volume preserving shift (affine.py:366-456)
-__global__ void __launch_bounds__(256) volpres_kernel(const float* __restrict__ x, int64_t ldx,
-                                                      const float* __restrict__ shift, int64_t ldp,
-                                                      const int32_t* __restrict__ periodic, float lower,
-                                                      float upper, float sign, float* __restrict__ y,
-                                                      int64_t ldy, int B, int D) {
+// (py_mod: fmodf + sign fix-up in float32, floor + fma in float64; common.h)
+template <typename T>
+__global__ void __launch_bounds__(256) volpres_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ shift,
+                                                      int64_t ldp, const int32_t* __restrict__ periodic, T lower, T upper,
+                                                      T sign, T* __restrict__ y, int64_t ldy, int B, int D) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * D) return;
     const int b = (int)(i / D), f = (int)(i % D);
-    float v = x[(int64_t)b * ldx + f] + sign * shift[(int64_t)b * ldp + f];
-    if (periodic && periodic[f]) {
-        // float32 `%` with Python semantics, then + lower (affine.py:409, :454)
-        const float period = upper - lower;
-        float r = fmodf(v, period);
-        if (r != 0.f && ((r < 0.f) != (period < 0.f))) r += period;
-        v = r + lower;
-    }
+    T v = x[(int64_t)b * ldx + f] + sign * shift[(int64_t)b * ldp + f];
+    if (periodic && periodic[f]) v = py_mod(v, upper - lower) + lower;      // Python `%`, then + lower (affine.py:409, :454)
     y[(int64_t)b * ldy + f] = v;
 }
 
@@ -198,73 +196,51 @@ __global__ void __launch_bounds__(256) moebius_kernel(const float* __restrict__ 
 
 // ---------------------------------------------------------------- SOS polynomial (sos.py:198-265; sos.h)
 // K runtime; the log of the sum-of-squares derivative per element, summed in fp64 with the wave butterfly like the others.
-__global__ void __launch_bounds__(256) sos_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ params,
-                                                  tfep_param_layout L, int K, float* __restrict__ y, int64_t ldy,
-                                                  float* __restrict__ ldj, int accumulate, int B, int D) {
+template <typename T>
+__global__ void __launch_bounds__(256) sos_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ params,
+                                                  tfep_param_layout L, int K, T* __restrict__ y, int64_t ldy,
+                                                  T* __restrict__ ldj, int accumulate, int B, int D) {
     const int b = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (b >= B) return;
     const int lane = threadIdx.x & 63;
-    const float* xr = x + (int64_t)b * ldx;
-    const float* pr = params + (int64_t)b * L.ld;
-    float* yr = y + (int64_t)b * ldy;
+    const T* xr = x + (int64_t)b * ldx;
+    const T* pr = params + (int64_t)b * L.ld;
+    T* yr = y + (int64_t)b * ldy;
     double acc = 0.0;
     for (int f = lane; f < D; f += 64) {
-        const float* pf = pr + f * L.stride_f;
-        float d;
-        yr[f] = sos_element<0, float>(K, [&](int p) { return pf[p * L.stride_p]; }, xr[f], &d);
-        acc += (double)logf(d);
+        const T* pf = pr + f * L.stride_f;
+        T d;
+        yr[f] = sos_element<0, T>(K, [&](int p) { return pf[p * L.stride_p]; }, xr[f], &d);
+        acc += (double)log(d);
     }
     acc = wave_sum(acc);
     if (ldj) store_ldj(ldj, b, acc, accumulate);
 }
 
 // VJP: every parameter of every feature and the direct g_x; no log-det cotangent (non-differentiable in the reference).
-__global__ void __launch_bounds__(256) sos_backward_kernel(const float* __restrict__ x, int64_t ldx,
-                                                           const float* __restrict__ params, tfep_param_layout L, int K,
-                                                           const float* __restrict__ gy, int64_t ldgy,
-                                                           float* __restrict__ gparams, tfep_param_layout GL,
-                                                           float* __restrict__ gx, int64_t ldgx, int B, int D) {
+template <typename T>
+__global__ void __launch_bounds__(256) sos_backward_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ params,
+                                                           tfep_param_layout L, int K, const T* __restrict__ gy, int64_t ldgy,
+                                                           T* __restrict__ gparams, tfep_param_layout GL,
+                                                           T* __restrict__ gx, int64_t ldgx, int B, int D) {
     const int b = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (b >= B) return;
     const int lane = threadIdx.x & 63;
-    const float* pr = params + (int64_t)b * L.ld;
-    float* gpr = gparams + (int64_t)b * GL.ld;
+    const T* pr = params + (int64_t)b * L.ld;
+    T* gpr = gparams + (int64_t)b * GL.ld;
     for (int f = lane; f < D; f += 64) {
-        const float* pf = pr + f * L.stride_f;
-        float* gpf = gpr + f * GL.stride_f;
-        gx[(int64_t)b * ldgx + f] = sos_vjp_element<float>(
-            K, [&](int p) { return pf[p * L.stride_p]; }, [&](int p, float v) { gpf[p * GL.stride_p] = v; },
+        const T* pf = pr + f * L.stride_f;
+        T* gpf = gpr + f * GL.stride_f;
+        gx[(int64_t)b * ldgx + f] = sos_vjp_element<T>(
+            K, [&](int p) { return pf[p * L.stride_p]; }, [&](int p, T v) { gpf[p * GL.stride_p] = v; },
             x[(int64_t)b * ldx + f], gy[(int64_t)b * ldgy + f]);
     }
 }
 
-// ---------------------------------------------------------------- periodic embedding (mafembed.py:112-145)
-__global__ void __launch_bounds__(256) periodic_embedding_kernel(const float* __restrict__ x, int64_t ldx,
-                                                                 const int32_t* __restrict__ pidx, int n_per,
-                                                                 const int32_t* __restrict__ nidx, int n_non,
-                                                                 float lower, float scale,
-                                                                 float* __restrict__ out, int64_t ldo, int B) {
-    const int n_out = n_non + n_per;     // one thread per (row, source feature)
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * n_out) return;
-    const int b = (int)(i / n_out), j = (int)(i % n_out);
-    if (j < n_non) {
-        out[(int64_t)b * ldo + j] = x[(int64_t)b * ldx + nidx[j]];
-    } else {
-        const int q = j - n_non;
-        const float t = (x[(int64_t)b * ldx + pidx[q]] - lower) * scale;
-        float s, c;
-        sincosf(t, &s, &c);
-        out[(int64_t)b * ldo + n_non + 2 * q] = c;
-        out[(int64_t)b * ldo + n_non + 2 * q + 1] = s;
-    }
-}
-
 // ---------------------------------------------------------------- column gather / scatter
-template <bool SCATTER>
-__global__ void __launch_bounds__(256) columns_kernel(const float* __restrict__ src, int64_t lds,
-                                                      const int32_t* __restrict__ idx, int n_idx,
-                                                      float* __restrict__ dst, int64_t ldd, int B) {
+template <typename T, bool SCATTER>
+__global__ void __launch_bounds__(256) columns_kernel(const T* __restrict__ src, int64_t lds, const int32_t* __restrict__ idx,
+                                                      int n_idx, T* __restrict__ dst, int64_t ldd, int B) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * n_idx) return;
     const int b = (int)(i / n_idx), j = (int)(i % n_idx);
@@ -296,6 +272,81 @@ static int launch_spline(const float* x, int64_t ldx, const float* params, tfep_
     return check_launch("spline_kernel");
 }
 
+// Launchers shared by the float32 entry points and their _f64 twins; `who` prefixes the error messages.
+template <typename T, bool INVERSE>
+static int launch_affine(const char* who, const T* x, int64_t ldx, const T* params, tfep_param_layout L, T* y, int64_t ldy,
+                         T* ldj, int accumulate, int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "%s: negative size", who);
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && y, "%s: x/params/y must be non-NULL", who);
+    affine_kernel<T, INVERSE><<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, L, y, ldy, ldj, accumulate, B, D);
+    return check_launch("affine_kernel");
+}
+
+template <typename T>
+static int launch_sos(const char* who, const T* x, int64_t ldx, const T* params, tfep_param_layout L, int K, T* y,
+                      int64_t ldy, T* ldj, int accumulate, int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "%s: negative size", who);
+    TFEP_REQUIRE(K >= 1, "%s: n_polynomials=%d must be positive", who, K);
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && y, "%s: x/params/y must be non-NULL", who);
+    sos_kernel<T><<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, L, K, y, ldy, ldj, accumulate, B, D);
+    return check_launch("sos_kernel");
+}
+
+template <typename T>
+static int launch_sos_backward(const char* who, const T* x, int64_t ldx, const T* params, tfep_param_layout L, int K,
+                               const T* gy, int64_t ldgy, T* gparams, tfep_param_layout GL, T* gx, int64_t ldgx, int B, int D,
+                               void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "%s: negative size", who);
+    TFEP_REQUIRE(K >= 1, "%s: n_polynomials=%d must be positive", who, K);
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && gy && gparams && gx, "%s: NULL pointer", who);
+    sos_backward_kernel<T><<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, L, K, gy, ldgy, gparams, GL, gx,
+                                                                            ldgx, B, D);
+    return check_launch("sos_backward_kernel");
+}
+
+template <typename T>
+static int launch_volpres(const char* who, const T* x, int64_t ldx, const T* shift, int64_t ldp, const int32_t* periodic_mask,
+                          T lower, T upper, int sign, T* y, int64_t ldy, int B, int D, void* stream) {
+    TFEP_REQUIRE(sign == 1 || sign == -1, "%s: sign must be +1 or -1", who);
+    TFEP_REQUIRE(B >= 0 && D >= 0, "%s: negative size", who);
+    const int64_t n = (int64_t)B * D;
+    if (n == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && shift && y, "%s: x/shift/y must be non-NULL", who);
+    volpres_kernel<T><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, ldx, shift, ldp, periodic_mask, lower,
+                                                                                     upper, (T)sign, y, ldy, B, D);
+    return check_launch("volpres_kernel");
+}
+
+template <typename T>
+static int launch_periodic_embedding(const char* who, const T* x, int64_t ldx, const int32_t* pidx, int n_per,
+                                     const int32_t* nidx, int n_non, T lower, T upper, T* out, int64_t ldo, int B,
+                                     void* stream) {
+    TFEP_REQUIRE(B >= 0 && n_per >= 0 && n_non >= 0, "%s: negative size", who);
+    TFEP_REQUIRE(B == 0 || (x && out), "%s: x/out must be non-NULL", who);
+    TFEP_REQUIRE(n_per == 0 || pidx, "%s: periodic_indices is NULL", who);
+    TFEP_REQUIRE(n_non == 0 || nidx, "%s: nonperiodic_indices is NULL", who);
+    TFEP_REQUIRE(upper != lower, "%s: empty period", who);
+    const int64_t n = (int64_t)B * (n_per + n_non);
+    if (n == 0) return TFEP_OK;
+    periodic_embedding_kernel<T, false><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        x, ldx, pidx, n_per, nidx, n_non, lower, embedding_scale(lower, upper), nullptr, 0, out, ldo, B);
+    return check_launch("periodic_embedding_kernel");
+}
+
+template <typename T, bool SCATTER>
+static int launch_columns(const char* who, const T* src, int64_t lds, const int32_t* idx, int n_idx, T* dst, int64_t ldd,
+                          int B, void* stream) {
+    TFEP_REQUIRE(B >= 0 && n_idx >= 0, "%s: negative size", who);
+    const int64_t n = (int64_t)B * n_idx;
+    if (n == 0) return TFEP_OK;
+    TFEP_REQUIRE(src && dst && idx, "%s: NULL pointer", who);
+    columns_kernel<T, SCATTER><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, lds, idx, n_idx, dst, ldd, B);
+    return check_launch(who);
+}
+
 }  // namespace tfep
 
 using namespace tfep;
@@ -307,57 +358,60 @@ const char* tfep_last_error(void) { return last_error().c_str(); }
 
 int tfep_affine_forward(const float* x, int64_t ldx, const float* params, tfep_param_layout layout, float* y,
                         int64_t ldy, float* log_det_J, int accumulate, int B, int D, void* stream) {
-    TFEP_REQUIRE(B >= 0 && D >= 0, "affine: negative size");
-    if (B == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && y, "affine: x/params/y must be non-NULL");
-    affine_kernel<false><<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, y, ldy, log_det_J,
-                                                                         accumulate, B, D);
-    return check_launch("affine_kernel");
+    return launch_affine<float, false>("affine", x, ldx, params, layout, y, ldy, log_det_J, accumulate, B, D, stream);
 }
 
 int tfep_affine_inverse(const float* y, int64_t ldy, const float* params, tfep_param_layout layout, float* x,
                         int64_t ldx, float* log_det_J, int accumulate, int B, int D, void* stream) {
-    TFEP_REQUIRE(B >= 0 && D >= 0, "affine: negative size");
-    if (B == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && y, "affine: x/params/y must be non-NULL");
-    affine_kernel<true><<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(y, ldy, params, layout, x, ldx, log_det_J,
-                                                                        accumulate, B, D);
-    return check_launch("affine_kernel");
+    return launch_affine<float, true>("affine", y, ldy, params, layout, x, ldx, log_det_J, accumulate, B, D, stream);
+}
+
+int tfep_affine_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, double* y,
+                            int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream) {
+    return launch_affine<double, false>("affine_f64", x, ldx, params, layout, y, ldy, log_det_J, accumulate, B, D, stream);
+}
+
+int tfep_affine_inverse_f64(const double* y, int64_t ldy, const double* params, tfep_param_layout layout, double* x,
+                            int64_t ldx, double* log_det_J, int accumulate, int B, int D, void* stream) {
+    return launch_affine<double, true>("affine_f64", y, ldy, params, layout, x, ldx, log_det_J, accumulate, B, D, stream);
 }
 
 int tfep_sos_forward(const float* x, int64_t ldx, const float* params, tfep_param_layout layout, int n_polynomials,
                      float* y, int64_t ldy, float* log_det_J, int accumulate, int B, int D, void* stream) {
-    TFEP_REQUIRE(B >= 0 && D >= 0, "sos: negative size");
-    TFEP_REQUIRE(n_polynomials >= 1, "sos: n_polynomials=%d must be positive", n_polynomials);
-    if (B == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && y, "sos: x/params/y must be non-NULL");
-    sos_kernel<<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, n_polynomials, y, ldy, log_det_J,
-                                                                accumulate, B, D);
-    return check_launch("sos_kernel");
+    return launch_sos("sos", x, ldx, params, layout, n_polynomials, y, ldy, log_det_J, accumulate, B, D, stream);
+}
+
+int tfep_sos_forward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, int n_polynomials,
+                         double* y, int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream) {
+    return launch_sos("sos_f64", x, ldx, params, layout, n_polynomials, y, ldy, log_det_J, accumulate, B, D, stream);
 }
 
 int tfep_sos_backward(const float* x, int64_t ldx, const float* params, tfep_param_layout layout, int n_polynomials,
                       const float* gy, int64_t ldgy, float* gparams, tfep_param_layout glayout, float* gx, int64_t ldgx,
                       int B, int D, void* stream) {
-    TFEP_REQUIRE(B >= 0 && D >= 0, "sos_backward: negative size");
-    TFEP_REQUIRE(n_polynomials >= 1, "sos_backward: n_polynomials=%d must be positive", n_polynomials);
-    if (B == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && gy && gparams && gx, "sos_backward: NULL pointer");
-    sos_backward_kernel<<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, layout, n_polynomials, gy, ldgy,
-                                                                         gparams, glayout, gx, ldgx, B, D);
-    return check_launch("sos_backward_kernel");
+    return launch_sos_backward("sos_backward", x, ldx, params, layout, n_polynomials, gy, ldgy, gparams, glayout, gx, ldgx,
+                               B, D, stream);
+}
+
+int tfep_sos_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, int n_polynomials,
+                          const double* gy, int64_t ldgy, double* gparams, tfep_param_layout glayout, double* gx,
+                          int64_t ldgx, int B, int D, void* stream) {
+    return launch_sos_backward("sos_backward_f64", x, ldx, params, layout, n_polynomials, gy, ldgy, gparams, glayout, gx,
+                               ldgx, B, D, stream);
 }
 
 int tfep_volume_preserving_shift(const float* x, int64_t ldx, const float* shift, int64_t ldp,
                                  const int32_t* periodic_mask, float lower, float upper, int sign, float* y,
                                  int64_t ldy, int B, int D, void* stream) {
-    TFEP_REQUIRE(sign == 1 || sign == -1, "volume_preserving_shift: sign must be +1 or -1");
-    if ((int64_t)B * D == 0) return TFEP_OK;
-    TFEP_REQUIRE(x && shift && y, "volume_preserving_shift: x/shift/y must be non-NULL");
-    const int64_t n = (int64_t)B * D;
-    volpres_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, ldx, shift, ldp, periodic_mask,
-                                                                                 lower, upper, (float)sign, y, ldy, B, D);
-    return check_launch("volpres_kernel");
+    return launch_volpres("volume_preserving_shift", x, ldx, shift, ldp, periodic_mask, lower, upper, sign, y, ldy, B, D,
+                          stream);
+}
+
+int tfep_volume_preserving_shift_f64(const double* x, int64_t ldx, const double* shift, int64_t ldp,
+                                     const int32_t* periodic_mask, double lower, double upper, int sign, double* y,
+                                     int64_t ldy, int B, int D, void* stream) {
+    return launch_volpres("volume_preserving_shift_f64", x, ldx, shift, ldp, periodic_mask, lower, upper, sign, y, ldy, B, D,
+                          stream);
 }
 
 int tfep_spline_n_parameters_per_feature(const tfep_spline_desc* d) {
@@ -410,33 +464,35 @@ int tfep_moebius_forward_split_out(const float* x, int64_t ldx, const float* par
 int tfep_periodic_embedding(const float* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
                             const int32_t* nonperiodic_indices, int n_nonperiodic, float lower, float upper,
                             float* out, int64_t ldo, int B, void* stream) {
-    TFEP_REQUIRE(B == 0 || (x && out), "periodic_embedding: x/out must be non-NULL");
-    TFEP_REQUIRE(n_periodic == 0 || periodic_indices, "periodic_embedding: periodic_indices is NULL");
-    TFEP_REQUIRE(n_nonperiodic == 0 || nonperiodic_indices, "periodic_embedding: nonperiodic_indices is NULL");
-    const int64_t n = (int64_t)B * (n_periodic + n_nonperiodic);
-    if (n == 0) return TFEP_OK;
-    const float scale = (float)(2.0 * 3.14159265358979323846 / ((double)upper - (double)lower));
-    periodic_embedding_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-        x, ldx, periodic_indices, n_periodic, nonperiodic_indices, n_nonperiodic, lower, scale, out, ldo, B);
-    return check_launch("periodic_embedding_kernel");
+    return launch_periodic_embedding("periodic_embedding", x, ldx, periodic_indices, n_periodic, nonperiodic_indices,
+                                     n_nonperiodic, lower, upper, out, ldo, B, stream);
+}
+
+int tfep_periodic_embedding_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
+                                const int32_t* nonperiodic_indices, int n_nonperiodic, double lower, double upper,
+                                double* out, int64_t ldo, int B, void* stream) {
+    return launch_periodic_embedding("periodic_embedding_f64", x, ldx, periodic_indices, n_periodic, nonperiodic_indices,
+                                     n_nonperiodic, lower, upper, out, ldo, B, stream);
 }
 
 int tfep_gather_columns(const float* src, int64_t lds, const int32_t* idx, int n_idx, float* dst, int64_t ldd, int B,
                         void* stream) {
-    const int64_t n = (int64_t)B * n_idx;
-    if (n == 0) return TFEP_OK;
-    TFEP_REQUIRE(src && dst && idx, "gather_columns: NULL pointer");
-    columns_kernel<false><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, lds, idx, n_idx, dst, ldd, B);
-    return check_launch("gather_columns");
+    return launch_columns<float, false>("gather_columns", src, lds, idx, n_idx, dst, ldd, B, stream);
 }
 
 int tfep_scatter_columns(const float* src, int64_t lds, const int32_t* idx, int n_idx, float* dst, int64_t ldd, int B,
                          void* stream) {
-    const int64_t n = (int64_t)B * n_idx;
-    if (n == 0) return TFEP_OK;
-    TFEP_REQUIRE(src && dst && idx, "scatter_columns: NULL pointer");
-    columns_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, lds, idx, n_idx, dst, ldd, B);
-    return check_launch("scatter_columns");
+    return launch_columns<float, true>("scatter_columns", src, lds, idx, n_idx, dst, ldd, B, stream);
+}
+
+int tfep_gather_columns_f64(const double* src, int64_t lds, const int32_t* idx, int n_idx, double* dst, int64_t ldd, int B,
+                            void* stream) {
+    return launch_columns<double, false>("gather_columns_f64", src, lds, idx, n_idx, dst, ldd, B, stream);
+}
+
+int tfep_scatter_columns_f64(const double* src, int64_t lds, const int32_t* idx, int n_idx, double* dst, int64_t ldd, int B,
+                             void* stream) {
+    return launch_columns<double, true>("scatter_columns_f64", src, lds, idx, n_idx, dst, ldd, B, stream);
 }
 
 }  // extern "C"
