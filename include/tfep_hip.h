@@ -253,6 +253,17 @@ int tfep_moebius_forward_split_out(const float* x, int64_t ldx, const float* par
                                    float* y, int64_t ldy, float* log_det_J, int accumulate,
                                    void* y_split, int64_t ld_split, float* y_inv_scale, int B, int D, void* stream);
 
+/* Symmetrized Moebius transformer on `dimension`-vectors (moebius.py:481-629), dimension 2 .. 8, D = n_vectors * dimension:
+ *   y = |x| (f(x; w) + f(x; -w)) / |f(x; w) + f(x; -w)|  with f the Moebius map above on the sphere of radius |x|,
+ *   log|det J| = sum over vectors of log[(1 - r^2)(1 + r^2)^(d-1) / (4 q + (1 - r^2)^2)^(d/2)],
+ *   w_unit = max_radius / (1 + |w|) w,  r = |w_unit|,  q = r^2 - (x / |x| . w_unit)^2;  0 < max_radius < 1.
+ * inverse = 1: the analytic inverse (moebius.py:519-605) -- NOT the forward map on -w: the map is even in w.
+ * w = 0 is the identity with log-det 0 in both directions; the inverse is finite at w = 0 and at x parallel to w, where
+ * the reference divides 0 by 0 (csrc/symmoebius.h).  float I/O computes in fp64. */
+int tfep_symmetrized_moebius(const float* x, int64_t ldx, const float* params, int64_t ldp, int dimension, double max_radius,
+                             int inverse, float* y, int64_t ldy, float* log_det_J, int accumulate, int B, int D,
+                             void* stream);
+
 /* PeriodicEmbedding.forward (embeddings/mafembed.py:112-145):
  * out = [x[:, nonperiodic]..., cos t0, sin t0, cos t1, sin t1, ...], t = (x - lower) * 2pi/(upper-lower). */
 int tfep_periodic_embedding(const float* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
@@ -605,6 +616,12 @@ int tfep_moebius_backward(const float* x, int64_t ldx, const float* params, int6
                           const float* gy, int64_t ldgy, const float* g_log_det_J,
                           float* gparams, int64_t ldgp, float* gx, int64_t ldgx,
                           int B, int D, void* stream);
+/* VJP of the symmetrized Moebius map in the direction `inverse` (x = the input of that direction): gparams / gx (B, D)
+ * from the cotangents of the output and of the log-det (g_log_det_J (B) or NULL: the log-det carries gradient in both
+ * directions, moebius.py:481-629 is plain differentiable torch). */
+int tfep_symmetrized_moebius_backward(const float* x, int64_t ldx, const float* params, int64_t ldp, int dimension,
+                                      double max_radius, int inverse, const float* gy, int64_t ldgy, const float* g_log_det_J,
+                                      float* gparams, int64_t ldgp, float* gx, int64_t ldgx, int B, int D, void* stream);
 /* dst[b, c] = src[b, c] for a (B, C) block with row strides (VJP of the volume-preserving shift,
  * affine.py:366-411: gparams = gx = gy; and sub-blocks of MixedTransformer parameters). */
 int tfep_copy_2d(const float* src, int64_t lds, float* dst, int64_t ldd, int B, int C, void* stream);
@@ -697,6 +714,14 @@ int tfep_sos_forward_f64(const double* x, int64_t ldx, const double* params, tfe
 int tfep_sos_backward_f64(const double* x, int64_t ldx, const double* params, tfep_param_layout layout, int n_polynomials,
                           const double* gy, int64_t ldgy, double* gparams, tfep_param_layout glayout, double* gx,
                           int64_t ldgx, int B, int D, void* stream);
+/* float64 I/O and IEEE division, square root and logarithm */
+int tfep_symmetrized_moebius_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int dimension,
+                                 double max_radius, int inverse, double* y, int64_t ldy, double* log_det_J, int accumulate,
+                                 int B, int D, void* stream);
+int tfep_symmetrized_moebius_backward_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int dimension,
+                                          double max_radius, int inverse, const double* gy, int64_t ldgy,
+                                          const double* g_log_det_J, double* gparams, int64_t ldgp, double* gx, int64_t ldgx,
+                                          int B, int D, void* stream);
 /* periodic wrap with Python `%` semantics in fp64: y = (x + sign b) % (upper - lower) + lower on the periodic features. */
 int tfep_volume_preserving_shift_f64(const double* x, int64_t ldx, const double* shift, int64_t ldp,
                                      const int32_t* periodic_mask, double lower, double upper, int sign,

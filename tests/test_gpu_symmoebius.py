@@ -1,0 +1,391 @@
+"""GPU tests of the symmetrized Moebius transformer (reference transformers/moebius.py:193-372, :481-629) on its HIP kernels:
+forward, analytic inverse and the VJP of both in float32 and float64, MAF layers (forward, blocked and pass-per-degree
+inverse, training through the layer backward and through the inverse), a mixed transformer with this member, HIP-graph
+replay, against tests/golden/symmoebius.npz.
+
+Bounds: the project's parity bounds (float32: rel L2 1e-5, log-det 1e-5 max(1, max|ldj|); float64: 1e-10, gradients 1e-9;
+flows as tests/test_gpu_sos.py and tests/test_gpu_float64_flows.py).  Where the reference's OWN float32 run (the stored
+``*_f32`` results) is further from its float64 run than such a float32 bound, the bound is max(bound, 4 x that error):
+``f32_bound``.  It never depends on what the kernels return."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'symmoebius.npz')
+CASES = [(d, R) for d in (2, 3, 4) for R in (0.99, 0.7)]
+DTYPES = [torch.float32, torch.float64]
+
+
+def rel(a, b):
+    a, b = _np(a), _np(b)
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+
+
+def _np(a):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.asarray(a, np.float64)
+
+
+def _golden():
+    return np.load(GOLDEN)
+
+
+def f32_bound(bound, g, key, err):
+    """The float32 bound of a quantity: ``bound``, or 4 x the error ``err(f32, f64)`` of the reference's own float32 result
+    where that is larger (the reference's float32 inverse loses digits in sqrt(1 - a_inv^2), and a float32 conditioner's
+    rounding of w is amplified by the same cancellation)."""
+    return max(bound, 4.0 * err(g[key + '_f32'], g[key + '_f64']))
+
+
+def ldj_err(got, ref):
+    return float(np.abs(_np(got) - _np(ref)).max())
+
+
+def max_err(got, ref):
+    return float(np.abs(_np(got) - _np(ref)).max() / max(np.abs(_np(ref)).max(), 1e-300))
+
+
+def _case(g, d, R, dt, *keys):
+    return [torch.from_numpy(g[f'tr/d{d}_R{R}/{k}']).cuda().to(dt) for k in keys]
+
+
+def sym_torch(x, w, dim, R, inverse=False):
+    """float64 torch restatement of the reference's two functions (moebius.py:481-629) on (B, D) tensors."""
+    B = x.shape[0]
+    x, w = x.reshape(B, -1, dim), w.reshape(B, -1, dim)
+    xn = x.norm(dim=-1, keepdim=True)
+    wn = w.norm(dim=-1, keepdim=True)
+    u = R / (1 + wn) * w
+    r2 = (u * u).sum(-1, keepdim=True)
+
+    def log_det(xu):
+        q = r2 - (xu * u).sum(-1, keepdim=True) ** 2
+        return torch.log((1 - r2) * (1 + r2) ** (dim - 1) / (4 * q + (1 - r2) ** 2) ** (dim / 2)).squeeze(-1).sum(1)
+    if not inverse:
+        def f(ws):
+            diff = x - ws
+            return (xn ** 2 - (ws * ws).sum(-1, keepdim=True)) / (diff * diff).sum(-1, keepdim=True) * diff - ws
+        s = f(xn * u) + f(-xn * u)
+        return (xn * s / s.norm(dim=-1, keepdim=True)).reshape(B, -1), log_det(x / xn)
+    xu = x / xn
+    da = u / r2.sqrt()
+    a = (xu * da).sum(-1, keepdim=True)
+    db = xu - a * da
+    db = db / db.norm(dim=-1, keepdim=True)
+    a_inv = -a * (r2 + 1) / torch.sqrt(1 + r2 ** 2 + r2 * (4 * a ** 2 - 2))
+    x_inv = -(a_inv * da - torch.sqrt(1 - a_inv ** 2) * db)
+    return (xn * x_inv).reshape(B, -1), -log_det(x_inv)
+
+
+# ------------------------------------------------------------------ the transformer against the golden
+
+@pytest.mark.parametrize('dt', DTYPES)
+@pytest.mark.parametrize('d,R', CASES)
+def test_transformer_forward_and_inverse_against_the_reference(d, R, dt):
+    from tfep_amd.nn.transformers import SymmetrizedMoebiusTransformer
+    g = _golden()
+    name = f'tr/d{d}_R{R}'
+    x, w, yin = _case(g, d, R, dt, 'x', 'w', 'yin')
+    tr = SymmetrizedMoebiusTransformer(d, max_radius=R)
+    tol = 1e-5 if dt == torch.float32 else 1e-10
+    for sfx, fn, inp in (('', tr.forward, x), ('_inv', tr.inverse, yin)):
+        y, ldj = fn(inp, w)
+        assert y.dtype == dt and ldj.dtype == dt and y.shape == inp.shape and ldj.shape == (inp.shape[0],)
+        ref_y, ref_l = g[f'{name}/y{sfx}_f64'], g[f'{name}/ldj{sfx}_f64']
+        e_y, e_l = rel(y, ref_y), ldj_err(ldj, ref_l)
+        b_y, b_l = tol, tol * max(1.0, np.abs(ref_l).max())
+        if dt == torch.float32:      # (see f32_bound: no larger than the plain bound on these inputs except y_inv at d = 2, R = 0.99)
+            b_y = f32_bound(b_y, g, f'{name}/y{sfx}', rel)
+            b_l = f32_bound(b_l, g, f'{name}/ldj{sfx}', ldj_err)
+        print(f'{name}{sfx} {dt}: y rel L2 {e_y:.3e} (bound {b_y:.3e}), ldj err {e_l:.3e} (bound {b_l:.3e})')
+        assert e_y <= b_y and e_l <= b_l
+
+
+@pytest.mark.parametrize('dt', DTYPES)
+@pytest.mark.parametrize('d,R', CASES)
+def test_transformer_gradients_against_the_reference(d, R, dt):
+    """Gradients of sum(c y^2 + e y) + sum(g ldj) in both directions.  The kernels compute in fp64 on the float32-rounded
+    inputs of the float64 golden, so the float32 bound is the plain 1e-5 in BOTH directions (the reference's own float32
+    run through the inverse does not reach it at d = 2: that is its sqrt(1 - a_inv^2), which the closed form here avoids)."""
+    from tfep_amd.nn.transformers import SymmetrizedMoebiusTransformer
+    g = _golden()
+    name = f'tr/d{d}_R{R}'
+    x, w, yin, c, e, gl = _case(g, d, R, dt, 'x', 'w', 'yin', 'c', 'e', 'g')
+    tr = SymmetrizedMoebiusTransformer(d, max_radius=R)
+    tol = 1e-5 if dt == torch.float32 else 1e-9
+    for sfx, fn, inp in (('', tr.forward, x), ('_inv', tr.inverse, yin)):
+        xx, ww = inp.clone().requires_grad_(True), w.clone().requires_grad_(True)
+        y, ldj = fn(xx, ww)
+        ((c * y ** 2 + e * y).sum() + (gl * ldj).sum()).backward()
+        e_x, e_w = rel(xx.grad, g[f'{name}/gx{sfx}_f64']), rel(ww.grad, g[f'{name}/gw{sfx}_f64'])
+        print(f'{name}{sfx} {dt}: gx rel L2 {e_x:.3e}, gw rel L2 {e_w:.3e} (bound {tol:.1e})')
+        assert e_x <= tol and e_w <= tol
+
+
+# ------------------------------------------------------------------ properties of the map
+
+@pytest.mark.parametrize('dt', DTYPES)
+@pytest.mark.parametrize('d', [2, 3, 4, 5, 8])
+def test_round_trip_norms_evenness_and_identity(d, dt):
+    from tfep_amd import ops
+    gen = torch.Generator(device='cuda').manual_seed(11 + d)
+    B, D = 37, 7 * d
+    x = 2 * torch.randn(B, D, device='cuda', dtype=dt, generator=gen)
+    w = 3 * torch.randn(B, D, device='cuda', dtype=dt, generator=gen)
+    y, l = ops.symmetrized_moebius(x, w, d, 0.99)
+    xb, lb = ops.symmetrized_moebius(y, w, d, 0.99, inverse=True)
+    if dt == torch.float64:
+        assert float((xb - x).abs().max()) <= 1e-11 * float(x.abs().max())
+        assert float((l + lb).abs().max()) <= 1e-11 * max(1.0, float(l.abs().max()))
+    else:
+        assert rel(xb, x) <= 1e-5
+        assert float((l + lb).abs().max()) <= 1e-5 * max(1.0, float(l.abs().max()))
+    nx, ny = x.reshape(B, -1, d).norm(dim=-1), y.reshape(B, -1, d).norm(dim=-1)
+    assert torch.allclose(ny, nx, rtol=1e-6 if dt == torch.float32 else 1e-14, atol=0)
+    y2, l2 = ops.symmetrized_moebius(x, -w, d, 0.99)                # even in w
+    assert torch.allclose(y2, y, rtol=0, atol=1e-6 if dt == torch.float32 else 1e-14) and torch.allclose(l2, l, rtol=0, atol=1e-12)
+    for inverse in (False, True):                                    # w = 0: the identity, log-det 0, in both directions
+        y0, l0 = ops.symmetrized_moebius(x, torch.zeros_like(w), d, 0.99, inverse=inverse)
+        assert torch.allclose(y0, x, rtol=1e-6 if dt == torch.float32 else 1e-15, atol=0) and torch.all(l0 == 0)
+
+
+@pytest.mark.parametrize('dt', DTYPES)
+def test_runtime_dimension_kernel_against_a_torch_restatement(dt):
+    """d = 5 takes the run-time-d kernel; compared with ``sym_torch`` in float64 on the same (rounded) inputs."""
+    from tfep_amd.nn.transformers import SymmetrizedMoebiusTransformer
+    d, R, B = 5, 0.9, 48
+    gen = torch.Generator(device='cuda').manual_seed(5)
+    x = 2 * torch.randn(B, 4 * d, device='cuda', dtype=dt, generator=gen)
+    w = 3 * torch.randn(B, 4 * d, device='cuda', dtype=dt, generator=gen)
+    cy, cl = torch.randn(B, 4 * d, device='cuda', dtype=dt, generator=gen), torch.randn(B, device='cuda', dtype=dt, generator=gen)
+    tr = SymmetrizedMoebiusTransformer(d, max_radius=R)
+    tol, gtol = (1e-5, 1e-5) if dt == torch.float32 else (1e-10, 1e-9)
+    for inverse in (False, True):
+        xx, ww = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+        y, l = (tr.inverse if inverse else tr.forward)(xx, ww)
+        ((cy * y).sum() + (cl * l).sum()).backward()
+        xr, wr = x.double().clone().requires_grad_(True), w.double().clone().requires_grad_(True)
+        yr, lr = sym_torch(xr, wr, d, R, inverse)
+        ((cy.double() * yr).sum() + (cl.double() * lr).sum()).backward()
+        assert rel(y, yr) <= tol and ldj_err(l, lr) <= tol * max(1.0, float(lr.detach().abs().max()))
+        assert rel(xx.grad, xr.grad) <= gtol and rel(ww.grad, wr.grad) <= gtol
+
+
+@pytest.mark.parametrize('dt', DTYPES)
+def test_rows_do_not_depend_on_the_batch(dt):
+    from tfep_amd import ops
+    gen = torch.Generator(device='cuda').manual_seed(2)
+    for d in (2, 3, 4, 6):
+        x = 2 * torch.randn(1000, 300 * d, device='cuda', dtype=dt, generator=gen)        # more vectors than lanes
+        w = 3 * torch.randn(1000, 300 * d, device='cuda', dtype=dt, generator=gen)
+        for inverse in (False, True):
+            y, l = ops.symmetrized_moebius(x, w, d, 0.99, inverse=inverse)
+            y1, l1 = ops.symmetrized_moebius(x[617:618], w[617:618], d, 0.99, inverse=inverse)
+            assert torch.equal(y1[0], y[617]) and torch.equal(l1[0], l[617])
+
+
+def test_strided_inputs_empty_batches_accumulation_and_errors():
+    from tfep_amd import _lib, ops
+    gen = torch.Generator(device='cuda').manual_seed(3)
+    big = 2 * torch.randn(20, 40, device='cuda', generator=gen)
+    w = 3 * torch.randn(20, 12, device='cuda', generator=gen)
+    for x in (big[:, 3:15], big[:, 4:28:2], big[:, :12]):            # rows off the vector alignment, column stride 2, row stride 40
+        assert not x.is_contiguous()
+        for dim in (2, 3, 4):
+            y, l = ops.symmetrized_moebius(x, w, dim, 0.99)
+            yc, lc = ops.symmetrized_moebius(x.contiguous(), w, dim, 0.99)
+            assert torch.equal(y, yc) and torch.equal(l, lc)
+    x = big[:, :12].contiguous()
+    acc = torch.full((20,), 2.0, device='cuda')
+    _, l = ops.symmetrized_moebius(x, w, 3, 0.99)
+    _, l2 = ops.symmetrized_moebius(x, w, 3, 0.99, log_det_J=acc)
+    assert l2 is acc and torch.allclose(acc, l + 2.0, rtol=1e-6)
+    for dt in DTYPES:                                                 # B = 0
+        y, l = ops.symmetrized_moebius(torch.empty(0, 12, device='cuda', dtype=dt), torch.empty(0, 12, device='cuda', dtype=dt), 3, 0.99)
+        assert y.shape == (0, 12) and l.shape == (0,) and y.dtype == dt
+        e = torch.empty(0, 12, device='cuda', dtype=dt, requires_grad=True)
+        y, l = torch.ops.tfep.symmetrized_moebius_inverse(e, torch.empty(0, 12, device='cuda', dtype=dt), 3, 0.99)
+        (y.sum() + l.sum()).backward()
+        assert e.grad.shape == (0, 12)
+    with pytest.raises(TypeError):                                    # mixed float32 / float64
+        ops.symmetrized_moebius(x, w.double(), 3, 0.99)
+    with pytest.raises(TypeError):
+        ops.symmetrized_moebius(x.double(), w, 3, 0.99)
+    with pytest.raises(TypeError):
+        torch.ops.tfep.symmetrized_moebius_backward(x, w, x.double(), l, 3, 0.99, False)
+    for dim, match in ((1, 'unsupported'), (9, 'unsupported'), (5, 'not a multiple')):
+        with pytest.raises(ValueError, match=match):
+            ops.symmetrized_moebius(x, w, dim, 0.99)
+    with pytest.raises(ValueError, match='max_radius'):
+        ops.symmetrized_moebius(x, w, 3, 1.0)
+    lib = _lib.load()
+    assert lib.tfep_symmetrized_moebius(None, 12, None, 12, 3, 0.99, 0, None, 12, None, 0, 4, 12, None) != 0
+    assert lib.tfep_symmetrized_moebius(None, 12, None, 12, 3, 0.99, 0, None, 12, None, 0, -1, 12, None) != 0
+    assert lib.tfep_symmetrized_moebius_backward_f64(None, 12, None, 12, 3, 0.99, 0, None, 12, None, None, 12, None, 12, 4, 12, None) != 0
+    assert lib.tfep_symmetrized_moebius_backward(None, 12, None, 12, 3, 0.99, 2, None, 12, None, None, 12, None, 12, 4, 12, None) != 0
+
+
+@pytest.mark.parametrize('d', [2, 3, 5])
+def test_gradcheck_float64(d):
+    gen = torch.Generator(device='cuda').manual_seed(7)
+    x = (2 * torch.randn(3, 2 * d, device='cuda', dtype=torch.float64, generator=gen)).requires_grad_(True)
+    w = (3 * torch.randn(3, 2 * d, device='cuda', dtype=torch.float64, generator=gen)).requires_grad_(True)
+    for op in (torch.ops.tfep.symmetrized_moebius_forward, torch.ops.tfep.symmetrized_moebius_inverse):
+        assert torch.autograd.gradcheck(lambda a, b: op(a, b, d, 0.9), (x, w), eps=1e-6, atol=1e-6, rtol=1e-6)
+
+
+@pytest.mark.parametrize('dt', DTYPES)
+def test_opcheck(dt):
+    gen = torch.Generator(device='cuda').manual_seed(8)
+    x = (2 * torch.randn(5, 12, device='cuda', dtype=dt, generator=gen)).requires_grad_(True)
+    w = (3 * torch.randn(5, 12, device='cuda', dtype=dt, generator=gen)).requires_grad_(True)
+    gy, gl = torch.randn(5, 12, device='cuda', dtype=dt, generator=gen), torch.randn(5, device='cuda', dtype=dt, generator=gen)
+    torch.library.opcheck(torch.ops.tfep.symmetrized_moebius_forward.default, (x, w, 3, 0.99))
+    torch.library.opcheck(torch.ops.tfep.symmetrized_moebius_inverse.default, (x, w, 4, 0.99))
+    torch.library.opcheck(torch.ops.tfep.symmetrized_moebius_backward.default, (x.detach(), w.detach(), gy, gl, 3, 0.99, True))
+
+
+# ------------------------------------------------------------------ flows
+
+def build_flow(name, g=None):
+    """The tfep_amd twin of tools/gen_golden.py:symmoebius_flows()[name], weights from the golden."""
+    from tfep_amd.nn.conditioners import generate_degrees
+    from tfep_amd.nn.flows import MAF, SequentialFlow
+    from tfep_amd.nn.transformers import MixedTransformer, NeuralSplineTransformer, SymmetrizedMoebiusTransformer
+    if name == 'flow':           # D = 12: four 3-vectors, each inside one degree
+        flow = SequentialFlow(
+            MAF(generate_degrees(12, 'ascending', repeats=3), transformer=SymmetrizedMoebiusTransformer(3), initialize_identity=False),
+            MAF(generate_degrees(12, 'descending', repeats=3), transformer=SymmetrizedMoebiusTransformer(3), initialize_identity=False))
+    else:
+        mixed = MixedTransformer(
+            [SymmetrizedMoebiusTransformer(2), NeuralSplineTransformer(torch.full((6,), -4.0), torch.full((6,), 4.0), 8)],
+            [[0, 1, 2, 3], [4, 5, 6, 7, 8, 9]])
+        flow = SequentialFlow(MAF(generate_degrees(10, 'ascending'), transformer=mixed, initialize_identity=False))
+    if g is not None:
+        sd = flow.state_dict()
+        prefix = f'{name}/sd/'
+        gold = {k[len(prefix):]: g[k] for k in g.files if k.startswith(prefix)}
+        assert set(gold) == {k for k in sd if not k.endswith('.mask')}
+        for k, v in gold.items():
+            t = torch.from_numpy(np.asarray(v))
+            assert t.shape == sd[k].shape and t.dtype == sd[k].dtype, k
+            sd[k] = t
+        flow.load_state_dict(sd, strict=True)
+    return flow.cuda()
+
+
+@pytest.mark.parametrize('direction', ['forward', 'inverse'])
+@pytest.mark.parametrize('name', ['flow', 'mixed'])
+def test_flow_values_loss_and_gradients_against_the_reference(name, direction):
+    """float32 flows: values to the float32 bounds, loss / input gradient / parameter gradients to the bounds of
+    tests/test_gpu_sos.py, each widened by ``f32_bound`` where the reference's own float32 flow is further off (through the
+    inverse of the d = 2 mixed member the float32 conditioner's rounding of w is amplified)."""
+    from tfep_amd.loss import BoltzmannKLDivLoss
+    g = _golden()
+    flow = build_flow(name, g)
+    sfx = '' if direction == 'forward' else '_inv'
+    fn = flow.forward if direction == 'forward' else flow.inverse
+    x = torch.from_numpy(g[f'{name}/x']).cuda().requires_grad_(True)
+    c, d = torch.from_numpy(g[f'{name}/c']).cuda(), torch.from_numpy(g[f'{name}/d']).cuda()
+    with torch.no_grad():
+        y0, l0 = fn(x)
+    ref_l = g[f'{name}/ldj{sfx}_f64']
+    e_y, e_l = rel(y0, g[f'{name}/y{sfx}_f64']), ldj_err(l0, ref_l)
+    b_y = f32_bound(1e-5, g, f'{name}/y{sfx}', rel)
+    b_l = f32_bound(1e-5 * max(1.0, np.abs(ref_l).max()), g, f'{name}/ldj{sfx}', ldj_err)
+    print(f'{name}{sfx}: y rel L2 {e_y:.3e} (bound {b_y:.3e}), ldj err {e_l:.3e} (bound {b_l:.3e})')
+    assert e_y <= b_y and e_l <= b_l
+    y, ldj = fn(x)
+    assert torch.equal(y.detach(), y0) and torch.equal(ldj.detach(), l0)
+    loss = BoltzmannKLDivLoss()((c * y ** 2 + d * y).sum(dim=1), ldj)
+    loss.backward()
+    ref_loss = float(g[f'{name}/loss{sfx}_f64'])
+    e_loss = abs(float(loss.detach()) - ref_loss) / abs(ref_loss)
+    b_loss = f32_bound(2e-5, g, f'{name}/loss{sfx}', lambda a, b: abs(float(a) - float(b)) / abs(float(b)))
+    e_gx, b_gx = rel(x.grad, g[f'{name}/gx{sfx}_f64']), f32_bound(5e-5, g, f'{name}/gx{sfx}', rel)
+    print(f'{name}{sfx}: loss rel {e_loss:.3e} (bound {b_loss:.3e}), gx rel L2 {e_gx:.3e} (bound {b_gx:.3e})')
+    assert e_loss <= b_loss and e_gx < b_gx
+    for k, p in flow.named_parameters():
+        ref = g[f'{name}/grad{sfx}_f64/{k}']
+        assert p.grad is not None and tuple(p.grad.shape) == ref.shape, k
+        err = max_err(p.grad, ref)
+        bound = max(2e-4, 4.0 * max_err(g[f'{name}/grad{sfx}_f32/{k}'], ref))
+        print(f'{name}{sfx}: grad {k} max err {err:.3e} (bound {bound:.3e})')
+        assert err < bound, (k, err)
+
+
+@pytest.mark.parametrize('direction', ['forward', 'inverse'])
+@pytest.mark.parametrize('name', ['flow', 'mixed'])
+def test_float64_flow_against_the_reference(name, direction):
+    from tfep_amd.loss import BoltzmannKLDivLoss
+    g = _golden()
+    flow = build_flow(name, g).double()
+    sfx = '' if direction == 'forward' else '_inv'
+    fn = flow.forward if direction == 'forward' else flow.inverse
+    x = torch.from_numpy(g[f'{name}/x']).cuda().double().requires_grad_(True)
+    c, d = (torch.from_numpy(g[f'{name}/{k}']).cuda().double() for k in ('c', 'd'))
+    y, ldj = fn(x)
+    assert y.dtype == torch.float64 and ldj.dtype == torch.float64
+    # the bounds of tests/test_gpu_float64_flows.py: forward rtol 1e-9 (atol 1e-10 / 1e-9), inverse rtol 1e-8 (atol 1e-9 / 1e-8)
+    rt, at_y, at_l = (1e-9, 1e-10, 1e-9) if direction == 'forward' else (1e-8, 1e-9, 1e-8)
+    np.testing.assert_allclose(_np(y), g[f'{name}/y{sfx}_f64'], rtol=rt, atol=at_y)
+    np.testing.assert_allclose(_np(ldj), g[f'{name}/ldj{sfx}_f64'], rtol=rt, atol=at_l)
+    loss = BoltzmannKLDivLoss()((c * y ** 2 + d * y).sum(dim=1), ldj)
+    loss.backward()
+    np.testing.assert_allclose(float(loss.detach()), float(g[f'{name}/loss{sfx}_f64']), rtol=1e-9)
+    errs = {'gx': max_err(x.grad, g[f'{name}/gx{sfx}_f64'])}
+    for k, p in flow.named_parameters():
+        assert p.grad is not None, k
+        errs[k] = max_err(p.grad, g[f'{name}/grad{sfx}_f64/{k}'])
+    print(f'{name}{sfx} float64: largest gradient error {max(errs.values()):.3e}')
+    assert all(e <= 1e-9 for e in errs.values()), errs          # grad_close of test_gpu_float64_flows.py
+
+
+def test_blocked_inverse_equals_the_pass_per_degree_inverse():
+    g = _golden()
+    flow = build_flow('flow', g)
+    y = torch.from_numpy(g['flow/x']).cuda()
+    assert all(layer._blocked_ok() for layer in flow)
+    with torch.no_grad():
+        xb, lb = flow.inverse(y)
+        for layer in flow:
+            layer.blocked_inverse = False
+        assert not any(layer._blocked_ok() for layer in flow)
+        xp, lp = flow.inverse(y)
+    assert rel(xb, xp) <= 1e-5 and ldj_err(lb, lp) <= 1e-5 * max(1.0, float(lp.abs().max()))
+    assert rel(xb, g['flow/y_inv_f64']) <= f32_bound(1e-5, g, 'flow/y_inv', rel)
+
+
+def test_float64_layer_round_trip_on_the_pass_per_degree_inverse():
+    """A float64 layer inverts with the reference's pass per degree (no blocked inverse in float64).  Every vector inside
+    one degree: only then is the layer autoregressive, and the inverse an inverse.  (Vectors that straddle degrees are covered
+    by the mixed flow of the golden, whose d = 2 member sits on ascending degrees.)"""
+    from tfep_amd.nn.conditioners import generate_degrees
+    from tfep_amd.nn.flows import MAF
+    from tfep_amd.nn.transformers import SymmetrizedMoebiusTransformer
+    torch.manual_seed(0)
+    layer = MAF(generate_degrees(8, 'ascending', repeats=4), transformer=SymmetrizedMoebiusTransformer(4),
+                initialize_identity=False).cuda().double()
+    assert not layer._blocked_ok()
+    x = torch.randn(50, 8, device='cuda', dtype=torch.float64)
+    with torch.no_grad():
+        y, l = layer(x)
+        xb, lb = layer.inverse(y)
+    assert rel(xb, x) <= 1e-10 and float((l + lb).abs().max()) <= 1e-10
+
+
+def test_graph_replay_equals_eager():
+    from tfep_amd.graphs import GraphedFlow
+    g = _golden()
+    flow = build_flow('flow', g)
+    x = torch.from_numpy(g['flow/x']).cuda()
+    with torch.no_grad():
+        y, l = flow(x)
+    graphed = GraphedFlow(flow, x.shape[0], x.shape[1])
+    for _ in range(2):
+        yg, lg = graphed(x)
+        assert torch.equal(yg, y) and torch.equal(lg, l)

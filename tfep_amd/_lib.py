@@ -143,6 +143,14 @@ _SIGNATURES = {
                                     _P, c_int, c_int, c_int, _P]),
     'tfep_moebius_forward': (c_int, [_P, c_int64, _P, c_int64, c_int, c_float, c_int, c_int,
                                      _P, c_int64, _P, c_int, c_int, c_int, _P]),
+    'tfep_symmetrized_moebius': (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, c_int, c_int,
+                                         c_int, _P]),
+    'tfep_symmetrized_moebius_backward': (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, _P,
+                                                  c_int64, _P, c_int64, c_int, c_int, _P]),
+    'tfep_symmetrized_moebius_f64': (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, c_int, c_int,
+                                             c_int, _P]),
+    'tfep_symmetrized_moebius_backward_f64': (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, _P,
+                                                      c_int64, _P, c_int64, c_int, c_int, _P]),
     'tfep_moebius_forward_split_out': (c_int, [_P, c_int64, _P, c_int64, c_float, _P, c_int64, _P, c_int, _P, c_int64, _P,
                                                c_int, c_int, _P]),
     'tfep_periodic_embedding': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_float, c_float,

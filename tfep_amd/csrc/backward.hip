@@ -10,6 +10,7 @@
 #include "common.h"
 #include "spline.h"
 #include "fp64_fast.h"
+#include "symmoebius.h"
 #include "embedding.h"
 
 namespace tfep {
@@ -761,6 +762,40 @@ __global__ void __launch_bounds__(256) moebius_backward_kernel(const float* __re
     }
 }
 
+// ---------------------------------------------------------------- symmetrized Moebius VJP (moebius.py:481-629)
+// Reverse mode through symmoebius_vector (symmoebius.h), forward or inverse direction; one lane per vector, the cotangent
+// of the row's log-det enters every vector.  gldj may be NULL (no log-det cotangent).
+template <typename T, int DIM, bool INVERSE>
+__global__ void __launch_bounds__(256) symmoebius_backward_kernel(const T* __restrict__ x, int64_t ldx,
+                                                                  const T* __restrict__ params, int64_t ldp, int dim_rt,
+                                                                  double max_radius, const T* __restrict__ gy, int64_t ldgy,
+                                                                  const T* __restrict__ gldj, T* __restrict__ gparams,
+                                                                  int64_t ldgp, T* __restrict__ gx, int64_t ldgx, int B, int D) {
+    const int b = blockIdx.x * ROWS_PER_BLOCK_B + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const int dim = DIM > 0 ? DIM : dim_rt;
+    const int nvec = D / dim;
+    const double gl = gldj ? (double)gldj[b] : 0.0;
+    for (int v = lane; v < nvec; v += 64) {
+        double xv[MOEBIUS_MAX_DIM], wv[MOEBIUS_MAX_DIM], gyv[MOEBIUS_MAX_DIM], gxv[MOEBIUS_MAX_DIM], gwv[MOEBIUS_MAX_DIM];
+#pragma unroll
+        for (int i = 0; i < MOEBIUS_MAX_DIM; ++i)
+            if (i < dim) {
+                xv[i] = (double)x[(int64_t)b * ldx + v * dim + i];
+                wv[i] = (double)params[(int64_t)b * ldp + v * dim + i];
+                gyv[i] = (double)gy[(int64_t)b * ldgy + v * dim + i];
+            }
+        symmoebius_vjp_vector<T, INVERSE>(xv, wv, dim, max_radius, gyv, gl, gxv, gwv);
+#pragma unroll
+        for (int i = 0; i < MOEBIUS_MAX_DIM; ++i)
+            if (i < dim) {
+                gparams[(int64_t)b * ldgp + v * dim + i] = (T)gwv[i];
+                gx[(int64_t)b * ldgx + v * dim + i] = (T)gxv[i];
+            }
+    }
+}
+
 // dst[b, c] = src[b, c]
 __global__ void __launch_bounds__(256) copy_2d_kernel(const float* __restrict__ src, int64_t lds,
                                                       float* __restrict__ dst, int64_t ldd, int B, int C) {
@@ -828,6 +863,39 @@ static int launch_periodic_embedding_backward(const char* who, const T* x, int64
     periodic_embedding_kernel<T, true><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
         x, ldx, pidx, n_per, nidx, n_non, lower, embedding_scale(lower, upper), gout, ldg, gx, ldgx, B);
     return check_launch("periodic_embedding_kernel");
+}
+
+template <typename T, bool INVERSE>
+static int launch_symmoebius_backward_dir(const T* x, int64_t ldx, const T* params, int64_t ldp, int dim, double max_radius,
+                                          const T* gy, int64_t ldgy, const T* gl, T* gparams, int64_t ldgp, T* gx,
+                                          int64_t ldgx, int B, int D, hipStream_t s) {
+    auto kernel = dim == 2   ? symmoebius_backward_kernel<T, 2, INVERSE>
+                  : dim == 3 ? symmoebius_backward_kernel<T, 3, INVERSE>
+                  : dim == 4 ? symmoebius_backward_kernel<T, 4, INVERSE>
+                             : symmoebius_backward_kernel<T, 0, INVERSE>;
+    kernel<<<row_blocks_b(B), 256, 0, s>>>(x, ldx, params, ldp, dim, max_radius, gy, ldgy, gl, gparams, ldgp, gx, ldgx, B, D);
+    return check_launch("symmoebius_backward_kernel");
+}
+
+template <typename T>
+static int launch_symmoebius_backward(const char* who, const T* x, int64_t ldx, const T* params, int64_t ldp, int dimension,
+                                      double max_radius, int inverse, const T* gy, int64_t ldgy, const T* gl, T* gparams,
+                                      int64_t ldgp, T* gx, int64_t ldgx, int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "%s: negative size", who);
+    TFEP_REQUIRE(dimension >= 2 && dimension <= MOEBIUS_MAX_DIM, "%s: dimension=%d unsupported (2..%d)", who, dimension,
+                 MOEBIUS_MAX_DIM);
+    TFEP_REQUIRE(D % dimension == 0, "%s: n_features=%d is not a multiple of dimension=%d", who, D, dimension);
+    TFEP_REQUIRE(max_radius > 0.0 && max_radius < 1.0, "%s: max_radius=%g must lie in (0, 1)", who, max_radius);
+    TFEP_REQUIRE(inverse == 0 || inverse == 1, "%s: inverse must be 0 or 1", who);
+    if (B == 0 || D == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && gy && gparams && gx, "%s: NULL pointer", who);
+    TFEP_REQUIRE(ldx >= D && ldp >= D && ldgy >= D && ldgp >= D && ldgx >= D, "%s: a row stride is shorter than n_features=%d",
+                 who, D);
+    hipStream_t s = (hipStream_t)stream;
+    return inverse ? launch_symmoebius_backward_dir<T, true>(x, ldx, params, ldp, dimension, max_radius, gy, ldgy, gl, gparams,
+                                                             ldgp, gx, ldgx, B, D, s)
+                   : launch_symmoebius_backward_dir<T, false>(x, ldx, params, ldp, dimension, max_radius, gy, ldgy, gl, gparams,
+                                                              ldgp, gx, ldgx, B, D, s);
 }
 
 }  // namespace tfep
@@ -919,6 +987,21 @@ int tfep_moebius_backward(const float* x, int64_t ldx, const float* params, int6
                                                                              unit_sphere, (float)sign, gy, ldgy, g_log_det_J,
                                                                              gparams, ldgp, gx, ldgx, B, D);
     return check_launch("moebius_backward_kernel");
+}
+
+int tfep_symmetrized_moebius_backward(const float* x, int64_t ldx, const float* params, int64_t ldp, int dimension,
+                                      double max_radius, int inverse, const float* gy, int64_t ldgy, const float* g_log_det_J,
+                                      float* gparams, int64_t ldgp, float* gx, int64_t ldgx, int B, int D, void* stream) {
+    return launch_symmoebius_backward("symmetrized_moebius_backward", x, ldx, params, ldp, dimension, max_radius, inverse, gy,
+                                      ldgy, g_log_det_J, gparams, ldgp, gx, ldgx, B, D, stream);
+}
+
+int tfep_symmetrized_moebius_backward_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int dimension,
+                                          double max_radius, int inverse, const double* gy, int64_t ldgy,
+                                          const double* g_log_det_J, double* gparams, int64_t ldgp, double* gx, int64_t ldgx,
+                                          int B, int D, void* stream) {
+    return launch_symmoebius_backward("symmetrized_moebius_backward_f64", x, ldx, params, ldp, dimension, max_radius, inverse,
+                                      gy, ldgy, g_log_det_J, gparams, ldgp, gx, ldgx, B, D, stream);
 }
 
 int tfep_copy_2d(const float* src, int64_t lds, float* dst, int64_t ldd, int B, int C, void* stream) {

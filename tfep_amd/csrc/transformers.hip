@@ -3,12 +3,13 @@
 // per-sample log|det J| reduction: one wavefront owns one sample (row), its 64 lanes walk the
 // features with unit stride (coalesced 256-B segments per parameter row) and the log-derivative
 // is summed in fp64 with a wave butterfly -- no atomics, bit-reproducible.
-// Affine, volume-preserving shift, SOS, periodic embedding and column gather / scatter are templates on the element
+// Affine, volume-preserving shift, SOS, symmetrized Moebius, periodic embedding and column gather / scatter are templates on the element
 // type: the float instantiation serves the float32 entry points, the double one their _f64 twins.  (The float64 RQ spline
 // has numerics of its own: spline_f64.hip.)
 #include "common.h"
 #include "spline.h"
 #include "moebius.h"
+#include "symmoebius.h"
 #include "sos.h"
 #include "embedding.h"
 
@@ -194,6 +195,59 @@ __global__ void __launch_bounds__(256) moebius_kernel(const float* __restrict__ 
     if (ldj) store_ldj(ldj, b, acc, accumulate);
 }
 
+// ---------------------------------------------------------------- symmetrized Moebius (moebius.py:481-629; symmoebius.h)
+// One lane per d-vector like moebius_kernel; DIM = 2, 3, 4 at compile time (4: quaternions), DIM = 0: any d.  A vector of
+// 8 or 16 bytes is one load / store when the three rows start on such a boundary (wave uniform).
+template <typename T, int DIM, bool INVERSE>
+__global__ void __launch_bounds__(256) symmoebius_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ params,
+                                                         int64_t ldp, int dim_rt, double max_radius, T* __restrict__ y,
+                                                         int64_t ldy, T* __restrict__ ldj, int accumulate, int B, int D) {
+    const int b = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const int dim = DIM > 0 ? DIM : dim_rt;
+    const int nvec = D / dim;
+    const T* xr = x + (int64_t)b * ldx;
+    const T* pr = params + (int64_t)b * ldp;
+    T* yr = y + (int64_t)b * ldy;
+    constexpr int VB = DIM * (int)sizeof(T);                    // bytes of one vector
+    constexpr bool CAN_PACK = VB == 8 || VB == 16;
+    struct alignas(CAN_PACK ? VB : (int)sizeof(T)) Pack { T v[DIM > 0 ? DIM : 1]; };
+    const bool packed = CAN_PACK && (((uintptr_t)xr | (uintptr_t)pr | (uintptr_t)yr) & (uintptr_t)(VB - 1)) == 0;
+    double acc = 0.0;
+    for (int v = lane; v < nvec; v += 64) {
+        double xv[MOEBIUS_MAX_DIM], wv[MOEBIUS_MAX_DIM], yv[MOEBIUS_MAX_DIM];
+        if (packed) {
+            const Pack xx = reinterpret_cast<const Pack*>(xr)[v], pp = reinterpret_cast<const Pack*>(pr)[v];
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) {
+                xv[i] = (double)xx.v[i];
+                wv[i] = (double)pp.v[i];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < MOEBIUS_MAX_DIM; ++i)
+                if (i < dim) {
+                    xv[i] = (double)xr[v * dim + i];
+                    wv[i] = (double)pr[v * dim + i];
+                }
+        }
+        acc += symmoebius_vector<T, INVERSE>(xv, wv, dim, max_radius, yv);
+        if (packed) {
+            Pack yy;
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) yy.v[i] = (T)yv[i];
+            reinterpret_cast<Pack*>(yr)[v] = yy;
+        } else {
+#pragma unroll
+            for (int i = 0; i < MOEBIUS_MAX_DIM; ++i)
+                if (i < dim) yr[v * dim + i] = (T)yv[i];
+        }
+    }
+    acc = wave_sum(acc);
+    if (ldj) store_ldj(ldj, b, acc, accumulate);
+}
+
 // ---------------------------------------------------------------- SOS polynomial (sos.py:198-265; sos.h)
 // K runtime; the log of the sum-of-squares derivative per element, summed in fp64 with the wave butterfly like the others.
 template <typename T>
@@ -292,6 +346,34 @@ static int launch_sos(const char* who, const T* x, int64_t ldx, const T* params,
     TFEP_REQUIRE(x && params && y, "%s: x/params/y must be non-NULL", who);
     sos_kernel<T><<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, L, K, y, ldy, ldj, accumulate, B, D);
     return check_launch("sos_kernel");
+}
+
+template <typename T, bool INVERSE>
+static int launch_symmoebius_dir(const T* x, int64_t ldx, const T* params, int64_t ldp, int dim, double max_radius, T* y,
+                                 int64_t ldy, T* ldj, int accumulate, int B, int D, hipStream_t s) {
+    auto kernel = dim == 2 ? symmoebius_kernel<T, 2, INVERSE> : dim == 3 ? symmoebius_kernel<T, 3, INVERSE>
+                : dim == 4 ? symmoebius_kernel<T, 4, INVERSE> : symmoebius_kernel<T, 0, INVERSE>;
+    kernel<<<row_blocks(B), 256, 0, s>>>(x, ldx, params, ldp, dim, max_radius, y, ldy, ldj, accumulate, B, D);
+    return check_launch("symmoebius_kernel");
+}
+
+template <typename T>
+static int launch_symmoebius(const char* who, const T* x, int64_t ldx, const T* params, int64_t ldp, int dimension,
+                             double max_radius, int inverse, T* y, int64_t ldy, T* ldj, int accumulate, int B, int D,
+                             void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "%s: negative size", who);
+    TFEP_REQUIRE(dimension >= 2 && dimension <= MOEBIUS_MAX_DIM, "%s: dimension=%d unsupported (2..%d)", who, dimension,
+                 MOEBIUS_MAX_DIM);
+    TFEP_REQUIRE(D % dimension == 0, "%s: n_features=%d is not a multiple of dimension=%d", who, D, dimension);
+    TFEP_REQUIRE(max_radius > 0.0 && max_radius < 1.0, "%s: max_radius=%g must lie in (0, 1)", who, max_radius);
+    TFEP_REQUIRE(inverse == 0 || inverse == 1, "%s: inverse must be 0 or 1", who);
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(D == 0 || (x && params && y), "%s: x/params/y must be non-NULL", who);
+    TFEP_REQUIRE(ldx >= D && ldp >= D && ldy >= D, "%s: a row stride is shorter than n_features=%d", who, D);
+    return inverse ? launch_symmoebius_dir<T, true>(x, ldx, params, ldp, dimension, max_radius, y, ldy, ldj, accumulate, B, D,
+                                                    (hipStream_t)stream)
+                   : launch_symmoebius_dir<T, false>(x, ldx, params, ldp, dimension, max_radius, y, ldy, ldj, accumulate, B, D,
+                                                     (hipStream_t)stream);
 }
 
 template <typename T>
@@ -445,6 +527,20 @@ int tfep_moebius_forward(const float* x, int64_t ldx, const float* params, int64
     kernel<<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, ldp, dimension, max_radius, unit_sphere, (float)sign, y,
                                                            ldy, log_det_J, accumulate, B, D, nullptr, 0, nullptr);
     return check_launch("moebius_kernel");
+}
+
+int tfep_symmetrized_moebius(const float* x, int64_t ldx, const float* params, int64_t ldp, int dimension, double max_radius,
+                             int inverse, float* y, int64_t ldy, float* log_det_J, int accumulate, int B, int D,
+                             void* stream) {
+    return launch_symmoebius("symmetrized_moebius", x, ldx, params, ldp, dimension, max_radius, inverse, y, ldy, log_det_J,
+                             accumulate, B, D, stream);
+}
+
+int tfep_symmetrized_moebius_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int dimension,
+                                 double max_radius, int inverse, double* y, int64_t ldy, double* log_det_J, int accumulate,
+                                 int B, int D, void* stream) {
+    return launch_symmoebius("symmetrized_moebius_f64", x, ldx, params, ldp, dimension, max_radius, inverse, y, ldy,
+                             log_det_J, accumulate, B, D, stream);
 }
 
 int tfep_moebius_forward_split_out(const float* x, int64_t ldx, const float* params, int64_t ldp, float max_radius, float* y, int64_t ldy,

@@ -28,7 +28,7 @@ from ..masked import GRAD_IS_MASKED
 from ..embeddings.mafembed import MAFEmbedding, PeriodicEmbedding
 from ..transformers.affine import AffineTransformer, VolumePreservingShiftTransformer
 from ..transformers.mixed import MixedTransformer
-from ..transformers.moebius import MoebiusTransformer
+from ..transformers.moebius import MoebiusTransformer, SymmetrizedMoebiusTransformer
 from ..transformers.sos import SOSPolynomialTransformer
 from ..transformers.spline import NeuralSplineTransformer
 
@@ -62,7 +62,8 @@ def _embedding_params(layer):
 
 
 def _transformer_supported(tr):
-    if type(tr) in (AffineTransformer, MoebiusTransformer, VolumePreservingShiftTransformer, SOSPolynomialTransformer):
+    if type(tr) in (AffineTransformer, MoebiusTransformer, VolumePreservingShiftTransformer, SOSPolynomialTransformer,
+                    SymmetrizedMoebiusTransformer):
         return True
     if type(tr) is NeuralSplineTransformer:
         return True
@@ -110,6 +111,9 @@ def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, 
         elif type(tr) is SOSPolynomialTransformer:
             _lib.call('tfep_sos_backward_f64', _lib.ptr(x), D, th, lay, int(tr.n_polynomials), _lib.ptr(gy), D, gth, lay,
                       _lib.ptr(gx), D, B, D, stream)
+        elif type(tr) is SymmetrizedMoebiusTransformer:
+            _lib.call('tfep_symmetrized_moebius_backward_f64', _lib.ptr(x), D, th, ld_theta, int(tr.dimension),
+                      float(tr.max_radius), 0, _lib.ptr(gy), D, _lib.ptr(gl), gth, ld_theta, _lib.ptr(gx), D, B, D, stream)
         elif type(tr) is VolumePreservingShiftTransformer:
             gtheta[:, th_off:th_off + D].copy_(gy)     # y = x + b: the cotangent passes to b and to x unchanged
             gx.copy_(gy)
@@ -130,6 +134,9 @@ def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, 
         _lib.call('tfep_moebius_backward', _lib.ptr(x), D, th, ld_theta, int(tr.dimension), float(tr.max_radius),
                   int(bool(tr.unit_sphere)), 1, _lib.ptr(gy), D, _lib.ptr(gl), gth, ld_theta, _lib.ptr(gx), D, B, D,
                   stream)
+    elif type(tr) is SymmetrizedMoebiusTransformer:
+        _lib.call('tfep_symmetrized_moebius_backward', _lib.ptr(x), D, th, ld_theta, int(tr.dimension), float(tr.max_radius),
+                  0, _lib.ptr(gy), D, _lib.ptr(gl), gth, ld_theta, _lib.ptr(gx), D, B, D, stream)
     else:   # volume-preserving shift: y = x + b (wrap is piecewise identity), log-det = 0
         _lib.call('tfep_copy_2d', _lib.ptr(gy), D, gth, ld_theta, B, D, stream)
         _lib.call('tfep_copy_2d', _lib.ptr(gy), D, _lib.ptr(gx), D, B, D, stream)
@@ -244,7 +251,7 @@ class TransformerFunction(torch.autograd.Function):
 
 
 _HIP_TRANSFORMERS = (AffineTransformer, MoebiusTransformer, VolumePreservingShiftTransformer, NeuralSplineTransformer,
-                     MixedTransformer, SOSPolynomialTransformer)
+                     MixedTransformer, SOSPolynomialTransformer, SymmetrizedMoebiusTransformer)
 
 
 def generic_supported(layer):
@@ -340,6 +347,8 @@ def _differentiable_inverse(tr):
     from .partial import _GatherColumns, _ReplaceColumns
     if type(tr) is MoebiusTransformer:
         return lambda y_tr, theta: TransformerFunction.apply(tr, y_tr, -theta)
+    if type(tr) is SymmetrizedMoebiusTransformer:            # its inverse op has an autograd registration of its own
+        return lambda y_tr, theta: tr.inverse(y_tr.contiguous(), theta.contiguous())
     if _elementwise(tr):
         return lambda y_tr, theta: TransformerInverseFunction.apply(tr, y_tr, theta)
     if type(tr) is MixedTransformer:

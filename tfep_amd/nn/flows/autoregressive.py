@@ -22,7 +22,7 @@ from ..conditioners.made import MADE
 from ..embeddings.mafembed import PeriodicEmbedding
 from ..transformers.affine import AffineTransformer, VolumePreservingShiftTransformer
 from ..transformers.mixed import MixedTransformer, check_float64_members
-from ..transformers.moebius import MoebiusTransformer
+from ..transformers.moebius import MoebiusTransformer, SymmetrizedMoebiusTransformer
 from ..transformers.sos import SOSPolynomialTransformer
 from ..transformers.spline import NeuralSplineTransformer
 from .sequential import _side_stream
@@ -657,7 +657,7 @@ class AutoregressiveFlow(torch.nn.Module):
         tr = self._transformer
         if type(tr) in (AffineTransformer, NeuralSplineTransformer):
             return True
-        if type(tr) is MoebiusTransformer:
+        if type(tr) in (MoebiusTransformer, SymmetrizedMoebiusTransformer):
             # every vector must live inside one degree (e.g. generate_degrees(..., repeats=dimension))
             deg = made._degrees[0]
             deg = deg[deg != -1]
@@ -679,6 +679,8 @@ class AutoregressiveFlow(torch.nn.Module):
                 h['learn_lower'], h['learn_upper'], h['min_bin'], h['min_slope']))
         if type(tr) is MoebiusTransformer:
             return ('moebius', tr)
+        if type(tr) is SymmetrizedMoebiusTransformer:
+            return ('symmoebius', tr)
         if type(tr) is VolumePreservingShiftTransformer:
             return ('shift', tr)
         return ('affine', tr)
@@ -1729,6 +1731,8 @@ class AutoregressiveFlow(torch.nn.Module):
                     elif kind == 'moebius':
                         x_d, _ = ops.moebius(y_d, par, sub.dimension, sub.max_radius, sub.unit_sphere, inverse=True,
                                              log_det_J=ldj)
+                    elif kind == 'symmoebius':
+                        x_d, _ = ops.symmetrized_moebius(y_d, par, sub.dimension, sub.max_radius, inverse=True, log_det_J=ldj)
                     elif kind == 'shift':       # (a member of a mixed transformer, no periodic features) log-det 0
                         x_d, _ = ops.volume_preserving_shift(y_d, par, inverse=True)
                     else:

@@ -1,4 +1,4 @@
-"""Moebius transformer (reference ``tfep/nn/transformers/moebius.py:27-190``)."""
+"""Moebius and symmetrized Moebius transformers (reference ``tfep/nn/transformers/moebius.py:27-372``)."""
 import torch
 
 from ... import ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.tfep.*)
@@ -37,6 +37,39 @@ class MoebiusTransformer(MAFTransformer):
 
     def get_identity_parameters(self, n_features: int) -> torch.Tensor:
         return torch.zeros(size=(n_features,))
+
+    def get_degrees_out(self, degrees_in: torch.Tensor) -> torch.Tensor:
+        return degrees_in.detach().clone()
+
+
+class SymmetrizedMoebiusTransformer(MAFTransformer):
+    r""":math:`y = \|x\| \frac{f(x; w) + f(x; -w)}{\|f(x; w) + f(x; -w)\|}` on ``dimension``-vectors, :math:`f` the Moebius
+    map of :class:`MoebiusTransformer` on the sphere of radius :math:`\|x\|` (reference moebius.py:193-372).
+
+    Even in ``w``, with a closed-form inverse and log-det (``tfep_amd/csrc/symmoebius.h``); float32 and float64.  A class of
+    its own, not a ``MoebiusTransformer``: none of that transformer's float32-only speed paths apply.  ``w = 0`` is the
+    identity but has zero parameter gradient, so the identity parameters are random numbers of at most ``identity_eps``.
+    """
+
+    def __init__(self, dimension: int, max_radius: float = 0.99, identity_eps: float = 1e-9):
+        super().__init__()
+        self.dimension = dimension
+        self.max_radius = max_radius
+        self.identity_eps = identity_eps
+
+    def forward(self, x, parameters):
+        ops.check_device_tensor(x, 'x', ops._dtype(x))                     # float32, or float64 (the float64 kernels)
+        return tuple(torch.ops.tfep.symmetrized_moebius_forward(x, parameters, int(self.dimension),
+                                                                float(self.max_radius)))         # differentiable
+
+    def inverse(self, y, parameters):
+        ops.check_device_tensor(y, 'y', ops._dtype(y))
+        return tuple(torch.ops.tfep.symmetrized_moebius_inverse(y, parameters, int(self.dimension),
+                                                                float(self.max_radius)))         # differentiable
+
+    def get_identity_parameters(self, n_features: int) -> torch.Tensor:
+        par = torch.rand(n_features)                                        # (one draw: the reference's random stream)
+        return (2 * par - 1) * self.identity_eps
 
     def get_degrees_out(self, degrees_in: torch.Tensor) -> torch.Tensor:
         return degrees_in.detach().clone()

@@ -162,6 +162,20 @@ def moebius(x, parameters, dimension, max_radius=0.99, unit_sphere=False, invers
     return y, ldj
 
 
+def symmetrized_moebius(x, parameters, dimension, max_radius=0.99, inverse=False, log_det_J=None):
+    """SymmetrizedMoebiusTransformer.forward / .inverse (reference moebius.py:481-629).  float64 tensors run on the float64
+    kernels; mixed float32 / float64 arguments are a TypeError."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    B, D = x.shape
+    parameters, ldp = _check_params(parameters, B, D, dtype=dt)
+    y = torch.empty(B, D, dtype=x.dtype, device=x.device)
+    ldj, acc = _ldj_out(log_det_J, B, x, dt)
+    call('tfep_symmetrized_moebius' + _sfx(dt), ptr(x), ldx, ptr(parameters), ldp, int(dimension), float(max_radius),
+         int(bool(inverse)), ptr(y), max(D, 1), ptr(ldj), acc, B, D, stream_of(x))
+    return y, ldj
+
+
 def moebius_split_out(x, parameters, max_radius, cols_padded):
     """Forward map of unit-sphere 2-vectors that also returns y as split-f16 rows ``(y, log_det_J, y_split, y_inv_scale)`` for
     the next masked linear (``tfep_moebius_forward_split_out``)."""

@@ -10,6 +10,8 @@ in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the re
   tfep::sos_forward / sos_backward                                    reference transformers/sos.py:81-265 (SOS_OPS)
   tfep::spline_forward / spline_inverse / spline_backward            reference transformers/spline.py:184-261, 424-564
   tfep::moebius_forward / moebius_inverse / moebius_backward         reference transformers/moebius.py:104-147, 374-478
+  tfep::symmetrized_moebius_forward / _inverse / _backward           reference transformers/moebius.py:193-372, 481-629
+                                                                     (SYMMETRIZED_MOEBIUS_OPS)
   tfep::masked_linear / masked_linear_backward                       reference masked.py:220-302, 351-404
   tfep::fused_output_transformer                                     masked.py:188-208 (last layer) + the transformer
   tfep::tfep_reduce                                                  loss.py:125-140, analysis/estimator.py:73-86
@@ -251,6 +253,55 @@ def _moebius_bwd(ctx, gy, gl):
 moebius_forward.register_autograd(_moebius_bwd, setup_context=_moebius_setup)
 
 
+# ============================================================================= symmetrized Moebius
+
+@custom_op('tfep::symmetrized_moebius_forward', mutates_args=(), device_types=_DEV)
+def symmetrized_moebius_forward(x: Tensor, parameters: Tensor, dimension: int, max_radius: float) -> Tuple[Tensor, Tensor]:
+    return ops.symmetrized_moebius(x, parameters, dimension, max_radius, inverse=False)
+
+
+@custom_op('tfep::symmetrized_moebius_inverse', mutates_args=(), device_types=_DEV)
+def symmetrized_moebius_inverse(y: Tensor, parameters: Tensor, dimension: int, max_radius: float) -> Tuple[Tensor, Tensor]:
+    return ops.symmetrized_moebius(y, parameters, dimension, max_radius, inverse=True)
+
+
+@custom_op('tfep::symmetrized_moebius_backward', mutates_args=(), device_types=_DEV)
+def symmetrized_moebius_backward(x: Tensor, parameters: Tensor, grad_y: Tensor, grad_log_det_J: Tensor, dimension: int,
+                                 max_radius: float, inverse: bool) -> Tuple[Tensor, Tensor]:
+    """VJP of ``symmetrized_moebius_forward`` (``inverse`` False) or ``_inverse`` (True) at its input ``x``; the log-det
+    carries gradient in both directions."""
+    x, parameters, gy, gl = x.contiguous(), parameters.contiguous(), grad_y.contiguous(), grad_log_det_J.contiguous()
+    dt = _vjp_dtype(x, (x, 'x'), (parameters, 'parameters'), (gy, 'grad_y'), (gl, 'grad_log_det_J'))
+    B, D = x.shape
+    if parameters.shape != x.shape or gy.shape != x.shape or gl.shape != (B,):
+        raise ValueError('symmetrized_moebius_backward: parameters and grad_y must have the shape of x, grad_log_det_J (B,)')
+    gx = torch.empty_like(x)
+    gp = torch.empty_like(parameters)
+    _lib.call('tfep_symmetrized_moebius_backward' + ops._sfx(dt), _lib.ptr(x), D, _lib.ptr(parameters), D, int(dimension),
+              float(max_radius), int(bool(inverse)), _lib.ptr(gy), D, _lib.ptr(gl), _lib.ptr(gp), D, _lib.ptr(gx), D, B, D,
+              _lib.stream_of(x))
+    return gx, gp
+
+
+symmetrized_moebius_forward.register_fake(lambda x, parameters, *a: _pair_like(x))
+symmetrized_moebius_inverse.register_fake(lambda y, parameters, *a: _pair_like(y))
+symmetrized_moebius_backward.register_fake(lambda x, parameters, gy, gl, *a: (x.new_empty(x.shape),
+                                                                              parameters.new_empty(parameters.shape)))
+
+
+def _symmoebius_bwd(inverse):
+    def bwd(ctx, gy, gl):
+        x, p = ctx.saved_tensors
+        gy, gl = _vjp_inputs(ctx, (gy, gl))
+        gx, gp = torch.ops.tfep.symmetrized_moebius_backward(x, p, gy, gl, *ctx.cfg, inverse)
+        return gx, gp, None, None
+    return bwd
+
+
+symmetrized_moebius_forward.register_autograd(_symmoebius_bwd(False), setup_context=_moebius_setup)
+symmetrized_moebius_inverse.register_autograd(_symmoebius_bwd(True), setup_context=_moebius_setup)
+
+
 # ============================================================================= masked linear
 
 @custom_op('tfep::masked_linear', mutates_args=(), device_types=_DEV)
@@ -436,3 +487,4 @@ OPS = ('affine_forward', 'affine_inverse', 'affine_backward', 'spline_forward', 
        'fused_output_transformer', 'fused_output_transformer_', 'tfep_reduce')
 # (a tuple of their own: OPS is the list the existing op tests iterate over)
 SOS_OPS = ('sos_forward', 'sos_backward')
+SYMMETRIZED_MOEBIUS_OPS = ('symmetrized_moebius_forward', 'symmetrized_moebius_inverse', 'symmetrized_moebius_backward')

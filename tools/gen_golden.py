@@ -1388,6 +1388,94 @@ def gen_sos():
     np.savez_compressed(os.path.join(OUT, 'sos.npz'), **out)
 
 
+def symmoebius_flows():
+    """The flow configurations of symmoebius.npz: name -> (constructor(dtype), n_features)."""
+    from tfep.nn.conditioners.made import generate_degrees as gd
+    from tfep.nn.transformers.moebius import SymmetrizedMoebiusTransformer
+    return {
+        'flow': (lambda dt: SequentialFlow(
+            MAF(degrees_in=gd(12, 'ascending', repeats=3), transformer=SymmetrizedMoebiusTransformer(3),
+                initialize_identity=False),
+            MAF(degrees_in=gd(12, 'descending', repeats=3), transformer=SymmetrizedMoebiusTransformer(3),
+                initialize_identity=False)), 12),
+        'mixed': (lambda dt: SequentialFlow(
+            MAF(degrees_in=gd(10, 'ascending'),
+                transformer=MixedTransformer(
+                    transformers=[SymmetrizedMoebiusTransformer(2),
+                                  NeuralSplineTransformer(x0=torch.full((6,), -4.0).to(dt), xf=torch.full((6,), 4.0).to(dt),
+                                                          n_bins=8)],
+                    indices=[[0, 1, 2, 3], [4, 5, 6, 7, 8, 9]]),
+                initialize_identity=False)), 10),
+    }
+
+
+def gen_symmoebius():
+    """Reference SymmetrizedMoebiusTransformer (moebius.py:193-372, :481-629), float64 and float32 on float32-rounded inputs.
+    Transformer level: y, log-det, the inverse applied to an independent input, and the gradients of
+    sum(c y^2 + e y) + sum(g log_det_J) with respect to x and w in both directions; a seeded get_identity_parameters draw;
+    the flows of ``symmoebius_flows``: forward, inverse, and BoltzmannKLDivLoss(u(.), log_det_J) with
+    u(y) = sum_f (c_f y_f^2 + d_f y_f) and its gradients, forward and through the inverse."""
+    from tfep.nn.transformers.moebius import SymmetrizedMoebiusTransformer
+    out = {}
+    B, n_vec = 32, 6
+    for dim in (2, 3, 4):
+        for R in (0.99, 0.7):
+            name = f'tr/d{dim}_R{R}'
+            g = gen(200 + 10 * dim + int(R * 10))
+            D = n_vec * dim
+            x, w, yin = 2 * torch.randn(B, D, generator=g), 3 * torch.randn(B, D, generator=g), 2 * torch.randn(B, D, generator=g)
+            c, e, gl = torch.rand(D, generator=g) * 0.3, torch.randn(D, generator=g) * 0.2, torch.randn(B, generator=g)
+            for k, v in (('x', x), ('w', w), ('yin', yin), ('c', c), ('e', e), ('g', gl)):
+                out[f'{name}/{k}'] = npy(v)
+            tr = SymmetrizedMoebiusTransformer(dim, max_radius=R)
+            for tag, dt in (('f64', torch.float64), ('f32', torch.float32)):
+                for sfx, fn, inp in (('', tr.forward, x), ('_inv', tr.inverse, yin)):
+                    xx = inp.to(dt).clone().requires_grad_(True)       # (.to() of the same dtype returns the tensor itself)
+                    ww = w.to(dt).clone().requires_grad_(True)
+                    y, ldj = fn(xx, ww)
+                    ((c.to(dt) * y ** 2 + e.to(dt) * y).sum() + (gl.to(dt) * ldj).sum()).backward()
+                    out[f'{name}/y{sfx}_{tag}'], out[f'{name}/ldj{sfx}_{tag}'] = npy(y), npy(ldj)
+                    out[f'{name}/gx{sfx}_{tag}'], out[f'{name}/gw{sfx}_{tag}'] = npy(xx.grad), npy(ww.grad)
+    torch.manual_seed(7)
+    out['identity/seed7_n12'] = npy(SymmetrizedMoebiusTransformer(3).get_identity_parameters(12))
+
+    def quad(y, c, d):
+        return (c * y ** 2 + d * y).sum(dim=1)
+
+    B = 32
+    for name, (make, D) in symmoebius_flows().items():
+        # (mixed: with seeds 50 .. 52 the reference's own float32 gradient through the inverse is NaN -- in float32 its
+        # sqrt(1 - a_inv^2) reaches 0 at d = 2 -- and could not serve as the float32 yardstick)
+        seed = {'flow': 50, 'mixed': 60}[name]
+        torch.manual_seed(seed)
+        f32 = make(torch.float32)
+        perturb_weight_g(f32, seed + 1)
+        g = gen(seed + 2)
+        x = torch.randn(B, D, generator=g) * 1.5
+        c = torch.rand(D, generator=g) * 0.3
+        d = torch.randn(D, generator=g) * 0.2
+        sd = {k: v.clone() for k, v in f32.state_dict().items()}
+        with f64():
+            m64 = make(torch.float64)
+            m64.load_state_dict(to_double_sd(sd))
+        for tag, m, dt in (('f64', m64, torch.float64), ('f32', f32, torch.float32)):
+            for sfx, fn in (('', m.forward), ('_inv', m.inverse)):
+                m.zero_grad(set_to_none=True)
+                xx = x.to(dt).clone().requires_grad_(True)
+                y, ldj = fn(xx)
+                loss = BoltzmannKLDivLoss()(quad(y, c.to(dt), d.to(dt)), ldj)
+                loss.backward()
+                out[f'{name}/y{sfx}_{tag}'], out[f'{name}/ldj{sfx}_{tag}'] = npy(y), npy(ldj)
+                out[f'{name}/loss{sfx}_{tag}'], out[f'{name}/gx{sfx}_{tag}'] = npy(loss), npy(xx.grad)
+                for k, p in m.named_parameters():
+                    out[f'{name}/grad{sfx}_{tag}/{k}'] = npy(p.grad)
+        out[f'{name}/x'], out[f'{name}/c'], out[f'{name}/d'] = npy(x), npy(c), npy(d)
+        for k, v in sd.items():
+            if not k.endswith('.mask'):
+                out[f'{name}/sd/{k}'] = npy(v)
+    np.savez_compressed(os.path.join(OUT, 'symmoebius.npz'), **out)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
     if len(sys.argv) > 1:
