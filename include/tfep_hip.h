@@ -755,6 +755,67 @@ int tfep_spline_backward_f64(const double* x, int64_t ldx, const double* params,
                              const double* g_log_det_J, double* gparams, tfep_param_layout glayout,
                              double* gx, int64_t ldgx, int B, int D, void* stream);
 
+/*
+ * float64 blocked inverse of a MAF layer: the in-block chain.
+ *
+ * The host walks the degrees of the layer in blocks of consecutive degrees.  Units and inputs of every masked linear are
+ * stored sorted by degree, so a mask row is a prefix [0, cut) of the packed columns.  At the head of a block one
+ * tfep_masked_linear_gemm_f64 per linear l forms the products of the block's rows with the columns [0, k0[l]) -- all of
+ * them final, k0[l] = the block's first column rounded DOWN to a multiple of 16 -- without bias: for a hidden linear
+ * straight into the block's columns of a[l + 1], for the output linear into zout (column = packed row - zout_row0).  One
+ * call of this entry point then walks the n_steps degrees of the block in order.  Per degree:
+ *   parameters   par[f][p] = (has_panel ? zout : 0) + bias + sum_{c in [k0[L], cut)} w[L][row, c] a[L][b, c],
+ *                row = prow0(f) + p -- the P rows of a feature are consecutive in the packed output linear;
+ *   transformer  x[b, col_x(f)] = inverse element of member(f) at y[b, col_x(f)] (affine: parameters shift, log-scale;
+ *                RQ spline: every layout of tfep_spline_desc_f64, domain arrays indexed by the feature's slot f);
+ *                log_det_J[b] += the log-derivatives of the inverse, summed in slot order;
+ *   inputs       a[0][b, pos(f)] = x, or (cos t, sin t) at pos, pos + 1 with t = (x - emb_lower) emb_scale;
+ *   hidden       for l < L, rows r of this degree: a[l + 1][b, r] = elu((has_panel ? a[l + 1][b, r] : 0) + bias[l][r]
+ *                + sum_{c in [k0[l], cut)} w[l][r, c] a[l][b, c]).
+ * Each product is counted once: the panel stops at k0, the chain starts there.  Sums run in ascending column order on two
+ * interleaved accumulators, per sample row: results do not depend on the batch a row sits in.  fp64 throughout.
+ *
+ * a[l]: (B, lda[l]) input of linear l, l = 0 .. n_linears - 1 (a[0]: the conditioner input), zero where not yet known.
+ * w[l]: packed weights (rows x ldw[l]), bias[l]: packed bias.  n_old[l] (< 16): columns [k0, k0 + n_old) come from earlier
+ * blocks; n_cols[l]: columns [k0, k0 + n_cols) are kept in LDS (through the end of the block); lds_col0[l]: running sum of
+ * n_cols.  steps: (n_steps, 16) int32: [slot0, slot1, cut of the output rows, then (row0, row1, cut) per hidden linear],
+ * absolute indices.  feats: (n_slots, 8) int32: [col_x, member, P, prow0, pos, periodic, 0, 0], slots sorted by degree.
+ * member_kind: 0 affine, 1 RQ spline (spline[m], its x0 / xf / y0 / yf arrays have one entry per slot).  par_cols: the
+ * largest P; max_feats: the most features of one degree.  LDS: tfep_inverse_chain_f64_lds_bytes(sum n_cols, par_cols,
+ * max_feats) <= 160 KiB, else TFEP_ERR_INVALID_ARGUMENT.  64 sample rows per workgroup.  B = 0 is a no-op.
+ */
+#define TFEP_INVERSE_F64_MAX_LINEARS 5
+#define TFEP_INVERSE_F64_MAX_MEMBERS 4
+typedef struct tfep_inverse_chain_f64_desc {
+    int32_t B, n_linears, n_steps, n_members;
+    const double* y;
+    int64_t ldy;
+    double* x;
+    int64_t ldx;
+    double* log_det_J;
+    double* a[TFEP_INVERSE_F64_MAX_LINEARS];
+    int64_t lda[TFEP_INVERSE_F64_MAX_LINEARS];
+    const double* w[TFEP_INVERSE_F64_MAX_LINEARS];
+    int64_t ldw[TFEP_INVERSE_F64_MAX_LINEARS];
+    const double* bias[TFEP_INVERSE_F64_MAX_LINEARS];
+    const double* zout;
+    int64_t ldzout;
+    int32_t zout_row0;
+    int32_t par_cols, max_feats;
+    int32_t k0[TFEP_INVERSE_F64_MAX_LINEARS];
+    int32_t n_old[TFEP_INVERSE_F64_MAX_LINEARS];
+    int32_t n_cols[TFEP_INVERSE_F64_MAX_LINEARS];
+    int32_t lds_col0[TFEP_INVERSE_F64_MAX_LINEARS];
+    int32_t has_panel[TFEP_INVERSE_F64_MAX_LINEARS];
+    const int32_t* steps;
+    const int32_t* feats;
+    int32_t member_kind[TFEP_INVERSE_F64_MAX_MEMBERS];
+    tfep_spline_desc_f64 spline[TFEP_INVERSE_F64_MAX_MEMBERS];
+    double emb_lower, emb_scale;
+} tfep_inverse_chain_f64_desc;
+int64_t tfep_inverse_chain_f64_lds_bytes(int n_cols_total, int par_cols, int max_feats);
+int tfep_inverse_chain_f64(const tfep_inverse_chain_f64_desc* desc, void* stream);
+
 int tfep_periodic_embedding_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
                                 const int32_t* nonperiodic_indices, int n_nonperiodic,
                                 double lower, double upper, double* out, int64_t ldo, int B, void* stream);

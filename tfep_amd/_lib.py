@@ -80,6 +80,16 @@ class SplineDescF64(Structure):
                 ('min_bin_size', c_double), ('min_slope', c_double)]
 
 
+class InverseChainF64Desc(Structure):
+    _fields_ = [('B', c_int32), ('n_linears', c_int32), ('n_steps', c_int32), ('n_members', c_int32),
+                ('y', c_void_p), ('ldy', c_int64), ('x', c_void_p), ('ldx', c_int64), ('log_det_J', c_void_p),
+                ('a', c_void_p * 5), ('lda', c_int64 * 5), ('w', c_void_p * 5), ('ldw', c_int64 * 5), ('bias', c_void_p * 5),
+                ('zout', c_void_p), ('ldzout', c_int64), ('zout_row0', c_int32), ('par_cols', c_int32), ('max_feats', c_int32),
+                ('k0', c_int32 * 5), ('n_old', c_int32 * 5), ('n_cols', c_int32 * 5), ('lds_col0', c_int32 * 5),
+                ('has_panel', c_int32 * 5), ('steps', c_void_p), ('feats', c_void_p), ('member_kind', c_int32 * 4),
+                ('spline', SplineDescF64 * 4), ('emb_lower', c_double), ('emb_scale', c_double)]
+
+
 class EgnnLayerParams(Structure):
     _fields_ = [('F', c_int32), ('G', c_int32)] + [(k, c_void_p) for k in (
         'dist_means', 'dist_log_gammas', 'msg0_w', 'msg0_b', 'msg2_w', 'msg2_b', 'att_w', 'att_b', 'ux0_w', 'ux0_b',
@@ -254,6 +264,8 @@ _SIGNATURES = {
                                         _P, c_int, c_int, c_int, _P]),
     'tfep_spline_backward_f64': (c_int, [_P, c_int64, _P, ParamLayout, POINTER(SplineDescF64), _P, c_int64, _P, _P,
                                          ParamLayout, _P, c_int64, c_int, c_int, _P]),
+    'tfep_inverse_chain_f64_lds_bytes': (c_int64, [c_int, c_int, c_int]),
+    'tfep_inverse_chain_f64': (c_int, [POINTER(InverseChainF64Desc), _P]),
     'tfep_periodic_embedding_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double,
                                             _P, c_int64, c_int, _P]),
     'tfep_periodic_embedding_backward_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double, _P, c_int64,

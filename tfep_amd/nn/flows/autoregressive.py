@@ -452,10 +452,12 @@ class AutoregressiveFlow(torch.nn.Module):
     @property
     def is_float64(self):
         """True for a float64 layer (``.double()``, or built under ``torch.set_default_dtype(torch.float64)``): the dtype of
-        the conditioner's parameters.  A float64 layer always takes the generic path -- conditioner (three fp64-MFMA GEMMs
-        for a MADE), float64 transformer kernel, column scatter -- and its inverse the reference's pass per degree; the
-        float32 switches (``fused``, ``split_gemm``, ``layer_kernel``, ``blocked_inverse``, the ``TFEP_*`` variables)
-        do not apply to it."""
+        the conditioner's parameters.  The forward of a float64 layer always takes the generic path -- conditioner (three
+        fp64-MFMA GEMMs for a MADE), float64 transformer kernel, column scatter.  Its inverse is the float64 blocked forward
+        substitution (``_inverse_blocked_f64``: about one forward in flops) where the layer qualifies (``_blocked_f64_ok``)
+        and ``blocked_inverse`` is true, else the reference's pass per degree; ``last_inverse_route`` says which one ran.
+        The other float32 switches (``fused``, ``split_gemm``, ``layer_kernel``, the ``TFEP_*`` variables) do not apply to
+        it."""
         f64 = self._dev.get('float64')               # (the cache goes with every .to() / .double() / load_state_dict)
         if f64 is None:
             f64 = next((p.dtype == torch.float64 for p in self._conditioner.parameters() if p.is_floating_point()), False)
@@ -617,7 +619,15 @@ class AutoregressiveFlow(torch.nn.Module):
     #: 16-row waves, which cfg4-i's short chains do faster than two shards (70 against 81 ms).
     inverse_shard_rows = None
 
+    #: Which algorithm the last ``inverse`` call of this layer ran: ``'blocked'`` (float32 blocked forward substitution),
+    #: ``'blocked_f64'`` (its float64 counterpart, ``_inverse_blocked_f64``) or ``'per_degree'`` (one conditioner pass per degree).
+    last_inverse_route = None
+
     def _inverse_values(self, y: torch.Tensor):
+        if self.is_float64 and self._blocked_f64_ok():
+            self.last_inverse_route = 'blocked_f64'
+            return self._inverse_blocked_f64(y)
+        self.last_inverse_route = 'blocked' if self._blocked_ok() else 'per_degree'
         if self._blocked_ok():
             shard = self.inverse_shard_rows
             if os.environ.get('TFEP_INV_SHARD_ROWS') is not None:
@@ -1739,6 +1749,230 @@ class AutoregressiveFlow(torch.nn.Module):
                         x_d, _ = ops.affine(y_d, par, inverse=True, log_det_J=ldj)
                     ops.scatter_columns(x_d, st['cols'], x)
                     self._scatter_inputs(xpad, x_d, st['inputs'])
+        return x, ldj
+
+    # ------------------------------------------------------------------ float64 blocked inverse
+    #: Degrees per block of the float64 blocked inverse; halved until the block's state fits the chain kernel's LDS
+    #: (``_blocked_f64.fit_block``).  Larger blocks mean fewer, fuller panel GEMMs; 16 is what fits a cfg2-sized layer.
+    inverse_block_f64 = 16
+
+    def _blocked_f64_ok(self):
+        """Does this float64 layer take the float64 blocked inverse?  A MADE conditioner (2 .. 5 masked linears, masks that
+        a degree assignment reproduces, no embedding or a PeriodicEmbedding, no ``_conditioner_indices``) and an affine or
+        RQ-spline transformer, or a mixed transformer of up to four such members; features that no step transforms pass
+        through.  Everything else keeps the pass per degree."""
+        made = self._conditioner
+        if not self.blocked_inverse or not self.is_float64 or not isinstance(made, MADE) or len(self._conditioner_indices) > 0:
+            return False
+        if not made._degrees_ok:
+            return False
+        emb = getattr(made, 'embedding', None)
+        if emb is not None and type(emb) is not PeriodicEmbedding:
+            return False
+        tr = self._transformer
+        members = tr._transformers if type(tr) is MixedTransformer else [tr]
+        if not all(type(t) in (AffineTransformer, NeuralSplineTransformer) for t in members):
+            return False
+        return self._blocked_f64_host_plan() is not None
+
+    def _blocked_f64_host_plan(self):
+        """The host plan of the float64 blocked inverse (``flows/_blocked_f64.py``), or None when the layer's degrees do not
+        fit it; cached per block size and mask version."""
+        made = self._conditioner
+        key = ('blocked_f64_host', int(self.inverse_block_f64), made._mask_versions())
+        if key not in self._dev:
+            self._dev[key] = self._make_blocked_f64_host_plan(max(1, int(self.inverse_block_f64)))
+        return self._dev[key]
+
+    def _make_blocked_f64_host_plan(self, G):
+        import numpy as np
+        from . import _blocked_f64 as bf
+        made, tr = self._conditioner, self._transformer
+        lins = made._linears()
+        if not (2 <= len(lins) <= bf.MAX_LINEARS):
+            return None
+        dev0 = self._inverse_masks.device
+        D = self._inverse_masks.shape[1]
+        deg_x = torch.full((D,), -1, dtype=torch.long)
+        for d_, m_ in enumerate(self._inverse_masks.cpu()):
+            deg_x[m_] = d_
+        tr_idx = (self._transformer_indices.cpu() if self.has_fixed_indices else torch.arange(D)).long()
+        deg_tr = deg_x[tr_idx]
+        n_tr = len(tr_idx)
+        if n_tr == 0 or bool((deg_tr < 0).any()):
+            return None
+        emb = getattr(made, 'embedding', None)
+        deg_in = deg_x if emb is None else emb.get_degrees_out(deg_x.to(dev0)).cpu().long()
+        degs = [d.cpu().long() for d in made._degrees]
+        # the conditioner must be the MADE of exactly these degrees: inputs as the steps of the inverse say, outputs as the
+        # transformer lays its parameters out
+        if len(degs) != len(lins) + 1 or not torch.equal(degs[0], deg_in):
+            return None
+        if not torch.equal(degs[-1], tr.get_degrees_out(deg_tr.to(dev0)).cpu().long()):
+            return None
+        if type(tr) is MixedTransformer:
+            members = list(tr._transformers)
+            inds = [ind.cpu().long() for ind in tr._indices]
+            member_of = np.full(n_tr, -1, dtype=np.int64)
+            local_of = np.zeros(n_tr, dtype=np.int64)
+            for g, ind in enumerate(inds):
+                member_of[ind.numpy()] = g
+                local_of[ind.numpy()] = np.arange(len(ind))
+            if len(members) > bf.MAX_MEMBERS or (member_of < 0).any() or sum(len(i) for i in inds) != n_tr:
+                return None
+            offsets, counts = tr.host_splits(), [len(i) for i in inds]
+        else:
+            members, member_of, local_of, offsets, counts = [tr], None, np.arange(n_tr), None, None
+        kinds = [0 if type(t) is AffineTransformer else 1 for t in members]
+        P_of = [2 if k == 0 else t.n_parameters_per_feature for k, t in zip(kinds, members)]
+        mem = np.zeros(n_tr, dtype=np.int64) if member_of is None else member_of
+        params_of = np.asarray(P_of, dtype=np.int64)[mem]
+        if int(params_of.sum()) != lins[-1].out_features:
+            return None
+        slot_order, base, row_of_out = bf.feature_slots(deg_tr.numpy(), params_of, member_of, local_of, offsets, counts)
+        order0, pos0 = bf.stable_order(deg_in.numpy())
+        hidden = [bf.stable_order(d.numpy()) for d in degs[1:-1]]
+        deg_cols = [deg_in.numpy()[order0]] + [d.numpy()[o] for d, (o, _) in zip(degs[1:-1], hidden)]
+        plan = bf.fit_block(deg_cols, deg_tr.numpy()[slot_order], params_of[slot_order], G)
+        if plan is None:
+            return None
+        first, periodic, limits = self._input_columns()
+
+        def input_pos(c):
+            p = int(pos0[first[c]])
+            if periodic[c] and int(pos0[first[c] + 1]) != p + 1:
+                raise RuntimeError('the (cos, sin) pair of a periodic feature is not adjacent in degree order')
+            return p
+        feats = np.zeros((n_tr, bf.FEAT_INTS), dtype=np.int32)
+        for s, t in enumerate(slot_order):
+            c = int(tr_idx[t])
+            feats[s, :6] = (c, mem[t], params_of[t], base[s], input_pos(c), int(periodic[c]))
+        fixed = [int(c) for c in self._fixed_indices.cpu().tolist()]
+        plan.update(feats=feats, slot_member=mem[slot_order], slot_local=np.asarray(local_of)[slot_order], members=members,
+                    kinds=kinds, row_of_out=row_of_out, pos0=pos0, hidden_pos=[p for _, p in hidden], limits=limits,
+                    fixed_plain=[(c, input_pos(c)) for c in fixed if not periodic[c]],
+                    fixed_periodic=[(c, input_pos(c)) for c in fixed if periodic[c]])
+        return plan
+
+    def _blocked_f64_device_plan(self, device, hp):
+        """Device tables, packed-weight buffers and one prefilled chain descriptor per block (cached with the host plan)."""
+        key = str(device)
+        dp = hp.setdefault('device', {}).get(key)
+        if dp is not None:
+            return dp
+        import numpy as np
+        made = self._conditioner
+        lins = made._linears()
+        L = len(lins) - 1
+        i32 = dict(device=device, dtype=torch.int32)
+        f64 = dict(device=device, dtype=torch.float64)
+        rows = [torch.from_numpy(p.astype(np.int32)).to(device) for p in hp['hidden_pos']] + \
+               [torch.from_numpy(hp['row_of_out'].astype(np.int32)).to(device)]
+        cols = [torch.from_numpy(hp['pos0'].astype(np.int32)).to(device)] + rows[:-1]
+        n_rows = [ops.round_up(lin.out_features, 16) for lin in lins[:-1]] + [lins[-1].out_features]
+        k_pad = [ops.round_up(lin.in_features, 16) for lin in lins]
+        # zeroed once: the weight preparation rewrites every mapped entry and never touches the padding
+        w = [ops.zeros(n_rows[l], k_pad[l], **f64) for l in range(L + 1)]
+        n_slots = len(hp['feats'])
+        dom = torch.zeros(4, n_slots, dtype=torch.float64)
+        dom[1], dom[3] = 1.0, 1.0
+        for g, (t, kind) in enumerate(zip(hp['members'], hp['kinds'])):
+            if kind == 1:
+                sel = torch.from_numpy(np.nonzero(hp['slot_member'] == g)[0])
+                loc = torch.from_numpy(hp['slot_local'][sel.numpy()])
+                for j, a in enumerate((t.x0, t.xf, t._y0, t._yf)):
+                    dom[j, sel] = a.detach().cpu().to(torch.float64)[loc]
+        dom = dom.to(device)
+        steps = torch.from_numpy(np.concatenate([b['steps'] for b in hp['blocks']], axis=0)).to(device)
+        feats = torch.from_numpy(hp['feats']).to(device)
+        lo, hi = hp['limits']
+        descs, step0 = [], 0
+        for b in hp['blocks']:
+            d = _lib.InverseChainF64Desc()
+            d.n_linears, d.n_steps, d.n_members = L + 1, len(b['steps']), len(hp['members'])
+            d.par_cols, d.max_feats, d.zout_row0 = hp['par_cols'], hp['max_feats'], b['out_rows'][0]
+            for l in range(L + 1):
+                d.k0[l], d.n_old[l], d.n_cols[l], d.lds_col0[l] = b['k0'][l], b['n_old'][l], b['n_cols'][l], b['lds_col0'][l]
+                d.has_panel[l] = int(b['k0'][l] > 0)
+                d.w[l], d.ldw[l], d.lda[l] = w[l].data_ptr(), k_pad[l], k_pad[l]
+            d.steps = steps.data_ptr() + step0 * steps.shape[1] * 4
+            d.feats = feats.data_ptr()
+            step0 += len(b['steps'])
+            for g, (t, kind) in enumerate(zip(hp['members'], hp['kinds'])):
+                d.member_kind[g] = kind
+                if kind == 1:
+                    h = t.host()
+                    d.spline[g] = _lib.SplineDescF64(dom[0].data_ptr(), dom[1].data_ptr(), dom[2].data_ptr(), dom[3].data_ptr(),
+                                                     h['n_bins'], int(h['circular']), int(h['identity']), int(h['learn_lower']),
+                                                     int(h['learn_upper']), h['min_bin'], h['min_slope'])
+            d.emb_lower, d.emb_scale = float(lo), 2.0 * math.pi / (float(hi) - float(lo))
+            descs.append(d)
+
+        def idx(pairs, j):
+            return torch.tensor([p[j] for p in pairs], **i32)
+        dp = dict(rows=rows, cols=cols, n_rows=n_rows, k_pad=k_pad, w=w, dom=dom, steps=steps, feats=feats, descs=descs,
+                  fixed_plain=(idx(hp['fixed_plain'], 0), idx(hp['fixed_plain'], 1)),
+                  fixed_periodic=(idx(hp['fixed_periodic'], 0), idx(hp['fixed_periodic'], 1)))
+        hp['device'][key] = dp
+        return dp
+
+    def _inverse_blocked_f64(self, y):
+        """The float64 blocked forward substitution: per block of ``inverse_block_f64`` degrees one fp64-MFMA panel GEMM per
+        masked linear (the block's rows times every column that earlier blocks made final, up to the last multiple of 16)
+        and one launch of the chain kernel (``tfep_inverse_chain_f64``: the remaining columns, ELU, transformer parameters,
+        inverse transformer, log-det, periodic embedding), on weights packed once per call with rows and columns sorted by
+        degree.  About one forward in flops; all in fp64; a row's bits do not depend on its batch."""
+        hp = self._blocked_f64_host_plan()
+        y, ldy = _lib.rows(y, 'y', torch.float64)
+        B, D = y.shape
+        dev = y.device
+        f64 = dict(device=dev, dtype=torch.float64)
+        x = y.clone() if self.has_fixed_indices else torch.empty(B, D, **f64)     # fixed features propagate unchanged
+        ldj = ops.zeros(B, **f64)
+        if B == 0:
+            return x, ldj
+        dp = self._blocked_f64_device_plan(dev, hp)
+        made = self._conditioner
+        made.begin_call()
+        lins = made._linears()
+        L = len(lins) - 1
+        bias = []
+        for l, lin in enumerate(lins):             # packed on every call, like the reference's pre-hook
+            v, g = (lin.weight_v.detach(), lin.weight_g.detach()) if lin.has_weight_norm else (lin._parameters['weight'].detach(), None)
+            ops.masked_weight_prepare_f64(v, g, lin.mask, dp['rows'][l], dp['cols'][l], dp['n_rows'][l], dp['k_pad'][l],
+                                          out=dp['w'][l], clear=False)
+            bias.append(made._pack_bias(lin, dp['rows'][l], dp['n_rows'][l]))
+        a = [ops.zeros(B, dp['k_pad'][l], **f64) for l in range(L + 1)]
+        cols_f, pos_f = dp['fixed_plain']
+        if cols_f.numel():
+            ops.scatter_columns(ops.gather_columns(y, cols_f), pos_f, a[0])
+        cols_f, pos_f = dp['fixed_periodic']
+        if cols_f.numel():
+            lo, hi = hp['limits']
+            t = (ops.gather_columns(y, cols_f) - lo) * (2.0 * math.pi / (hi - lo))
+            ops.scatter_columns(torch.cos(t), pos_f, a[0])
+            ops.scatter_columns(torch.sin(t), pos_f + 1, a[0])
+        ldz = hp['max_out_rows']
+        zout = torch.empty(B, ldz, **f64)
+        stream = _lib.stream_of(y)
+        vp = ctypes.c_void_p
+        for blk, d in zip(hp['blocks'], dp['descs']):
+            for l in range(L + 1):
+                r0, r1 = blk['rows'][l] if l < L else blk['out_rows']
+                k0 = blk['k0'][l]
+                if k0 == 0 or r1 <= r0:
+                    continue
+                # panel: rows [r0, r1) of linear l times the final columns [0, k0); no bias (the chain adds it once)
+                out_ptr, ldo = (a[l + 1].data_ptr() + 8 * r0, dp['k_pad'][l + 1]) if l < L else (zout.data_ptr(), ldz)
+                _lib.call('tfep_masked_linear_gemm_f64', vp(a[l].data_ptr()), dp['k_pad'][l],
+                          vp(dp['w'][l].data_ptr() + 8 * r0 * dp['k_pad'][l]), dp['k_pad'][l], None, None, 0, vp(out_ptr), ldo,
+                          B, r1 - r0, dp['n_rows'][l] - r0, k0, 0, 0, None, 0, stream)
+            d.B = B
+            d.y, d.ldy, d.x, d.ldx, d.log_det_J = y.data_ptr(), ldy, x.data_ptr(), D, ldj.data_ptr()
+            for l in range(L + 1):
+                d.a[l], d.bias[l] = a[l].data_ptr(), bias[l].data_ptr()
+            d.zout, d.ldzout = zout.data_ptr(), ldz
+            _lib.call('tfep_inverse_chain_f64', ctypes.byref(d), stream)
         return x, ldj
 
     def get_transformer_parameters(self, x: torch.Tensor) -> torch.Tensor:
