@@ -264,6 +264,15 @@ int tfep_symmetrized_moebius(const float* x, int64_t ldx, const float* params, i
                              int inverse, float* y, int64_t ldy, float* log_det_J, int accumulate, int B, int D,
                              void* stream);
 
+/* Quaternion product transformer (quatprod.py): D = n_quaternions * 4, a quaternion is 4 contiguous features with the
+ * scalar LAST (x, y, z, w), Hamilton product, identity (0, 0, 0, 1):
+ *   inverse = 0: y = (p / |p|) (x) x,        inverse = 1: y = conj(p / |p|) (x) x.
+ * Volume preserving: log_det_J (B, or NULL) is set to zero, or left untouched with accumulate = 1.  p = 0 gives NaN, as
+ * in the reference (0 / 0); nothing special-cases it.  16-byte loads and stores on rows that start on a 16-byte boundary,
+ * element by element otherwise (csrc/quatprod.h).  float I/O computes in fp64. */
+int tfep_quaternion_product(const float* x, int64_t ldx, const float* params, int64_t ldp, int inverse, float* y,
+                            int64_t ldy, float* log_det_J, int accumulate, int B, int D, void* stream);
+
 /* PeriodicEmbedding.forward (embeddings/mafembed.py:112-145):
  * out = [x[:, nonperiodic]..., cos t0, sin t0, cos t1, sin t1, ...], t = (x - lower) * 2pi/(upper-lower). */
 int tfep_periodic_embedding(const float* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
@@ -622,6 +631,12 @@ int tfep_moebius_backward(const float* x, int64_t ldx, const float* params, int6
 int tfep_symmetrized_moebius_backward(const float* x, int64_t ldx, const float* params, int64_t ldp, int dimension,
                                       double max_radius, int inverse, const float* gy, int64_t ldgy, const float* g_log_det_J,
                                       float* gparams, int64_t ldgp, float* gx, int64_t ldgx, int B, int D, void* stream);
+/* VJP of the quaternion product map in the direction `inverse` (x = the input of that direction): gx (B, D) is the
+ * transposed orthogonal map applied to gy, gparams (B, D) the cotangent of the RAW parameters, through the normalisation:
+ * (g - q (q . g)) / |p| with q = p / |p|.  The log-det is the constant zero, so it has no cotangent argument. */
+int tfep_quaternion_product_backward(const float* x, int64_t ldx, const float* params, int64_t ldp, int inverse,
+                                     const float* gy, int64_t ldgy, float* gparams, int64_t ldgp, float* gx, int64_t ldgx,
+                                     int B, int D, void* stream);
 /* dst[b, c] = src[b, c] for a (B, C) block with row strides (VJP of the volume-preserving shift,
  * affine.py:366-411: gparams = gx = gy; and sub-blocks of MixedTransformer parameters). */
 int tfep_copy_2d(const float* src, int64_t lds, float* dst, int64_t ldd, int B, int C, void* stream);
@@ -722,6 +737,12 @@ int tfep_symmetrized_moebius_backward_f64(const double* x, int64_t ldx, const do
                                           double max_radius, int inverse, const double* gy, int64_t ldgy,
                                           const double* g_log_det_J, double* gparams, int64_t ldgp, double* gx, int64_t ldgx,
                                           int B, int D, void* stream);
+/* float64 I/O, IEEE division and square root */
+int tfep_quaternion_product_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int inverse, double* y,
+                                int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream);
+int tfep_quaternion_product_backward_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int inverse,
+                                         const double* gy, int64_t ldgy, double* gparams, int64_t ldgp, double* gx,
+                                         int64_t ldgx, int B, int D, void* stream);
 /* periodic wrap with Python `%` semantics in fp64: y = (x + sign b) % (upper - lower) + lower on the periodic features. */
 int tfep_volume_preserving_shift_f64(const double* x, int64_t ldx, const double* shift, int64_t ldp,
                                      const int32_t* periodic_mask, double lower, double upper, int sign,

@@ -161,6 +161,12 @@ _SIGNATURES = {
                                              c_int, _P]),
     'tfep_symmetrized_moebius_backward_f64': (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, _P,
                                                       c_int64, _P, c_int64, c_int, c_int, _P]),
+    'tfep_quaternion_product': (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+    'tfep_quaternion_product_backward': (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int64, _P, c_int64,
+                                                 c_int, c_int, _P]),
+    'tfep_quaternion_product_f64': (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+    'tfep_quaternion_product_backward_f64': (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int64, _P, c_int64,
+                                                     c_int, c_int, _P]),
     'tfep_moebius_forward_split_out': (c_int, [_P, c_int64, _P, c_int64, c_float, _P, c_int64, _P, c_int, _P, c_int64, _P,
                                                c_int, c_int, _P]),
     'tfep_periodic_embedding': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_float, c_float,

@@ -11,6 +11,7 @@
 #include "spline.h"
 #include "fp64_fast.h"
 #include "symmoebius.h"
+#include "quatprod.h"
 #include "embedding.h"
 
 namespace tfep {
@@ -796,6 +797,37 @@ __global__ void __launch_bounds__(256) symmoebius_backward_kernel(const T* __res
     }
 }
 
+// ---------------------------------------------------------------- quaternion product VJP (quatprod.py; quatprod.h)
+// Reverse mode through quatprod_element, forward or inverse direction; one lane per quaternion.  The log-det is the
+// constant zero: its cotangent takes no part.
+template <typename T, bool INVERSE>
+__global__ void __launch_bounds__(256) quatprod_backward_kernel(const T* __restrict__ x, int64_t ldx,
+                                                                const T* __restrict__ params, int64_t ldp,
+                                                                const T* __restrict__ gy, int64_t ldgy,
+                                                                T* __restrict__ gparams, int64_t ldgp, T* __restrict__ gx,
+                                                                int64_t ldgx, int B, int D) {
+    const int b = blockIdx.x * ROWS_PER_BLOCK_B + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const int nq = D / 4;
+    const T* xr = x + (int64_t)b * ldx;
+    const T* pr = params + (int64_t)b * ldp;
+    const T* gr = gy + (int64_t)b * ldgy;
+    T* gpr = gparams + (int64_t)b * ldgp;
+    T* gxr = gx + (int64_t)b * ldgx;
+    const bool px = quat_aligned<T>(xr), pp = quat_aligned<T>(pr), pg = quat_aligned<T>(gr), pgp = quat_aligned<T>(gpr),
+               pgx = quat_aligned<T>(gxr);                                                        // wave uniform
+    for (int q = lane; q < nq; q += 64) {
+        double xv[4], pv[4], gv[4], gxv[4], gpv[4];
+        quat_load(xr, q, px, xv);
+        quat_load(pr, q, pp, pv);
+        quat_load(gr, q, pg, gv);
+        quatprod_vjp_element<T, INVERSE>(xv, pv, gv, gxv, gpv);
+        quat_store(gpr, q, pgp, gpv);
+        quat_store(gxr, q, pgx, gxv);
+    }
+}
+
 // dst[b, c] = src[b, c]
 __global__ void __launch_bounds__(256) copy_2d_kernel(const float* __restrict__ src, int64_t lds,
                                                       float* __restrict__ dst, int64_t ldd, int B, int C) {
@@ -896,6 +928,22 @@ static int launch_symmoebius_backward(const char* who, const T* x, int64_t ldx, 
                                                              ldgp, gx, ldgx, B, D, s)
                    : launch_symmoebius_backward_dir<T, false>(x, ldx, params, ldp, dimension, max_radius, gy, ldgy, gl, gparams,
                                                               ldgp, gx, ldgx, B, D, s);
+}
+
+template <typename T>
+static int launch_quatprod_backward(const char* who, const T* x, int64_t ldx, const T* params, int64_t ldp, int inverse,
+                                    const T* gy, int64_t ldgy, T* gparams, int64_t ldgp, T* gx, int64_t ldgx, int B, int D,
+                                    void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "%s: negative size", who);
+    TFEP_REQUIRE(D % 4 == 0, "%s: n_features=%d is not a multiple of 4 (quaternions)", who, D);
+    TFEP_REQUIRE(inverse == 0 || inverse == 1, "%s: inverse must be 0 or 1", who);
+    if (B == 0 || D == 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && gy && gparams && gx, "%s: NULL pointer", who);
+    TFEP_REQUIRE(ldx >= D && ldp >= D && ldgy >= D && ldgp >= D && ldgx >= D, "%s: a row stride is shorter than n_features=%d",
+                 who, D);
+    auto kernel = inverse ? quatprod_backward_kernel<T, true> : quatprod_backward_kernel<T, false>;
+    kernel<<<row_blocks_b(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, ldp, gy, ldgy, gparams, ldgp, gx, ldgx, B, D);
+    return check_launch("quatprod_backward_kernel");
 }
 
 }  // namespace tfep
@@ -1002,6 +1050,20 @@ int tfep_symmetrized_moebius_backward_f64(const double* x, int64_t ldx, const do
                                           int B, int D, void* stream) {
     return launch_symmoebius_backward("symmetrized_moebius_backward_f64", x, ldx, params, ldp, dimension, max_radius, inverse,
                                       gy, ldgy, g_log_det_J, gparams, ldgp, gx, ldgx, B, D, stream);
+}
+
+int tfep_quaternion_product_backward(const float* x, int64_t ldx, const float* params, int64_t ldp, int inverse,
+                                     const float* gy, int64_t ldgy, float* gparams, int64_t ldgp, float* gx, int64_t ldgx,
+                                     int B, int D, void* stream) {
+    return launch_quatprod_backward("quaternion_product_backward", x, ldx, params, ldp, inverse, gy, ldgy, gparams, ldgp, gx,
+                                    ldgx, B, D, stream);
+}
+
+int tfep_quaternion_product_backward_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int inverse,
+                                         const double* gy, int64_t ldgy, double* gparams, int64_t ldgp, double* gx,
+                                         int64_t ldgx, int B, int D, void* stream) {
+    return launch_quatprod_backward("quaternion_product_backward_f64", x, ldx, params, ldp, inverse, gy, ldgy, gparams, ldgp,
+                                    gx, ldgx, B, D, stream);
 }
 
 int tfep_copy_2d(const float* src, int64_t lds, float* dst, int64_t ldd, int B, int C, void* stream) {

@@ -3,13 +3,14 @@
 // per-sample log|det J| reduction: one wavefront owns one sample (row), its 64 lanes walk the
 // features with unit stride (coalesced 256-B segments per parameter row) and the log-derivative
 // is summed in fp64 with a wave butterfly -- no atomics, bit-reproducible.
-// Affine, volume-preserving shift, SOS, symmetrized Moebius, periodic embedding and column gather / scatter are templates on the element
+// Affine, volume-preserving shift, SOS, symmetrized Moebius, quaternion product, periodic embedding and column gather / scatter are templates on the element
 // type: the float instantiation serves the float32 entry points, the double one their _f64 twins.  (The float64 RQ spline
 // has numerics of its own: spline_f64.hip.)
 #include "common.h"
 #include "spline.h"
 #include "moebius.h"
 #include "symmoebius.h"
+#include "quatprod.h"
 #include "sos.h"
 #include "embedding.h"
 
@@ -248,6 +249,31 @@ __global__ void __launch_bounds__(256) symmoebius_kernel(const T* __restrict__ x
     if (ldj) store_ldj(ldj, b, acc, accumulate);
 }
 
+// ---------------------------------------------------------------- quaternion product (quatprod.py; quatprod.h)
+// One lane per quaternion, one wave per row like the others.  The map preserves volume: the log-det written is zero, and
+// an accumulated log-det is left as it is.
+template <typename T, bool INVERSE>
+__global__ void __launch_bounds__(256) quatprod_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ params,
+                                                       int64_t ldp, T* __restrict__ y, int64_t ldy, T* __restrict__ ldj,
+                                                       int accumulate, int B, int D) {
+    const int b = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const int nq = D / 4;
+    const T* xr = x + (int64_t)b * ldx;
+    const T* pr = params + (int64_t)b * ldp;
+    T* yr = y + (int64_t)b * ldy;
+    const bool px = quat_aligned<T>(xr), pp = quat_aligned<T>(pr), py = quat_aligned<T>(yr);      // wave uniform
+    for (int q = lane; q < nq; q += 64) {
+        double xv[4], pv[4], yv[4];
+        quat_load(xr, q, px, xv);
+        quat_load(pr, q, pp, pv);
+        quatprod_element<T, INVERSE>(xv, pv, yv);
+        quat_store(yr, q, py, yv);
+    }
+    if (ldj && !accumulate && lane == 0) ldj[b] = (T)0;
+}
+
 // ---------------------------------------------------------------- SOS polynomial (sos.py:198-265; sos.h)
 // K runtime; the log of the sum-of-squares derivative per element, summed in fp64 with the wave butterfly like the others.
 template <typename T>
@@ -374,6 +400,20 @@ static int launch_symmoebius(const char* who, const T* x, int64_t ldx, const T* 
                                                     (hipStream_t)stream)
                    : launch_symmoebius_dir<T, false>(x, ldx, params, ldp, dimension, max_radius, y, ldy, ldj, accumulate, B, D,
                                                      (hipStream_t)stream);
+}
+
+template <typename T>
+static int launch_quatprod(const char* who, const T* x, int64_t ldx, const T* params, int64_t ldp, int inverse, T* y,
+                           int64_t ldy, T* ldj, int accumulate, int B, int D, void* stream) {
+    TFEP_REQUIRE(B >= 0 && D >= 0, "%s: negative size", who);
+    TFEP_REQUIRE(D % 4 == 0, "%s: n_features=%d is not a multiple of 4 (quaternions)", who, D);
+    TFEP_REQUIRE(inverse == 0 || inverse == 1, "%s: inverse must be 0 or 1", who);
+    if (B == 0) return TFEP_OK;
+    TFEP_REQUIRE(D == 0 || (x && params && y), "%s: x/params/y must be non-NULL", who);
+    TFEP_REQUIRE(ldx >= D && ldp >= D && ldy >= D, "%s: a row stride is shorter than n_features=%d", who, D);
+    auto kernel = inverse ? quatprod_kernel<T, true> : quatprod_kernel<T, false>;
+    kernel<<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, ldp, y, ldy, ldj, accumulate, B, D);
+    return check_launch("quatprod_kernel");
 }
 
 template <typename T>
@@ -541,6 +581,17 @@ int tfep_symmetrized_moebius_f64(const double* x, int64_t ldx, const double* par
                                  int B, int D, void* stream) {
     return launch_symmoebius("symmetrized_moebius_f64", x, ldx, params, ldp, dimension, max_radius, inverse, y, ldy,
                              log_det_J, accumulate, B, D, stream);
+}
+
+int tfep_quaternion_product(const float* x, int64_t ldx, const float* params, int64_t ldp, int inverse, float* y,
+                            int64_t ldy, float* log_det_J, int accumulate, int B, int D, void* stream) {
+    return launch_quatprod("quaternion_product", x, ldx, params, ldp, inverse, y, ldy, log_det_J, accumulate, B, D, stream);
+}
+
+int tfep_quaternion_product_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int inverse, double* y,
+                                int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream) {
+    return launch_quatprod("quaternion_product_f64", x, ldx, params, ldp, inverse, y, ldy, log_det_J, accumulate, B, D,
+                           stream);
 }
 
 int tfep_moebius_forward_split_out(const float* x, int64_t ldx, const float* params, int64_t ldp, float max_radius, float* y, int64_t ldy,

@@ -29,6 +29,7 @@ from ..embeddings.mafembed import MAFEmbedding, PeriodicEmbedding
 from ..transformers.affine import AffineTransformer, VolumePreservingShiftTransformer
 from ..transformers.mixed import MixedTransformer
 from ..transformers.moebius import MoebiusTransformer, SymmetrizedMoebiusTransformer
+from ..transformers.quatprod import QuaternionProductTransformer
 from ..transformers.sos import SOSPolynomialTransformer
 from ..transformers.spline import NeuralSplineTransformer
 
@@ -63,7 +64,7 @@ def _embedding_params(layer):
 
 def _transformer_supported(tr):
     if type(tr) in (AffineTransformer, MoebiusTransformer, VolumePreservingShiftTransformer, SOSPolynomialTransformer,
-                    SymmetrizedMoebiusTransformer):
+                    SymmetrizedMoebiusTransformer, QuaternionProductTransformer):
         return True
     if type(tr) is NeuralSplineTransformer:
         return True
@@ -114,6 +115,9 @@ def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, 
         elif type(tr) is SymmetrizedMoebiusTransformer:
             _lib.call('tfep_symmetrized_moebius_backward_f64', _lib.ptr(x), D, th, ld_theta, int(tr.dimension),
                       float(tr.max_radius), 0, _lib.ptr(gy), D, _lib.ptr(gl), gth, ld_theta, _lib.ptr(gx), D, B, D, stream)
+        elif type(tr) is QuaternionProductTransformer:      # (log-det 0: gl takes no part)
+            _lib.call('tfep_quaternion_product_backward_f64', _lib.ptr(x), D, th, ld_theta, 0, _lib.ptr(gy), D, gth, ld_theta,
+                      _lib.ptr(gx), D, B, D, stream)
         elif type(tr) is VolumePreservingShiftTransformer:
             gtheta[:, th_off:th_off + D].copy_(gy)     # y = x + b: the cotangent passes to b and to x unchanged
             gx.copy_(gy)
@@ -137,6 +141,9 @@ def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, 
     elif type(tr) is SymmetrizedMoebiusTransformer:
         _lib.call('tfep_symmetrized_moebius_backward', _lib.ptr(x), D, th, ld_theta, int(tr.dimension), float(tr.max_radius),
                   0, _lib.ptr(gy), D, _lib.ptr(gl), gth, ld_theta, _lib.ptr(gx), D, B, D, stream)
+    elif type(tr) is QuaternionProductTransformer:          # (log-det 0: gl takes no part)
+        _lib.call('tfep_quaternion_product_backward', _lib.ptr(x), D, th, ld_theta, 0, _lib.ptr(gy), D, gth, ld_theta,
+                  _lib.ptr(gx), D, B, D, stream)
     else:   # volume-preserving shift: y = x + b (wrap is piecewise identity), log-det = 0
         _lib.call('tfep_copy_2d', _lib.ptr(gy), D, gth, ld_theta, B, D, stream)
         _lib.call('tfep_copy_2d', _lib.ptr(gy), D, _lib.ptr(gx), D, B, D, stream)
@@ -251,7 +258,7 @@ class TransformerFunction(torch.autograd.Function):
 
 
 _HIP_TRANSFORMERS = (AffineTransformer, MoebiusTransformer, VolumePreservingShiftTransformer, NeuralSplineTransformer,
-                     MixedTransformer, SOSPolynomialTransformer, SymmetrizedMoebiusTransformer)
+                     MixedTransformer, SOSPolynomialTransformer, SymmetrizedMoebiusTransformer, QuaternionProductTransformer)
 
 
 def generic_supported(layer):
@@ -347,7 +354,8 @@ def _differentiable_inverse(tr):
     from .partial import _GatherColumns, _ReplaceColumns
     if type(tr) is MoebiusTransformer:
         return lambda y_tr, theta: TransformerFunction.apply(tr, y_tr, -theta)
-    if type(tr) is SymmetrizedMoebiusTransformer:            # its inverse op has an autograd registration of its own
+    if type(tr) in (SymmetrizedMoebiusTransformer, QuaternionProductTransformer):
+        # their inverse ops have autograd registrations of their own
         return lambda y_tr, theta: tr.inverse(y_tr.contiguous(), theta.contiguous())
     if _elementwise(tr):
         return lambda y_tr, theta: TransformerInverseFunction.apply(tr, y_tr, theta)

@@ -23,6 +23,7 @@ from ..embeddings.mafembed import PeriodicEmbedding
 from ..transformers.affine import AffineTransformer, VolumePreservingShiftTransformer
 from ..transformers.mixed import MixedTransformer, check_float64_members
 from ..transformers.moebius import MoebiusTransformer, SymmetrizedMoebiusTransformer
+from ..transformers.quatprod import QuaternionProductTransformer
 from ..transformers.sos import SOSPolynomialTransformer
 from ..transformers.spline import NeuralSplineTransformer
 from .sequential import _side_stream
@@ -667,8 +668,8 @@ class AutoregressiveFlow(torch.nn.Module):
         tr = self._transformer
         if type(tr) in (AffineTransformer, NeuralSplineTransformer):
             return True
-        if type(tr) in (MoebiusTransformer, SymmetrizedMoebiusTransformer):
-            # every vector must live inside one degree (e.g. generate_degrees(..., repeats=dimension))
+        if type(tr) in (MoebiusTransformer, SymmetrizedMoebiusTransformer, QuaternionProductTransformer):
+            # every vector (quaternion: dimension 4) must live inside one degree (e.g. generate_degrees(..., repeats=dimension))
             deg = made._degrees[0]
             deg = deg[deg != -1]
             d = tr.dimension
@@ -691,6 +692,8 @@ class AutoregressiveFlow(torch.nn.Module):
             return ('moebius', tr)
         if type(tr) is SymmetrizedMoebiusTransformer:
             return ('symmoebius', tr)
+        if type(tr) is QuaternionProductTransformer:
+            return ('quatprod', tr)
         if type(tr) is VolumePreservingShiftTransformer:
             return ('shift', tr)
         return ('affine', tr)
@@ -1743,6 +1746,8 @@ class AutoregressiveFlow(torch.nn.Module):
                                              log_det_J=ldj)
                     elif kind == 'symmoebius':
                         x_d, _ = ops.symmetrized_moebius(y_d, par, sub.dimension, sub.max_radius, inverse=True, log_det_J=ldj)
+                    elif kind == 'quatprod':    # log-det 0: ldj stays as it is
+                        x_d, _ = ops.quaternion_product(y_d, par, inverse=True, log_det_J=ldj)
                     elif kind == 'shift':       # (a member of a mixed transformer, no periodic features) log-det 0
                         x_d, _ = ops.volume_preserving_shift(y_d, par, inverse=True)
                     else:

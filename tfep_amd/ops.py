@@ -176,6 +176,24 @@ def symmetrized_moebius(x, parameters, dimension, max_radius=0.99, inverse=False
     return y, ldj
 
 
+def quaternion_product(x, parameters, inverse=False, log_det_J=None):
+    """QuaternionProductTransformer.forward / .inverse (reference quatprod.py): every 4 contiguous features are a quaternion,
+    scalar last.  The log-det is zero (an accumulated ``log_det_J`` is returned untouched).  float64 tensors run on the
+    float64 kernels; mixed float32 / float64 arguments are a TypeError; a feature count that is no multiple of 4 is a
+    ValueError."""
+    if isinstance(x, torch.Tensor) and x.dim() == 2 and x.shape[1] % 4 != 0:
+        raise ValueError(f'quaternion_product: n_features={x.shape[1]} is not a multiple of 4 (quaternions)')
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    B, D = x.shape
+    parameters, ldp = _check_params(parameters, B, D, dtype=dt)
+    y = torch.empty(B, D, dtype=x.dtype, device=x.device)
+    ldj, acc = _ldj_out(log_det_J, B, x, dt)
+    call('tfep_quaternion_product' + _sfx(dt), ptr(x), ldx, ptr(parameters), ldp, int(bool(inverse)), ptr(y), max(D, 1),
+         ptr(ldj), acc, B, D, stream_of(x))
+    return y, ldj
+
+
 def moebius_split_out(x, parameters, max_radius, cols_padded):
     """Forward map of unit-sphere 2-vectors that also returns y as split-f16 rows ``(y, log_det_J, y_split, y_inv_scale)`` for
     the next masked linear (``tfep_moebius_forward_split_out``)."""

@@ -12,6 +12,8 @@ in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the re
   tfep::moebius_forward / moebius_inverse / moebius_backward         reference transformers/moebius.py:104-147, 374-478
   tfep::symmetrized_moebius_forward / _inverse / _backward           reference transformers/moebius.py:193-372, 481-629
                                                                      (SYMMETRIZED_MOEBIUS_OPS)
+  tfep::quaternion_product_forward / _inverse / _backward            reference transformers/quatprod.py
+                                                                     (QUATERNION_PRODUCT_OPS)
   tfep::masked_linear / masked_linear_backward                       reference masked.py:220-302, 351-404
   tfep::fused_output_transformer                                     masked.py:188-208 (last layer) + the transformer
   tfep::tfep_reduce                                                  loss.py:125-140, analysis/estimator.py:73-86
@@ -302,6 +304,53 @@ symmetrized_moebius_forward.register_autograd(_symmoebius_bwd(False), setup_cont
 symmetrized_moebius_inverse.register_autograd(_symmoebius_bwd(True), setup_context=_moebius_setup)
 
 
+# ============================================================================= quaternion product
+
+@custom_op('tfep::quaternion_product_forward', mutates_args=(), device_types=_DEV)
+def quaternion_product_forward(x: Tensor, parameters: Tensor) -> Tuple[Tensor, Tensor]:
+    return ops.quaternion_product(x, parameters, inverse=False)
+
+
+@custom_op('tfep::quaternion_product_inverse', mutates_args=(), device_types=_DEV)
+def quaternion_product_inverse(y: Tensor, parameters: Tensor) -> Tuple[Tensor, Tensor]:
+    return ops.quaternion_product(y, parameters, inverse=True)
+
+
+@custom_op('tfep::quaternion_product_backward', mutates_args=(), device_types=_DEV)
+def quaternion_product_backward(x: Tensor, parameters: Tensor, grad_y: Tensor, inverse: bool) -> Tuple[Tensor, Tensor]:
+    """VJP of ``quaternion_product_forward`` (``inverse`` False) or ``_inverse`` (True) at its input ``x``.  The log-det is
+    the constant zero: its cotangent is no argument."""
+    x, parameters, gy = x.contiguous(), parameters.contiguous(), grad_y.contiguous()
+    dt = _vjp_dtype(x, (x, 'x'), (parameters, 'parameters'), (gy, 'grad_y'))
+    B, D = x.shape
+    if parameters.shape != x.shape or gy.shape != x.shape:
+        raise ValueError('quaternion_product_backward: parameters and grad_y must have the shape of x')
+    gx = torch.empty_like(x)
+    gp = torch.empty_like(parameters)
+    _lib.call('tfep_quaternion_product_backward' + ops._sfx(dt), _lib.ptr(x), max(D, 1), _lib.ptr(parameters), max(D, 1),
+              int(bool(inverse)), _lib.ptr(gy), max(D, 1), _lib.ptr(gp), max(D, 1), _lib.ptr(gx), max(D, 1), B, D,
+              _lib.stream_of(x))
+    return gx, gp
+
+
+quaternion_product_forward.register_fake(lambda x, parameters: _pair_like(x))
+quaternion_product_inverse.register_fake(lambda y, parameters: _pair_like(y))
+quaternion_product_backward.register_fake(lambda x, parameters, gy, inverse: (x.new_empty(x.shape),
+                                                                              parameters.new_empty(parameters.shape)))
+
+
+def _quatprod_bwd(inverse):
+    def bwd(ctx, gy, gl):
+        x, p = ctx.saved_tensors
+        gy, _ = _vjp_inputs(ctx, (gy, gl))
+        return torch.ops.tfep.quaternion_product_backward(x, p, gy, inverse)
+    return bwd
+
+
+quaternion_product_forward.register_autograd(_quatprod_bwd(False), setup_context=_save_xp)
+quaternion_product_inverse.register_autograd(_quatprod_bwd(True), setup_context=_save_xp)
+
+
 # ============================================================================= masked linear
 
 @custom_op('tfep::masked_linear', mutates_args=(), device_types=_DEV)
@@ -488,3 +537,4 @@ OPS = ('affine_forward', 'affine_inverse', 'affine_backward', 'spline_forward', 
 # (a tuple of their own: OPS is the list the existing op tests iterate over)
 SOS_OPS = ('sos_forward', 'sos_backward')
 SYMMETRIZED_MOEBIUS_OPS = ('symmetrized_moebius_forward', 'symmetrized_moebius_inverse', 'symmetrized_moebius_backward')
+QUATERNION_PRODUCT_OPS = ('quaternion_product_forward', 'quaternion_product_inverse', 'quaternion_product_backward')

@@ -1476,6 +1476,101 @@ def gen_symmoebius():
     np.savez_compressed(os.path.join(OUT, 'symmoebius.npz'), **out)
 
 
+def quatprod_flows():
+    """The flow configurations of quatprod.npz: name -> (constructor(dtype), n_features)."""
+    from tfep.nn.conditioners.made import generate_degrees as gd
+    from tfep.nn.transformers.quatprod import QuaternionProductTransformer
+
+    def mixed(dt):
+        return MixedTransformer(
+            transformers=[QuaternionProductTransformer(),
+                          NeuralSplineTransformer(x0=torch.full((4,), -4.0).to(dt), xf=torch.full((4,), 4.0).to(dt), n_bins=8)],
+            indices=[[0, 1, 2, 3, 4, 5, 6, 7], [8, 9, 10, 11]])
+    return {
+        # two quaternions, each inside one degree
+        'quat': (lambda dt: SequentialFlow(
+            MAF(degrees_in=gd(8, 'ascending', repeats=4), transformer=QuaternionProductTransformer(), initialize_identity=False),
+            MAF(degrees_in=gd(8, 'descending', repeats=4), transformer=QuaternionProductTransformer(),
+                initialize_identity=False)), 8),
+        # two quaternions beside four spline features (positions), degrees in groups of 4
+        'mixquat': (lambda dt: SequentialFlow(
+            MAF(degrees_in=gd(12, 'ascending', repeats=4), transformer=mixed(dt), initialize_identity=False)), 12),
+        # one degree per feature: the quaternions straddle degrees (the reference's algorithm, pass per degree, still defines
+        # what ``inverse`` returns; it is not the inverse map then)
+        'straddle': (lambda dt: SequentialFlow(
+            MAF(degrees_in=gd(8, 'ascending'), transformer=QuaternionProductTransformer(), initialize_identity=False)), 8),
+    }
+
+
+def gen_quatprod():
+    """Reference QuaternionProductTransformer (quatprod.py), float64 and float32 on float32-rounded inputs, with
+    ``tools/roma_standin.py`` in place of the ``roma`` package (scalar-last Hamilton product).
+    Transformer level (1 and 3 quaternions, B = 16): y and the inverse applied to an independent input, and the gradients of
+    sum(gy * y) with respect to the input and the raw parameters in both directions.  The flows of ``quatprod_flows``:
+    forward, inverse, and BoltzmannKLDivLoss(u(.), log_det_J) with u(y) = sum_f (c_f y_f^2 + d_f y_f) and its gradients,
+    forward and through the inverse."""
+    import roma_standin
+    roma_standin.install()
+    from tfep.nn.transformers.quatprod import QuaternionProductTransformer
+    out = {}
+    B = 16
+    tr = QuaternionProductTransformer()
+    for n_quat in (1, 3):
+        name = f'tr/n{n_quat}'
+        g = gen(300 + n_quat)
+        D = 4 * n_quat
+
+        def unit(t):
+            return (t.reshape(B, n_quat, 4) / t.reshape(B, n_quat, 4).norm(dim=-1, keepdim=True)).reshape(B, D)
+        x, yin = unit(torch.randn(B, D, generator=g)), unit(torch.randn(B, D, generator=g))
+        p, gy = 2 * torch.randn(B, D, generator=g), torch.randn(B, D, generator=g)
+        for k, v in (('x', x), ('p', p), ('yin', yin), ('gy', gy)):
+            out[f'{name}/{k}'] = npy(v)
+        for tag, dt in (('f64', torch.float64), ('f32', torch.float32)):
+            for sfx, fn, inp in (('', tr.forward, x), ('_inv', tr.inverse, yin)):
+                xx = inp.to(dt).clone().requires_grad_(True)
+                pp = p.to(dt).clone().requires_grad_(True)
+                y, ldj = fn(xx, pp)
+                (gy.to(dt) * y).sum().backward()
+                out[f'{name}/y{sfx}_{tag}'], out[f'{name}/ldj{sfx}_{tag}'] = npy(y), npy(ldj)
+                out[f'{name}/gx{sfx}_{tag}'], out[f'{name}/gpar{sfx}_{tag}'] = npy(xx.grad), npy(pp.grad)
+    out['identity/n12'] = npy(tr.get_identity_parameters(12))
+
+    def quad(y, c, d):
+        return (c * y ** 2 + d * y).sum(dim=1)
+
+    B = 32
+    for i, (name, (make, D)) in enumerate(quatprod_flows().items()):
+        seed = 70 + 10 * i
+        torch.manual_seed(seed)
+        f32 = make(torch.float32)
+        perturb_weight_g(f32, seed + 1)
+        g = gen(seed + 2)
+        x = torch.randn(B, D, generator=g)
+        c = torch.rand(D, generator=g) * 0.3
+        d = torch.randn(D, generator=g) * 0.2
+        sd = {k: v.clone() for k, v in f32.state_dict().items()}
+        with f64():
+            m64 = make(torch.float64)
+            m64.load_state_dict(to_double_sd(sd))
+        for tag, m, dt in (('f64', m64, torch.float64), ('f32', f32, torch.float32)):
+            for sfx, fn in (('', m.forward), ('_inv', m.inverse)):
+                m.zero_grad(set_to_none=True)
+                xx = x.to(dt).clone().requires_grad_(True)
+                y, ldj = fn(xx)
+                loss = BoltzmannKLDivLoss()(quad(y, c.to(dt), d.to(dt)), ldj)
+                loss.backward()
+                out[f'{name}/y{sfx}_{tag}'], out[f'{name}/ldj{sfx}_{tag}'] = npy(y), npy(ldj)
+                out[f'{name}/loss{sfx}_{tag}'], out[f'{name}/gx{sfx}_{tag}'] = npy(loss), npy(xx.grad)
+                for k, prm in m.named_parameters():
+                    out[f'{name}/grad{sfx}_{tag}/{k}'] = npy(prm.grad)
+        out[f'{name}/x'], out[f'{name}/c'], out[f'{name}/d'] = npy(x), npy(c), npy(d)
+        for k, v in sd.items():
+            if not k.endswith('.mask'):
+                out[f'{name}/sd/{k}'] = npy(v)
+    np.savez_compressed(os.path.join(OUT, 'quatprod.npz'), **out)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
     if len(sys.argv) > 1:
