@@ -850,6 +850,60 @@ int tfep_gather_columns_f64(const double* src, int64_t lds, const int32_t* idx, 
 int tfep_scatter_columns_f64(const double* src, int64_t lds, const int32_t* idx, int n_idx,
                              double* dst, int64_t ldd, int B, void* stream);
 
+/*
+ * FlipInvariantEmbedding.forward (embeddings/mafembed.py:174-348; Koehler et al. 2023, SI eq. 46), float32 and float64.
+ * The embedded columns are n_embedded / vector_dim vectors v of vector_dim consecutive table entries; with the two
+ * perceptrons vector_dim -> hidden -> emb_dim ("emb_*": embedding_layer.{0,2}) and vector_dim -> hidden -> 1 ("wgt_*":
+ * weight_layer.{0,2}), torch.nn.Linear layout (weight: out x in, row-major), ELU between the layers:
+ *     e+- = emb(+-v),   (w+, w-) = softmax(wgt(+v), wgt(-v)),   out = w+ e+ + w- e-
+ *   out[b] = [x[b, nonembedded_indices[0..n_nonembedded)], emb_dim values per vector]           (mafembed.py:303-306)
+ * out(x) and out(x with every embedded column negated) are equal bit for bit.  float32 computes in fp32, float64 in IEEE
+ * fp64.  Limits: vector_dim <= 8, hidden <= 64, emb_dim <= 32, n_embedded % vector_dim == 0 (invalid argument otherwise).
+ * B == 0 returns TFEP_OK.  The index tables hold columns of x: they are not checked against its width.
+ */
+int tfep_flip_invariant_embedding(const float* x, int64_t ldx, const int32_t* embedded_indices, int n_embedded,
+                                  const int32_t* nonembedded_indices, int n_nonembedded, int vector_dim, int hidden,
+                                  int emb_dim, const float* emb_w1, const float* emb_b1, const float* emb_w2,
+                                  const float* emb_b2, const float* wgt_w1, const float* wgt_b1, const float* wgt_w2,
+                                  const float* wgt_b2, float* out, int64_t ldo, int B, void* stream);
+int tfep_flip_invariant_embedding_f64(const double* x, int64_t ldx, const int32_t* embedded_indices, int n_embedded,
+                                      const int32_t* nonembedded_indices, int n_nonembedded, int vector_dim, int hidden,
+                                      int emb_dim, const double* emb_w1, const double* emb_b1, const double* emb_w2,
+                                      const double* emb_b2, const double* wgt_w1, const double* wgt_b1, const double* wgt_w2,
+                                      const double* wgt_b2, double* out, int64_t ldo, int B, void* stream);
+/*
+ * VJP of the above for the cotangent gout (B, n_nonembedded + emb_dim n_vectors); the forward is recomputed from x.
+ *   gx (B, every input column): written in full -- the pass-through columns receive their cotangent, the embedded ones the
+ *       VJP through both networks and the softmax; nothing needs zeroing.
+ *   g_*: gradients of the eight parameter tensors, shaped like them; accumulate != 0 adds to their contents (the layer
+ *       backward adds chunk after chunk), otherwise they are overwritten.  Sums over the B n_vectors lanes run in fp64 in
+ *       a fixed order (wave, workgroup, then workspace rows in row order; no atomics): two runs of the same call give the
+ *       same bits.  g_wgt_b2 is exactly zero (the softmax over the pair is shift invariant).
+ *   workspace: tfep_flip_invariant_embedding_backward_workspace_bytes(...) bytes of device memory, 8-byte aligned; its
+ *       contents on entry do not matter.
+ */
+int tfep_flip_invariant_embedding_backward(const float* x, int64_t ldx, const int32_t* embedded_indices, int n_embedded,
+                                           const int32_t* nonembedded_indices, int n_nonembedded, int vector_dim,
+                                           int hidden, int emb_dim, const float* emb_w1, const float* emb_b1,
+                                           const float* emb_w2, const float* emb_b2, const float* wgt_w1,
+                                           const float* wgt_b1, const float* wgt_w2, const float* wgt_b2, const float* gout,
+                                           int64_t ldg, float* gx, int64_t ldgx, float* g_emb_w1, float* g_emb_b1,
+                                           float* g_emb_w2, float* g_emb_b2, float* g_wgt_w1, float* g_wgt_b1,
+                                           float* g_wgt_w2, float* g_wgt_b2, int accumulate, double* workspace, int B,
+                                           void* stream);
+int tfep_flip_invariant_embedding_backward_f64(const double* x, int64_t ldx, const int32_t* embedded_indices, int n_embedded,
+                                               const int32_t* nonembedded_indices, int n_nonembedded, int vector_dim,
+                                               int hidden, int emb_dim, const double* emb_w1, const double* emb_b1,
+                                               const double* emb_w2, const double* emb_b2, const double* wgt_w1,
+                                               const double* wgt_b1, const double* wgt_w2, const double* wgt_b2,
+                                               const double* gout, int64_t ldg, double* gx, int64_t ldgx, double* g_emb_w1,
+                                               double* g_emb_b1, double* g_emb_w2, double* g_emb_b2, double* g_wgt_w1,
+                                               double* g_wgt_b1, double* g_wgt_w2, double* g_wgt_b2, int accumulate,
+                                               double* workspace, int B, void* stream);
+/* Bytes of the backward's workspace for these sizes (the same for both element types); negative on unsupported sizes. */
+int64_t tfep_flip_invariant_embedding_backward_workspace_bytes(int B, int n_embedded, int vector_dim, int hidden,
+                                                               int emb_dim);
+
 /* ------------------------------------------------------------------------- */
 /* TFEP reductions (tfep/loss.py, tfep/analysis/estimator.py)                 */
 /* ------------------------------------------------------------------------- */

@@ -279,7 +279,15 @@ _SIGNATURES = {
     'tfep_gather_columns_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, _P]),
     'tfep_scatter_columns_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, _P]),
     'tfep_tfep_reduce_f64': (c_int, [_P, _P, _P, _P, _P, c_double, c_int, c_int, _P, _P, _P]),
+    'tfep_flip_invariant_embedding_backward_workspace_bytes': (c_int64, [c_int, c_int, c_int, c_int, c_int]),
 }
+# x, ldx, the two index tables, (vector_dim, hidden, emb_dim), the eight parameters; then out, ldo -- or gout, ldg, gx,
+# ldgx, the eight gradients, accumulate, workspace --; B, stream
+_FLIP_HEAD = [_P, c_int64, _P, c_int, _P, c_int, c_int, c_int, c_int] + [_P] * 8
+_SIGNATURES.update({'tfep_flip_invariant_embedding' + s: (c_int, _FLIP_HEAD + [_P, c_int64, c_int, _P]) for s in ('', '_f64')})
+_SIGNATURES.update({'tfep_flip_invariant_embedding_backward' + s: (
+    c_int, _FLIP_HEAD + [_P, c_int64, _P, c_int64] + [_P] * 8 + [c_int, _P, c_int, _P]) for s in ('', '_f64')})
+del _FLIP_HEAD
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

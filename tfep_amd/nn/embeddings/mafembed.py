@@ -1,16 +1,17 @@
 """MAF embedding layers (reference ``tfep/nn/embeddings/mafembed.py``): periodic, flip-invariant and mixed embeddings
 of the conditioner input.
 
-``PeriodicEmbedding`` runs on its HIP kernels (forward and backward).  ``FlipInvariantEmbedding`` is two 2-layer
-perceptrons on 2-8 inputs per vector and ``MixedEmbedding`` is index bookkeeping: both are O(batch x features) work in
-front of the MADE GEMMs and are written with ordinary (differentiable) torch ops on the device.
+``PeriodicEmbedding`` and ``FlipInvariantEmbedding`` run on their HIP kernels, forward and backward, in float32 and
+float64 (``csrc/embedding.h``, ``csrc/flipembed.hip``).  ``FlipInvariantEmbedding`` keeps the reference's torch code as
+``torch_forward`` for what the kernels do not take -- CPU tensors, other dtypes, networks above the kernel's size limits --
+and ``last_route`` says which one ran.  ``MixedEmbedding`` is index bookkeeping around its members.
 """
 import abc
 from typing import Optional, Sequence
 
 import torch
 
-from ... import ops
+from ... import ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.tfep.*)
 from ...utils.misc import ensure_tensor_sequence, remove_and_shift_sorted_indices
 
 
@@ -118,7 +119,16 @@ class FlipInvariantEmbedding(MAFEmbedding):
 
     Output layout follows the reference: the non-embedded features first, then ``embedding_dimension`` features
     per vector.  Arguments as reference mafembed.py:187-215.
+
+    A float32 / float64 tensor on a HIP device, of the dtype of the parameters, with ``vector_dimension <= 8``,
+    ``hidden_layer_width <= 64`` and ``embedding_dimension <= 32`` runs on the HIP kernels
+    (``torch.ops.tfep.flip_invariant_embedding``: one launch forward, the VJP kernel backward); anything else runs
+    ``torch_forward``, the reference's torch code.  Both give ``emb(x) == emb(x with the embedded columns negated)`` bit
+    for bit.
     """
+
+    #: which code the last ``forward`` call ran: ``'kernel'`` or ``'torch'``
+    last_route = None
 
     def __init__(self, n_features_in: int, embedding_dimension: int,
                  embedded_indices: Optional[Sequence[int]] = None, vector_dimension: int = 4,
@@ -133,6 +143,49 @@ class FlipInvariantEmbedding(MAFEmbedding):
         self.weight_layer = perceptron(1)                           # their (pre-softmax) weights
         self.register_buffer('_embedded_indices', embedded)
         self.register_buffer('_nonembedded_indices', rest)
+        self._i32 = {}
+
+    def _apply(self, fn, *args, **kwargs):
+        self._i32 = {}
+        return super()._apply(fn, *args, **kwargs)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._i32 = {}
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def device_indices(self, device):
+        """``(embedded, non-embedded)`` column tables as int32 tensors on ``device`` (cached)."""
+        key = str(device)
+        if key not in self._i32:
+            self._i32[key] = (self._embedded_indices.to(device=device, dtype=torch.int32),
+                              self._nonembedded_indices.to(device=device, dtype=torch.int32))
+        return self._i32[key]
+
+    def network_parameters(self):
+        """The eight parameter tensors in the order of the kernels' argument lists."""
+        e, w = self.embedding_layer, self.weight_layer
+        return (e[0].weight, e[0].bias, e[2].weight, e[2].bias, w[0].weight, w[0].bias, w[2].weight, w[2].bias)
+
+    @property
+    def hidden_layer_width(self) -> int:
+        """int: The width of the hidden layer of the two networks."""
+        return self.embedding_layer[0].out_features
+
+    def within_kernel_limits(self) -> bool:
+        """Whether the two networks are of a size the HIP kernels take."""
+        return ops.flip_embedding_supported(self.vector_dimension, self.hidden_layer_width, self.embedding_dimension)
+
+    def takes_kernel_route(self, x) -> bool:
+        """True when ``forward(x)`` runs on the HIP kernels.  A float32 tensor on a float64 module (or the reverse) on the
+        device is the TypeError of the project's dtype contract, not a reason to fall back."""
+        kernel_types = (torch.float32, torch.float64)
+        w = self.embedding_layer[0].weight
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and w.is_cuda and self.within_kernel_limits()
+                and x.dtype in kernel_types and w.dtype in kernel_types):
+            return False
+        if x.dtype != w.dtype:
+            raise TypeError(f'{type(self).__name__}: x is {x.dtype}, the parameters are {w.dtype}')
+        return True
 
     @property
     def vector_dimension(self) -> int:
@@ -145,6 +198,16 @@ class FlipInvariantEmbedding(MAFEmbedding):
         return self.embedding_layer[-1].out_features
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.takes_kernel_route(x):
+            self.last_route = 'torch'
+            return self.torch_forward(x)
+        self.last_route = 'kernel'
+        embedded, rest = self.device_indices(x.device)
+        return torch.ops.tfep.flip_invariant_embedding(x, embedded, rest, self.vector_dimension,
+                                                       *self.network_parameters())
+
+    def torch_forward(self, x: torch.Tensor) -> torch.Tensor:
+        """The embedding in ordinary (differentiable) torch operators, on any device and dtype."""
         batch_size = x.shape[0]
         v = x[:, self._embedded_indices].reshape(-1, self.vector_dimension)      # (batch * n_vectors, vector_dim)
         # The vector and its flip go through the networks as two separate calls of the same shape: then the result

@@ -25,7 +25,7 @@ import torch
 from ... import _lib, ops
 from ..conditioners.made import MADE
 from ..masked import GRAD_IS_MASKED
-from ..embeddings.mafembed import MAFEmbedding, PeriodicEmbedding
+from ..embeddings.mafembed import FlipInvariantEmbedding, MAFEmbedding, PeriodicEmbedding
 from ..transformers.affine import AffineTransformer, VolumePreservingShiftTransformer
 from ..transformers.mixed import MixedTransformer
 from ..transformers.moebius import MoebiusTransformer, SymmetrizedMoebiusTransformer
@@ -819,7 +819,9 @@ def layer_backward(layer, x, gy, gldj, saved=None, need_gx=True):
     gW = [(ops.zeros if B == 0 else torch.empty)(n_pad[l], k_pad[l], **f32) for l in range(L + 1)]      # (empty batch: no chunk writes)
     gb = [ops.zeros(n_pad[l], **f32) for l in range(L + 1)]
     gx = torch.empty(B, D, **f32) if need_gx else None
-    emb_generic = emb is not None and type(emb) is not PeriodicEmbedding
+    # a flip-invariant embedding on its kernels: the VJP entry point is called directly, like the periodic one's
+    emb_flip = type(emb) is FlipInvariantEmbedding and emb.takes_kernel_route(x)
+    emb_generic = emb is not None and type(emb) is not PeriodicEmbedding and not emb_flip
     emb_params = _embedding_params(layer)
     g_emb = [torch.zeros_like(p) for p in emb_params]
 
@@ -833,7 +835,7 @@ def layer_backward(layer, x, gy, gldj, saved=None, need_gx=True):
 
         # ---- recompute the conditioner forward for the chunk
         if emb_generic:
-            # any other MAFEmbedding (flip-invariant / mixed): differentiated by autograd, chunk by chunk
+            # any other MAFEmbedding (mixed, a flip-invariant one off its kernels): differentiated by autograd, chunk by chunk
             with torch.enable_grad():
                 x_emb = xc.detach().requires_grad_(True)
                 cin_graph = emb(x_emb)
@@ -915,6 +917,11 @@ def layer_backward(layer, x, gy, gldj, saved=None, need_gx=True):
                 if new_g is not None:
                     acc_g += new_g
             del cin_graph, x_emb
+        elif emb_flip:
+            # gx written in full by the kernel; the parameter gradients are added to g_emb chunk after chunk
+            gxc = torch.empty(Bc, D, **f32)
+            ops.flip_invariant_embedding_backward(xc, *emb.device_indices(dev), emb.vector_dimension,
+                                                  [p.detach() for p in emb.network_parameters()], g, grads=g_emb, gx=gxc)
         elif emb is not None:
             per, non = emb.device_indices(dev)
             gxc = ops.zeros(Bc, D, **f32)

@@ -19,7 +19,7 @@ import torch
 from ... import _lib, ops
 from ...utils.misc import ensure_tensor_sequence
 from ..conditioners.made import MADE
-from ..embeddings.mafembed import PeriodicEmbedding
+from ..embeddings.mafembed import FlipInvariantEmbedding, MixedEmbedding, PeriodicEmbedding
 from ..transformers.affine import AffineTransformer, VolumePreservingShiftTransformer
 from ..transformers.mixed import MixedTransformer, check_float64_members
 from ..transformers.moebius import MoebiusTransformer, SymmetrizedMoebiusTransformer
@@ -476,9 +476,9 @@ class AutoregressiveFlow(torch.nn.Module):
         if type(tr) is MixedTransformer:
             check_float64_members(tr)
         emb = getattr(self._conditioner, 'embedding', None)
-        if emb is not None and type(emb) is not PeriodicEmbedding:
+        if emb is not None and not _float64_embedding(emb):
             raise TypeError(f'{type(self).__name__}: float64 is not supported for the {type(emb).__name__} embedding yet '
-                            '(float64 layers take a PeriodicEmbedding or none)')
+                            '(float64 layers take a PeriodicEmbedding, a FlipInvariantEmbedding, a MixedEmbedding of those, or none)')
 
     def _forward_f64(self, x):
         self._check_float64(x, 'x')
@@ -2000,6 +2000,14 @@ capture_flags = None
 #: counter)`` in it and runs on the split kernels without waiting; the sequence reads all the counters at its end -- ONE host
 #: synchronisation per flow call instead of one per layer -- and repeats the call from the first flagged layer on.
 deferred_flags = None
+
+
+def _float64_embedding(emb):
+    """The embeddings a float64 layer takes: those with float64 kernels, alone or as the members of a MixedEmbedding."""
+    kernels = (PeriodicEmbedding, FlipInvariantEmbedding)
+    if type(emb) is MixedEmbedding:
+        return all(type(member) in kernels for member in emb.embedding_layers)
+    return type(emb) in kernels
 
 
 def _flag_for_capture(x):

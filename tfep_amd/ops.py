@@ -226,6 +226,83 @@ def periodic_embedding(x, periodic_indices, nonperiodic_indices, lower, upper):
     return out
 
 
+#: the sizes the flip-invariant embedding kernels are built for (``csrc/flipembed.h``)
+FLIP_MAX_VECTOR_DIM, FLIP_MAX_HIDDEN, FLIP_MAX_EMBEDDING_DIM = 8, 64, 32
+
+
+def flip_embedding_supported(vector_dim, hidden, emb_dim):
+    """Whether ``tfep_flip_invariant_embedding*`` takes these network sizes."""
+    return 1 <= vector_dim <= FLIP_MAX_VECTOR_DIM and 1 <= hidden <= FLIP_MAX_HIDDEN and 1 <= emb_dim <= FLIP_MAX_EMBEDDING_DIM
+
+
+def _flip_head(x, embedded_indices, nonembedded_indices, vector_dim, parameters, dt):
+    """The leading arguments the forward and the backward entry point share; ``parameters``: the eight tensors
+    ``embedding_layer.{0,2}.{weight,bias}``, ``weight_layer.{0,2}.{weight,bias}`` in that order.  Returns ``(args, keep,
+    n_out)``: ``keep`` holds the contiguous copies until the launch is queued."""
+    if len(parameters) != 8:
+        raise ValueError('flip_invariant_embedding: eight parameter tensors expected')
+    keep = [check_device_tensor(p, 'parameters', dt).contiguous() for p in parameters]
+    for t, n in ((embedded_indices, 'embedded_indices'), (nonembedded_indices, 'nonembedded_indices')):
+        check_device_tensor(t, n, torch.int32)
+    d, (H, d_w), (E, H2) = int(vector_dim), keep[0].shape, keep[2].shape
+    shapes = [(H, d), (H,), (E, H), (E,), (H, d), (H,), (1, H), (1,)]
+    if [tuple(p.shape) for p in keep] != shapes:
+        raise ValueError(f'flip_invariant_embedding: parameter shapes {[tuple(p.shape) for p in keep]} are not those of '
+                         f'two perceptrons {d} -> {H} -> {E} / 1')
+    n_emb, n_non = embedded_indices.numel(), nonembedded_indices.numel()
+    if n_emb + n_non != x.shape[1]:
+        raise ValueError(f'flip_invariant_embedding: the index tables cover {n_emb + n_non} features, x has {x.shape[1]}')
+    eidx, nidx = embedded_indices.contiguous(), nonembedded_indices.contiguous()
+    keep += [eidx, nidx]
+    args = (ptr(eidx), n_emb, ptr(nidx), n_non, d, H, E, *(ptr(p) for p in keep[:8]))
+    return args, keep, n_non + (n_emb // d if d > 0 else 0) * E
+
+
+def flip_invariant_embedding(x, embedded_indices, nonembedded_indices, vector_dim, parameters):
+    """FlipInvariantEmbedding.forward (reference mafembed.py:270-306) in one launch.  float64 tensors run on the float64
+    kernel; mixed float32 / float64 arguments are a TypeError; sizes over the limits a ValueError."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    B = x.shape[0]
+    head, keep, n_out = _flip_head(x, embedded_indices, nonembedded_indices, vector_dim, parameters, dt)
+    out = torch.empty(B, n_out, dtype=dt, device=x.device)
+    call('tfep_flip_invariant_embedding' + _sfx(dt), ptr(x), ldx, *head, ptr(out), max(n_out, 1), B, stream_of(x))
+    return out
+
+
+def flip_invariant_embedding_backward(x, embedded_indices, nonembedded_indices, vector_dim, parameters, grad_out,
+                                      grads=None, gx=None):
+    """VJP of ``flip_invariant_embedding`` for the cotangent ``grad_out`` (its first ``n_out`` columns; any row stride):
+    ``(gx, grads)`` with ``grads`` the eight parameter gradients.  ``grads`` given: the call ADDS to them (the layer
+    backward's batch chunks); ``gx`` given: written in place (contiguous, the shape of ``x``)."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    B, D = x.shape
+    head, keep, n_out = _flip_head(x, embedded_indices, nonembedded_indices, vector_dim, parameters, dt)
+    grad_out, ldg = rows(grad_out, 'grad_out', dt)
+    if grad_out.shape[0] != B or grad_out.shape[1] < n_out:
+        raise ValueError(f'flip_invariant_embedding_backward: grad_out must be ({B}, >= {n_out}), got {tuple(grad_out.shape)}')
+    if gx is None:
+        gx = torch.empty(B, D, dtype=dt, device=x.device)
+    elif check_device_tensor(gx, 'gx', dt).shape != x.shape or not gx.is_contiguous():
+        raise ValueError('flip_invariant_embedding_backward: gx must be a contiguous tensor of the shape of x')
+    accumulate = grads is not None
+    if accumulate:
+        for g, p in zip(grads, keep[:8]):
+            if check_device_tensor(g, 'grads', dt).shape != p.shape or not g.is_contiguous():
+                raise ValueError('flip_invariant_embedding_backward: grads must be contiguous and shaped like the parameters')
+    else:
+        # (an empty batch launches nothing: its gradients are zeros, filled by a kernel -- see ``zeros``)
+        grads = [(zeros if B == 0 else torch.empty)(*p.shape, dtype=dt, device=x.device) for p in keep[:8]]
+    n_bytes = _lib.load().tfep_flip_invariant_embedding_backward_workspace_bytes(B, *head[1:2], *head[4:7])
+    if n_bytes < 0:
+        raise ValueError(_lib.load().tfep_last_error().decode())
+    ws = torch.empty(max(n_bytes // 8, 1), dtype=torch.float64, device=x.device)
+    call('tfep_flip_invariant_embedding_backward' + _sfx(dt), ptr(x), ldx, *head, ptr(grad_out), ldg, ptr(gx), max(D, 1),
+         *(ptr(g) for g in grads), int(accumulate), ptr(ws), B, stream_of(x))
+    return gx, list(grads)
+
+
 def gather_columns(src, idx):
     dt = _dtype(src)
     src, lds = rows(src, 'src', dt)

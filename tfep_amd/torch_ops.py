@@ -14,6 +14,8 @@ in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the re
                                                                      (SYMMETRIZED_MOEBIUS_OPS)
   tfep::quaternion_product_forward / _inverse / _backward            reference transformers/quatprod.py
                                                                      (QUATERNION_PRODUCT_OPS)
+  tfep::flip_invariant_embedding / _backward                         reference embeddings/mafembed.py:174-348
+                                                                     (FLIP_EMBEDDING_OPS)
   tfep::masked_linear / masked_linear_backward                       reference masked.py:220-302, 351-404
   tfep::fused_output_transformer                                     masked.py:188-208 (last layer) + the transformer
   tfep::tfep_reduce                                                  loss.py:125-140, analysis/estimator.py:73-86
@@ -351,6 +353,55 @@ quaternion_product_forward.register_autograd(_quatprod_bwd(False), setup_context
 quaternion_product_inverse.register_autograd(_quatprod_bwd(True), setup_context=_save_xp)
 
 
+# ============================================================================= flip-invariant embedding
+
+@custom_op('tfep::flip_invariant_embedding', mutates_args=(), device_types=_DEV)
+def flip_invariant_embedding(x: Tensor, embedded_indices: Tensor, nonembedded_indices: Tensor, vector_dim: int,
+                             emb_w1: Tensor, emb_b1: Tensor, emb_w2: Tensor, emb_b2: Tensor, wgt_w1: Tensor,
+                             wgt_b1: Tensor, wgt_w2: Tensor, wgt_b2: Tensor) -> Tensor:
+    """``FlipInvariantEmbedding.forward``: the index tables are int32, the eight parameters those of
+    ``embedding_layer.{0,2}`` and ``weight_layer.{0,2}``."""
+    return ops.flip_invariant_embedding(x, embedded_indices, nonembedded_indices, vector_dim,
+                                        (emb_w1, emb_b1, emb_w2, emb_b2, wgt_w1, wgt_b1, wgt_w2, wgt_b2))
+
+
+@custom_op('tfep::flip_invariant_embedding_backward', mutates_args=(), device_types=_DEV)
+def flip_invariant_embedding_backward(x: Tensor, embedded_indices: Tensor, nonembedded_indices: Tensor, vector_dim: int,
+                                      emb_w1: Tensor, emb_b1: Tensor, emb_w2: Tensor, emb_b2: Tensor, wgt_w1: Tensor,
+                                      wgt_b1: Tensor, wgt_w2: Tensor, wgt_b2: Tensor, grad_out: Tensor
+                                      ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """VJP of ``flip_invariant_embedding``: ``(gx, the eight parameter gradients)``."""
+    gx, grads = ops.flip_invariant_embedding_backward(x, embedded_indices, nonembedded_indices, vector_dim,
+                                                      (emb_w1, emb_b1, emb_w2, emb_b2, wgt_w1, wgt_b1, wgt_w2, wgt_b2),
+                                                      grad_out.contiguous())
+    return (gx, *grads)
+
+
+@flip_invariant_embedding.register_fake
+def _(x, embedded_indices, nonembedded_indices, vector_dim, emb_w1, emb_b1, emb_w2, *rest):
+    n_vectors = embedded_indices.numel() // vector_dim
+    return x.new_empty((x.shape[0], nonembedded_indices.numel() + n_vectors * emb_w2.shape[0]))
+
+
+@flip_invariant_embedding_backward.register_fake
+def _(x, embedded_indices, nonembedded_indices, vector_dim, *rest):
+    return (x.new_empty(x.shape), *(p.new_empty(p.shape) for p in rest[:8]))
+
+
+def _flip_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], inputs[2], *inputs[4:])
+    ctx.vector_dim = inputs[3]
+
+
+def _flip_bwd(ctx, grad_out):
+    x, eidx, nidx, *params = ctx.saved_tensors
+    gx, *grads = torch.ops.tfep.flip_invariant_embedding_backward(x, eidx, nidx, ctx.vector_dim, *params, grad_out)
+    return (gx, None, None, None, *grads)
+
+
+flip_invariant_embedding.register_autograd(_flip_bwd, setup_context=_flip_setup)
+
+
 # ============================================================================= masked linear
 
 @custom_op('tfep::masked_linear', mutates_args=(), device_types=_DEV)
@@ -538,3 +589,4 @@ OPS = ('affine_forward', 'affine_inverse', 'affine_backward', 'spline_forward', 
 SOS_OPS = ('sos_forward', 'sos_backward')
 SYMMETRIZED_MOEBIUS_OPS = ('symmetrized_moebius_forward', 'symmetrized_moebius_inverse', 'symmetrized_moebius_backward')
 QUATERNION_PRODUCT_OPS = ('quaternion_product_forward', 'quaternion_product_inverse', 'quaternion_product_backward')
+FLIP_EMBEDDING_OPS = ('flip_invariant_embedding', 'flip_invariant_embedding_backward')

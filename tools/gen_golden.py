@@ -1571,6 +1571,51 @@ def gen_quatprod():
     np.savez_compressed(os.path.join(OUT, 'quatprod.npz'), **out)
 
 
+# -----------------------------------------------------------------------------
+# FlipInvariantEmbedding on its kernels: module outputs and gradients at the shapes where a kernel can go wrong
+# -----------------------------------------------------------------------------
+
+def flipembed_configs():
+    """name -> (batch, constructor arguments).  q257: one lane past a 256-thread workgroup, no pass-through column;
+    strided: scattered, non-monotone vectors and two pass-through columns; max / min: the kernel's size limits."""
+    return {
+        'q257': (257, dict(n_features_in=4, embedding_dimension=3, hidden_layer_width=32)),
+        'strided': (5, dict(n_features_in=14, embedding_dimension=5, vector_dimension=4, hidden_layer_width=16,
+                            embedded_indices=[2, 3, 4, 5, 8, 9, 10, 11, 13, 0, 1, 6])),
+        'max': (3, dict(n_features_in=16, embedding_dimension=32, vector_dimension=8, hidden_layer_width=64)),
+        'min': (1, dict(n_features_in=3, embedding_dimension=1, vector_dimension=1, hidden_layer_width=1)),
+    }
+
+
+def gen_flipembed():
+    """Reference FlipInvariantEmbedding in float64 on float32-rounded inputs and weights: the output, and the gradients
+    of (out * c).sum(), c[b, j] = cos(b + 2 j), with respect to x and to the eight parameter tensors."""
+    out = {}
+    for i, (name, (B, kw)) in enumerate(flipembed_configs().items()):
+        torch.manual_seed(1300 + i)
+        sd = FlipInvariantEmbedding(**kw).state_dict()
+        # The reference builds the non-embedded table with a helper that assumes sorted indices: for the unsorted table of
+        # 'strided' it lists embedded columns as well.  The table is set to the complement of the embedded columns, in
+        # order -- what this project's constructor builds, and what the reference itself builds from sorted indices.
+        embedded = set(sd['_embedded_indices'].tolist())
+        sd['_nonembedded_indices'] = torch.tensor([f for f in range(kw['n_features_in']) if f not in embedded], dtype=torch.int64)
+        x = torch.randn(B, kw['n_features_in'], generator=gen(5300 + i))
+        with f64():
+            emb = FlipInvariantEmbedding(**kw)
+            emb._nonembedded_indices = sd['_nonembedded_indices'].clone()
+            emb.load_state_dict(to_double_sd(sd))
+            xg = x.double().requires_grad_(True)
+            y = emb(xg)
+            c = torch.cos(torch.arange(y.shape[0]).unsqueeze(1) + 2.0 * torch.arange(y.shape[1]).unsqueeze(0))
+            (y * c).sum().backward()
+        out[f'{name}/x'], out[f'{name}/out'], out[f'{name}/gx'] = npy(x), npy(y), npy(xg.grad)
+        for k, v in sd.items():
+            out[f'{name}/sd/{k}'] = npy(v)
+        for k, prm in emb.named_parameters():
+            out[f'{name}/gp/{k}'] = npy(prm.grad)
+    np.savez_compressed(os.path.join(OUT, 'flipembed.npz'), **out)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
     if len(sys.argv) > 1:
