@@ -904,6 +904,79 @@ int tfep_flip_invariant_embedding_backward_f64(const double* x, int64_t ldx, con
 int64_t tfep_flip_invariant_embedding_backward_workspace_bytes(int B, int n_embedded, int vector_dim, int hidden,
                                                                int emb_dim);
 
+/*
+ * Frame arithmetic of the Cartesian flow wrappers (flows/centroid.py, flows/oriented.py, utils/geometry.py:239-411),
+ * float32 and float64.  A row holds n_points points of dim (centroid: 1..3) or 3 (frame) contiguous coordinates; every
+ * row stride is an argument, so a column slice of a wider tensor works.  One wave per row; per-row sums are formed in
+ * fp64 in a fixed order without atomics, so the bits of a row do not depend on the batch it is in; all arithmetic is
+ * fp64 for both element types.  B == 0 returns TFEP_OK.  No entry point has parameter gradients.
+ *
+ * The centroid's selection: `subset` (n_subset DISTINCT int32 point indices; NULL = every point) and `weights` (one per
+ * entry of the selection, normalised to sum 1; NULL = equal weights).  A subset entry outside [0, n_points) is never
+ * dereferenced: it makes the row's centroid NaN.  `fixed_entry` is the fixed point's position in the selection,
+ * `fixed_point` = subset[fixed_entry] (= fixed_entry without a subset) the point itself.
+ *
+ *   centroid_shift:    shift (B, dim) = origin - centroid,  y = x + shift on every point.
+ *   centroid_restore:  out = y with the fixed point set to (origin - sum_{k != fixed_entry} w_k y_{s_k}) / w_fixed -- skipped
+ *                      when the subset has at most one point --, then minus shift when translate_back != 0.
+ *   *_backward:        the VJPs: (gy, gshift) -> gx (gshift may be NULL), and g -> (gy, gshift).
+ */
+int tfep_centroid_shift(const float* x, int64_t ldx, const int32_t* subset, int n_subset, const float* weights,
+                        const float* origin, int dim, int n_points, float* shift, float* y, int64_t ldy, int B,
+                        void* stream);
+int tfep_centroid_shift_f64(const double* x, int64_t ldx, const int32_t* subset, int n_subset, const double* weights,
+                            const double* origin, int dim, int n_points, double* shift, double* y, int64_t ldy, int B,
+                            void* stream);
+int tfep_centroid_restore(const float* y, int64_t ldy, const float* shift, const int32_t* subset, int n_subset,
+                          const float* weights, const float* origin, int fixed_point, int fixed_entry, int dim,
+                          int n_points, int translate_back, float* out, int64_t ldo, int B, void* stream);
+int tfep_centroid_restore_f64(const double* y, int64_t ldy, const double* shift, const int32_t* subset, int n_subset,
+                              const double* weights, const double* origin, int fixed_point, int fixed_entry, int dim,
+                              int n_points, int translate_back, double* out, int64_t ldo, int B, void* stream);
+int tfep_centroid_shift_backward(const int32_t* subset, int n_subset, const float* weights, int dim, int n_points,
+                                 const float* gy, int64_t ldgy, const float* gshift, float* gx, int64_t ldgx, int B,
+                                 void* stream);
+int tfep_centroid_shift_backward_f64(const int32_t* subset, int n_subset, const double* weights, int dim, int n_points,
+                                     const double* gy, int64_t ldgy, const double* gshift, double* gx, int64_t ldgx,
+                                     int B, void* stream);
+int tfep_centroid_restore_backward(const int32_t* subset, int n_subset, const float* weights, int fixed_point,
+                                   int fixed_entry, int dim, int n_points, int translate_back, const float* g,
+                                   int64_t ldg, float* gy, int64_t ldgy, float* gshift, int B, void* stream);
+int tfep_centroid_restore_backward_f64(const int32_t* subset, int n_subset, const double* weights, int fixed_point,
+                                       int fixed_entry, int dim, int n_points, int translate_back, const double* g,
+                                       int64_t ldg, double* gy, int64_t ldgy, double* gshift, int B, void* stream);
+/*
+ *   frame_orient:  R (B, 9, row-major 3 x 3) = the rotation of reference_frame_rotation_matrix(...,
+ *                  project_on_positive_axis=False) from the points axis_point and plane_point of each row, in closed
+ *                  form (the flip to the nearer half-axis, Rodrigues with 1 / (1 + c), the in-plane rotation with its
+ *                  q_p == 0 branch);  y_i = R x_i;  round_off != 0 writes exact zeros into the three constrained
+ *                  coordinates.  axis, plane_axis in 0..2 (x, y, z); normal = +-(1 + index of the third axis), the sign
+ *                  that of the plane normal (e_axis x e_plane for OrientedFlow).  n_points < 2, a point index out of
+ *                  range, equal point indices or axes that are no frame are invalid arguments.  Degenerate geometry is
+ *                  not special-cased: a zero-length axis point gives NaN in R and y, as the torch code does.
+ *   frame_rotate:  y_i = x_i R (row vectors), or x_i R^T when transposed != 0.
+ *   *_backward:    frame_rotate: gy -> (gx, gR).  frame_orient: (gy, gR) -> gx, including the dependence of R on the two
+ *                  defining points; gR (the cotangent the rotate-back puts on R) may be NULL.
+ */
+int tfep_frame_orient(const float* x, int64_t ldx, int axis_point, int plane_point, int axis, int plane_axis, int normal,
+                      int round_off, float* y, int64_t ldy, float* R, int n_points, int B, void* stream);
+int tfep_frame_orient_f64(const double* x, int64_t ldx, int axis_point, int plane_point, int axis, int plane_axis,
+                          int normal, int round_off, double* y, int64_t ldy, double* R, int n_points, int B, void* stream);
+int tfep_frame_orient_backward(const float* x, int64_t ldx, int axis_point, int plane_point, int axis, int plane_axis,
+                               int normal, int round_off, const float* gy, int64_t ldgy, const float* gR, float* gx,
+                               int64_t ldgx, int n_points, int B, void* stream);
+int tfep_frame_orient_backward_f64(const double* x, int64_t ldx, int axis_point, int plane_point, int axis, int plane_axis,
+                                   int normal, int round_off, const double* gy, int64_t ldgy, const double* gR, double* gx,
+                                   int64_t ldgx, int n_points, int B, void* stream);
+int tfep_frame_rotate(const float* x, int64_t ldx, const float* R, int transposed, float* y, int64_t ldy, int n_points,
+                      int B, void* stream);
+int tfep_frame_rotate_f64(const double* x, int64_t ldx, const double* R, int transposed, double* y, int64_t ldy,
+                          int n_points, int B, void* stream);
+int tfep_frame_rotate_backward(const float* x, int64_t ldx, const float* R, int transposed, const float* gy, int64_t ldgy,
+                               float* gx, int64_t ldgx, float* gR, int n_points, int B, void* stream);
+int tfep_frame_rotate_backward_f64(const double* x, int64_t ldx, const double* R, int transposed, const double* gy,
+                                   int64_t ldgy, double* gx, int64_t ldgx, double* gR, int n_points, int B, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* TFEP reductions (tfep/loss.py, tfep/analysis/estimator.py)                 */
 /* ------------------------------------------------------------------------- */

@@ -288,6 +288,23 @@ _SIGNATURES.update({'tfep_flip_invariant_embedding' + s: (c_int, _FLIP_HEAD + [_
 _SIGNATURES.update({'tfep_flip_invariant_embedding_backward' + s: (
     c_int, _FLIP_HEAD + [_P, c_int64, _P, c_int64] + [_P] * 8 + [c_int, _P, c_int, _P]) for s in ('', '_f64')})
 del _FLIP_HEAD
+# the frame arithmetic of the Cartesian wrappers (csrc/frames.hip): the selection of a centroid is (subset, n_subset,
+# weights), a frame (axis_point, plane_point, axis, plane_axis, normal, round_off)
+_SEL, _FRAME = [_P, c_int, _P], [c_int] * 6
+for _s in ('', '_f64'):
+    _SIGNATURES.update({
+        'tfep_centroid_shift' + _s: (c_int, [_P, c_int64, *_SEL, _P, c_int, c_int, _P, _P, c_int64, c_int, _P]),
+        'tfep_centroid_restore' + _s: (c_int, [_P, c_int64, _P, *_SEL, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int64,
+                                               c_int, _P]),
+        'tfep_centroid_shift_backward' + _s: (c_int, [*_SEL, c_int, c_int, _P, c_int64, _P, _P, c_int64, c_int, _P]),
+        'tfep_centroid_restore_backward' + _s: (c_int, [*_SEL, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P, c_int64,
+                                                        _P, c_int, _P]),
+        'tfep_frame_orient' + _s: (c_int, [_P, c_int64, *_FRAME, _P, c_int64, _P, c_int, c_int, _P]),
+        'tfep_frame_orient_backward' + _s: (c_int, [_P, c_int64, *_FRAME, _P, c_int64, _P, _P, c_int64, c_int, c_int, _P]),
+        'tfep_frame_rotate' + _s: (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, c_int, _P]),
+        'tfep_frame_rotate_backward' + _s: (c_int, [_P, c_int64, _P, c_int, _P, c_int64, _P, c_int64, _P, c_int, c_int, _P]),
+    })
+del _SEL, _FRAME, _s
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

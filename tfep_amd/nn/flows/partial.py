@@ -2,7 +2,7 @@
 
 ``TFEPMapBase.create_partial_flow`` (reference app/base.py:573-599) wraps the MAF stack in this module when
 some atoms are fixed.  Column gather / scatter run on the HIP kernels (``tfep_gather_columns`` /
-``tfep_scatter_columns``) and are differentiable (each is the other's adjoint).
+``tfep_scatter_columns``, float32 and float64) and are differentiable (each is the other's adjoint).
 """
 from typing import Sequence, Tuple
 
@@ -87,7 +87,7 @@ class PartialFlow(torch.nn.Module):
         has_fixed = len(self._fixed_indices) > 0
         x_in = x
         if has_fixed:
-            ops.check_device_tensor(x, 'x')
+            ops.check_device_tensor(x, 'x', ops._dtype(x))      # float32 or float64; the wrapped flow checks its own
             prop = self._indices(x)
             x_in = _GatherColumns.apply(x, prop)
         out = self.flow.inverse(x_in) if inverse else self.flow(x_in)

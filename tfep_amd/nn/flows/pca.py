@@ -4,7 +4,9 @@ Same constructor, buffers (``mean``, ``whitening_matrix``, ``blackening_matrix``
 reference's state_dict schema) and pass logic.  The whitening statistics are estimated once, at construction, with torch
 (mean / covariance / ``torch.linalg.eigh``, like the reference's ``utils.math.cov``, pca.py:52-76); the two dense
 ``(B, D) x (D, D)`` products of every pass run on the HIP GEMM kernel through ``torch.ops.tfep.masked_linear`` (no mask,
-no weight norm), which also gives them their gradient."""
+no weight norm), which also gives them their gradient.  The dtype of the pass is that of the buffers: float32 buffers
+serve float32 inputs on the float32 GEMM, float64 buffers (``.double()``, or a flow built from float64 data) serve float64
+inputs on the fp64-MFMA GEMM; an input of the other dtype is a TypeError."""
 import torch
 
 from ... import ops
@@ -53,16 +55,21 @@ class PCAWhitenedFlow(torch.nn.Module):
     def inverse(self, y):
         return self._pass(y, inverse=True)
 
+    def _dtype(self):
+        """The dtype of a pass: float64 when the whitening buffers are float64, float32 otherwise (buffers of any other
+        dtype are converted to float32, as before float64 was supported)."""
+        return torch.float64 if self.whitening_matrix.dtype == torch.float64 else torch.float32
+
     def _operands(self, device):
-        """float32 device copies for the kernels: ``(mean, W^T, B^T)`` (the GEMM computes ``x weight^T``), re-made when a
-        buffer is replaced or written (load_state_dict)."""
+        """Device copies for the kernels in the dtype of the pass: ``(mean, W^T, B^T)`` (the GEMM computes ``x weight^T``),
+        re-made when a buffer is replaced or written (load_state_dict)."""
         bufs = (self.mean, self.whitening_matrix, self.blackening_matrix)
-        key = tuple((b._version, b.data_ptr()) for b in bufs)
+        key = tuple((b._version, b.data_ptr(), b.dtype) for b in bufs)
         cached = self._dev.get(str(device))
         if cached is None or cached[0] != key:
-            f32 = dict(device=device, dtype=torch.float32)
-            cached = (key, self.mean.to(**f32).contiguous(), self.whitening_matrix.to(**f32).t().contiguous(),
-                      self.blackening_matrix.to(**f32).t().contiguous())
+            to = dict(device=device, dtype=self._dtype())
+            cached = (key, self.mean.to(**to).contiguous(), self.whitening_matrix.to(**to).t().contiguous(),
+                      self.blackening_matrix.to(**to).t().contiguous())
             self._dev[str(device)] = cached
         return cached[1:]
 
@@ -75,7 +82,7 @@ class PCAWhitenedFlow(torch.nn.Module):
         return torch.ops.tfep.masked_linear(x, b_t, None, None, None) + mean
 
     def _pass(self, x, inverse):
-        ops.check_device_tensor(x, 'x')
+        ops.check_device_tensor(x, 'x', self._dtype())
         if x.dim() != 2 or x.shape[1] != self.mean.shape[0]:
             raise RuntimeError(f'PCAWhitenedFlow: x has shape {tuple(x.shape)}, the whitening matrix was estimated for '
                                f'{self.mean.shape[0]} features')

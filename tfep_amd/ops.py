@@ -303,6 +303,189 @@ def flip_invariant_embedding_backward(x, embedded_indices, nonembedded_indices, 
     return gx, list(grads)
 
 
+# ----------------------------------------------------------------------------- frames of the Cartesian wrappers
+
+def _selection(subset, weights, origin, dim, dt):
+    """The centroid's selection as the frame kernels take it: ``(args, origin, keep)`` with ``args = (subset, n_subset,
+    weights)`` as pointers and a count, ``origin`` the checked flat origin (None if none was given); the tensors of ``keep``
+    live until the launch is queued."""
+    keep = []
+    n_sub = 0
+    if subset is not None:
+        subset = check_device_tensor(subset, 'subset', torch.int32).contiguous()
+        n_sub = subset.numel()
+        keep.append(subset)
+    if weights is not None:
+        weights = check_device_tensor(weights, 'weights', dt).reshape(-1).contiguous()
+        keep.append(weights)
+    if origin is not None:
+        origin = check_device_tensor(origin, 'origin', dt).reshape(-1).contiguous()
+        if origin.numel() != dim:
+            raise ValueError(f'origin has {origin.numel()} entries, dim is {dim}')
+        keep.append(origin)
+    return (ptr(subset), n_sub, ptr(weights)), origin, keep
+
+
+def _points(x, width, name):
+    if x.shape[1] % width != 0:
+        raise ValueError(f'{name} has {x.shape[1]} features, no multiple of {width}')
+    return x.shape[1] // width
+
+
+def _check_weights(weights, subset, n_points):
+    n_sel = n_points if subset is None else subset.numel()
+    if weights is not None and weights.numel() != n_sel:
+        raise ValueError(f'weights has {weights.numel()} entries for {n_sel} points of the centroid')
+
+
+def centroid_shift(x, subset, weights, origin, dim):
+    """``(shift, y)``: ``shift = origin - centroid`` as (B, dim) and ``y = x + shift`` on every point
+    (``tfep_centroid_shift``; reference flows/centroid.py).  ``subset``: int32 point indices or None (all points);
+    ``weights``: normalised, one per selected point, or None.  float64 tensors run on the float64 kernels; mixed float32 /
+    float64 arguments are a TypeError."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    B, dim = x.shape[0], int(dim)
+    n = _points(x, max(dim, 1), 'x')
+    _check_weights(weights, subset, n)
+    sel, origin, keep = _selection(subset, weights, origin, dim, dt)
+    shift = torch.empty(B, dim, dtype=dt, device=x.device)
+    y = torch.empty(B, x.shape[1], dtype=dt, device=x.device)
+    call('tfep_centroid_shift' + _sfx(dt), ptr(x), ldx, *sel, ptr(origin), dim, n, ptr(shift), ptr(y), max(x.shape[1], 1), B,
+         stream_of(x))
+    return shift, y
+
+
+def centroid_shift_backward(grad_y, grad_shift, subset, weights, dim):
+    """VJP of ``centroid_shift``: the cotangent of ``x``."""
+    dt = _dtype(grad_y)
+    gy, ldgy = rows(grad_y, 'grad_y', dt)
+    B, dim = gy.shape[0], int(dim)
+    n = _points(gy, max(dim, 1), 'grad_y')
+    _check_weights(weights, subset, n)
+    gs = None
+    if grad_shift is not None:
+        gs = check_device_tensor(grad_shift, 'grad_shift', dt).contiguous()
+        if tuple(gs.shape) != (B, dim):
+            raise ValueError(f'grad_shift must be ({B}, {dim}), got {tuple(gs.shape)}')
+    sel, _, keep = _selection(subset, weights, None, dim, dt)
+    gx = torch.empty(B, gy.shape[1], dtype=dt, device=gy.device)
+    call('tfep_centroid_shift_backward' + _sfx(dt), *sel, dim, n, ptr(gy), ldgy, ptr(gs), ptr(gx), max(gy.shape[1], 1), B,
+         stream_of(gy))
+    return gx
+
+
+def centroid_restore(y, shift, subset, weights, origin, fixed_point, fixed_entry, dim, translate_back):
+    """``y`` with the fixed point placed where it restores the centroid (skipped for a one-point subset), minus ``shift``
+    when ``translate_back`` (``tfep_centroid_restore``).  ``fixed_entry``: the fixed point's position in the selection;
+    ``fixed_point``: the point itself."""
+    dt = _dtype(y)
+    y, ldy = rows(y, 'y', dt)
+    B, dim = y.shape[0], int(dim)
+    n = _points(y, max(dim, 1), 'y')
+    _check_weights(weights, subset, n)
+    shift = check_device_tensor(shift, 'shift', dt).contiguous()
+    if tuple(shift.shape) != (B, dim):
+        raise ValueError(f'shift must be ({B}, {dim}), got {tuple(shift.shape)}')
+    sel, origin, keep = _selection(subset, weights, origin, dim, dt)
+    out = torch.empty(B, y.shape[1], dtype=dt, device=y.device)
+    call('tfep_centroid_restore' + _sfx(dt), ptr(y), ldy, ptr(shift), *sel, ptr(origin), int(fixed_point), int(fixed_entry),
+         dim, n, int(bool(translate_back)), ptr(out), max(y.shape[1], 1), B, stream_of(y))
+    return out
+
+
+def centroid_restore_backward(grad_out, subset, weights, fixed_point, fixed_entry, dim, translate_back):
+    """VJP of ``centroid_restore``: the cotangents ``(grad_y, grad_shift)``."""
+    dt = _dtype(grad_out)
+    g, ldg = rows(grad_out, 'grad_out', dt)
+    B, dim = g.shape[0], int(dim)
+    n = _points(g, max(dim, 1), 'grad_out')
+    _check_weights(weights, subset, n)
+    sel, _, keep = _selection(subset, weights, None, dim, dt)
+    gy = torch.empty(B, g.shape[1], dtype=dt, device=g.device)
+    gshift = torch.empty(B, dim, dtype=dt, device=g.device)
+    call('tfep_centroid_restore_backward' + _sfx(dt), *sel, int(fixed_point), int(fixed_entry), dim, n,
+         int(bool(translate_back)), ptr(g), ldg, ptr(gy), max(g.shape[1], 1), ptr(gshift), B, stream_of(g))
+    return gy, gshift
+
+
+def _frame(axis_point, plane_point, axis, plane_axis, normal, round_off):
+    return (int(axis_point), int(plane_point), int(axis), int(plane_axis), int(normal), int(bool(round_off)))
+
+
+def frame_orient(x, axis_point, plane_point, axis, plane_axis, normal, round_off):
+    """``(y, R)``: every point of a row rotated into the frame that puts point ``axis_point`` on ``axis`` and point
+    ``plane_point`` on the plane of ``axis`` and ``plane_axis`` (``tfep_frame_orient``; the rotation of
+    ``utils.geometry.reference_frame_rotation_matrix(..., project_on_positive_axis=False)``), and that rotation as (B, 9).
+    ``axis``, ``plane_axis``: 0..2; ``normal``: +-(1 + index of the third axis), signed like the plane normal.  ``round_off``
+    writes exact zeros into the three constrained coordinates."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    B, n = x.shape[0], _points(x, 3, 'x')
+    y = torch.empty(B, x.shape[1], dtype=dt, device=x.device)
+    rot = torch.empty(B, 9, dtype=dt, device=x.device)
+    call('tfep_frame_orient' + _sfx(dt), ptr(x), ldx, *_frame(axis_point, plane_point, axis, plane_axis, normal, round_off),
+         ptr(y), max(x.shape[1], 1), ptr(rot), n, B, stream_of(x))
+    return y, rot
+
+
+def frame_orient_backward(x, grad_y, grad_rot, axis_point, plane_point, axis, plane_axis, normal, round_off):
+    """VJP of ``frame_orient`` at ``x``: the cotangent of ``x`` from those of ``y`` and (optionally) of ``R``, including the
+    dependence of ``R`` on the two defining points."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    gy, ldgy = rows(grad_y, 'grad_y', dt)
+    B, n = x.shape[0], _points(x, 3, 'x')
+    if gy.shape != x.shape:
+        raise ValueError('frame_orient_backward: grad_y must have the shape of x')
+    gr = None
+    if grad_rot is not None:
+        gr = check_device_tensor(grad_rot, 'grad_rot', dt).contiguous()
+        if tuple(gr.shape) != (B, 9):
+            raise ValueError(f'grad_rot must be ({B}, 9), got {tuple(gr.shape)}')
+    gx = torch.empty(B, x.shape[1], dtype=dt, device=x.device)
+    call('tfep_frame_orient_backward' + _sfx(dt), ptr(x), ldx,
+         *_frame(axis_point, plane_point, axis, plane_axis, normal, round_off), ptr(gy), ldgy, ptr(gr), ptr(gx),
+         max(x.shape[1], 1), n, B, stream_of(x))
+    return gx
+
+
+def _rotation(rot, B, dt):
+    rot = check_device_tensor(rot, 'R', dt).contiguous()
+    if tuple(rot.shape) != (B, 9):
+        raise ValueError(f'R must be ({B}, 9), got {tuple(rot.shape)}')
+    return rot
+
+
+def frame_rotate(x, rot, transposed=False):
+    """``y_i = x_i R`` on the points (row vectors) of every row, ``x_i R^T`` with ``transposed`` (``tfep_frame_rotate``):
+    ``utils.geometry.batchwise_rotate(x, R, inverse=not transposed)``.  ``rot``: (B, 9)."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    B, n = x.shape[0], _points(x, 3, 'x')
+    rot = _rotation(rot, B, dt)
+    y = torch.empty(B, x.shape[1], dtype=dt, device=x.device)
+    call('tfep_frame_rotate' + _sfx(dt), ptr(x), ldx, ptr(rot), int(bool(transposed)), ptr(y), max(x.shape[1], 1), n, B,
+         stream_of(x))
+    return y
+
+
+def frame_rotate_backward(x, rot, grad_y, transposed=False):
+    """VJP of ``frame_rotate``: the cotangents ``(grad_x, grad_R)``."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    gy, ldgy = rows(grad_y, 'grad_y', dt)
+    B, n = x.shape[0], _points(x, 3, 'x')
+    if gy.shape != x.shape:
+        raise ValueError('frame_rotate_backward: grad_y must have the shape of x')
+    rot = _rotation(rot, B, dt)
+    gx = torch.empty(B, x.shape[1], dtype=dt, device=x.device)
+    grot = torch.empty(B, 9, dtype=dt, device=x.device)
+    call('tfep_frame_rotate_backward' + _sfx(dt), ptr(x), ldx, ptr(rot), int(bool(transposed)), ptr(gy), ldgy, ptr(gx),
+         max(x.shape[1], 1), ptr(grot), n, B, stream_of(x))
+    return gx, grot
+
+
 def gather_columns(src, idx):
     dt = _dtype(src)
     src, lds = rows(src, 'src', dt)

@@ -16,6 +16,9 @@ in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the re
                                                                      (QUATERNION_PRODUCT_OPS)
   tfep::flip_invariant_embedding / _backward                         reference embeddings/mafembed.py:174-348
                                                                      (FLIP_EMBEDDING_OPS)
+  tfep::centroid_shift / centroid_restore / frame_orient / frame_rotate, each with its _backward
+                                                                     reference flows/centroid.py, flows/oriented.py,
+                                                                     utils/geometry.py:239-411 (FRAME_OPS)
   tfep::masked_linear / masked_linear_backward                       reference masked.py:220-302, 351-404
   tfep::fused_output_transformer                                     masked.py:188-208 (last layer) + the transformer
   tfep::tfep_reduce                                                  loss.py:125-140, analysis/estimator.py:73-86
@@ -402,6 +405,137 @@ def _flip_bwd(ctx, grad_out):
 flip_invariant_embedding.register_autograd(_flip_bwd, setup_context=_flip_setup)
 
 
+# ============================================================================= frames of the Cartesian wrappers
+
+@custom_op('tfep::centroid_shift', mutates_args=(), device_types=_DEV)
+def centroid_shift(x: Tensor, subset: Optional[Tensor], weights: Optional[Tensor], origin: Tensor,
+                   dim: int) -> Tuple[Tensor, Tensor]:
+    """``(shift, y)`` of ``CenteredCentroidFlow``: ``shift = origin - centroid`` (B, dim), ``y = x + shift``.  ``subset``:
+    int32 point indices (distinct), ``weights``: normalised; float32 or float64, all alike (else TypeError)."""
+    return ops.centroid_shift(x, subset, weights, origin, dim)
+
+
+@custom_op('tfep::centroid_shift_backward', mutates_args=(), device_types=_DEV)
+def centroid_shift_backward(grad_y: Tensor, grad_shift: Tensor, subset: Optional[Tensor], weights: Optional[Tensor],
+                            dim: int) -> Tensor:
+    return ops.centroid_shift_backward(grad_y, grad_shift, subset, weights, dim)
+
+
+@custom_op('tfep::centroid_restore', mutates_args=(), device_types=_DEV)
+def centroid_restore(y: Tensor, shift: Tensor, subset: Optional[Tensor], weights: Optional[Tensor], origin: Tensor,
+                     fixed_point: int, fixed_entry: int, dim: int, translate_back: bool) -> Tensor:
+    """The fixed point placed so that the centroid is ``origin`` again, then ``- shift`` with ``translate_back``."""
+    return ops.centroid_restore(y, shift, subset, weights, origin, fixed_point, fixed_entry, dim, translate_back)
+
+
+@custom_op('tfep::centroid_restore_backward', mutates_args=(), device_types=_DEV)
+def centroid_restore_backward(grad_out: Tensor, subset: Optional[Tensor], weights: Optional[Tensor], fixed_point: int,
+                              fixed_entry: int, dim: int, translate_back: bool) -> Tuple[Tensor, Tensor]:
+    """``(grad_y, grad_shift)``."""
+    return ops.centroid_restore_backward(grad_out, subset, weights, fixed_point, fixed_entry, dim, translate_back)
+
+
+@custom_op('tfep::frame_orient', mutates_args=(), device_types=_DEV)
+def frame_orient(x: Tensor, axis_point: int, plane_point: int, axis: int, plane_axis: int, normal: int,
+                 round_off: bool) -> Tuple[Tensor, Tensor]:
+    """``(y, R)`` of ``OrientedFlow``: the row in its constrained frame and the rotation as (B, 9)."""
+    return ops.frame_orient(x, axis_point, plane_point, axis, plane_axis, normal, round_off)
+
+
+@custom_op('tfep::frame_orient_backward', mutates_args=(), device_types=_DEV)
+def frame_orient_backward(x: Tensor, grad_y: Tensor, grad_rot: Tensor, axis_point: int, plane_point: int, axis: int,
+                          plane_axis: int, normal: int, round_off: bool) -> Tensor:
+    return ops.frame_orient_backward(x, grad_y, grad_rot, axis_point, plane_point, axis, plane_axis, normal, round_off)
+
+
+@custom_op('tfep::frame_rotate', mutates_args=(), device_types=_DEV)
+def frame_rotate(x: Tensor, rot: Tensor, transposed: bool) -> Tensor:
+    """``y_i = x_i R`` (``transposed``: ``x_i R^T``) with the (B, 9) rotations of ``frame_orient``."""
+    return ops.frame_rotate(x, rot, transposed)
+
+
+@custom_op('tfep::frame_rotate_backward', mutates_args=(), device_types=_DEV)
+def frame_rotate_backward(x: Tensor, rot: Tensor, grad_y: Tensor, transposed: bool) -> Tuple[Tensor, Tensor]:
+    """``(grad_x, grad_R)``."""
+    return ops.frame_rotate_backward(x, rot, grad_y, transposed)
+
+
+centroid_shift.register_fake(lambda x, subset, weights, origin, dim: (x.new_empty((x.shape[0], dim)), x.new_empty(x.shape)))
+centroid_shift_backward.register_fake(lambda gy, gs, subset, weights, dim: gy.new_empty(gy.shape))
+centroid_restore.register_fake(lambda y, shift, *rest: y.new_empty(y.shape))
+centroid_restore_backward.register_fake(
+    lambda g, subset, weights, fixed_point, fixed_entry, dim, translate_back: (g.new_empty(g.shape),
+                                                                               g.new_empty((g.shape[0], dim))))
+frame_orient.register_fake(lambda x, *rest: (x.new_empty(x.shape), x.new_empty((x.shape[0], 9))))
+frame_orient_backward.register_fake(lambda x, *rest: x.new_empty(x.shape))
+frame_rotate.register_fake(lambda x, rot, transposed: x.new_empty(x.shape))
+frame_rotate_backward.register_fake(lambda x, rot, gy, transposed: (x.new_empty(x.shape), rot.new_empty(rot.shape)))
+
+
+def _meta(t):
+    return tuple(t.shape), t.dtype, t.device
+
+
+def _or_zeros(g, meta):
+    """An upstream gradient, zeros (filled by a kernel, see ``ops.zeros``) where autograd passes None."""
+    return ops.zeros(*meta[0], dtype=meta[1], device=meta[2]) if g is None else g
+
+
+def _centroid_shift_setup(ctx, inputs, output):
+    x, subset, weights, origin, dim = inputs
+    ctx.save_for_backward(subset, weights)
+    ctx.dim, ctx.like = dim, (_meta(output[0]), _meta(output[1]))
+
+
+def _centroid_shift_bwd(ctx, g_shift, g_y):
+    subset, weights = ctx.saved_tensors
+    shift, y = ctx.like
+    gx = torch.ops.tfep.centroid_shift_backward(_or_zeros(g_y, y), _or_zeros(g_shift, shift), subset, weights, ctx.dim)
+    return gx, None, None, None, None
+
+
+def _centroid_restore_setup(ctx, inputs, output):
+    y, shift, subset, weights, origin, fixed_point, fixed_entry, dim, translate_back = inputs
+    ctx.save_for_backward(subset, weights)
+    ctx.cfg = (fixed_point, fixed_entry, dim, translate_back)
+
+
+def _centroid_restore_bwd(ctx, g):
+    subset, weights = ctx.saved_tensors
+    gy, gshift = torch.ops.tfep.centroid_restore_backward(g, subset, weights, *ctx.cfg)
+    return gy, gshift, None, None, None, None, None, None, None
+
+
+def _frame_orient_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0])
+    ctx.cfg = tuple(inputs[1:])
+    ctx.like = (_meta(output[0]), _meta(output[1]))
+
+
+def _frame_orient_bwd(ctx, g_y, g_rot):
+    (x,) = ctx.saved_tensors
+    y, rot = ctx.like
+    gx = torch.ops.tfep.frame_orient_backward(x, _or_zeros(g_y, y), _or_zeros(g_rot, rot), *ctx.cfg)
+    return (gx, *([None] * 6))
+
+
+def _frame_rotate_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1])
+    ctx.transposed = inputs[2]
+
+
+def _frame_rotate_bwd(ctx, g):
+    x, rot = ctx.saved_tensors
+    gx, grot = torch.ops.tfep.frame_rotate_backward(x, rot, g, ctx.transposed)
+    return gx, grot, None
+
+
+centroid_shift.register_autograd(_centroid_shift_bwd, setup_context=_centroid_shift_setup)
+centroid_restore.register_autograd(_centroid_restore_bwd, setup_context=_centroid_restore_setup)
+frame_orient.register_autograd(_frame_orient_bwd, setup_context=_frame_orient_setup)
+frame_rotate.register_autograd(_frame_rotate_bwd, setup_context=_frame_rotate_setup)
+
+
 # ============================================================================= masked linear
 
 @custom_op('tfep::masked_linear', mutates_args=(), device_types=_DEV)
@@ -590,3 +724,5 @@ SOS_OPS = ('sos_forward', 'sos_backward')
 SYMMETRIZED_MOEBIUS_OPS = ('symmetrized_moebius_forward', 'symmetrized_moebius_inverse', 'symmetrized_moebius_backward')
 QUATERNION_PRODUCT_OPS = ('quaternion_product_forward', 'quaternion_product_inverse', 'quaternion_product_backward')
 FLIP_EMBEDDING_OPS = ('flip_invariant_embedding', 'flip_invariant_embedding_backward')
+FRAME_OPS = ('centroid_shift', 'centroid_restore', 'frame_orient', 'frame_rotate', 'centroid_shift_backward',
+             'centroid_restore_backward', 'frame_orient_backward', 'frame_rotate_backward')

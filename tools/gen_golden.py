@@ -1616,6 +1616,48 @@ def gen_flipembed():
     np.savez_compressed(os.path.join(OUT, 'flipembed.npz'), **out)
 
 
+# -----------------------------------------------------------------------------
+# float64 wrappers: what wrappers.npz lacks for the float64 tests of the wrapped flows
+# -----------------------------------------------------------------------------
+
+def gen_wrappers_f64():
+    """A NEW file, ``wrappers_f64.npz`` (``wrappers.npz`` is not touched): for every nested flow of
+    ``golden_util.wrapper_configs()``, built as ``gen_wrappers`` builds it and loaded with the float32-rounded state stored
+    in ``wrappers.npz``, the reference run in float64 on the same inputs: the gradients of ``y.sum() + ldj.sum()`` with
+    respect to the input and to every parameter (``wrappers.npz`` holds those of the cosine-weighted loss only), and ``y`` /
+    ``ldj`` again as a check that the state was loaded (they must equal the stored ``y_f64`` / ``ldj_f64``)."""
+    import types
+    sys.path.insert(0, os.path.join(os.path.dirname(OUT)))
+    import golden_util as gu
+    from tfep.nn.flows.centroid import CenteredCentroidFlow
+    from tfep.nn.flows.oriented import OrientedFlow
+    from tfep.nn.flows.partial import PartialFlow
+    ref_flows = types.SimpleNamespace(CenteredCentroidFlow=CenteredCentroidFlow, OrientedFlow=OrientedFlow,
+                                      PartialFlow=PartialFlow)
+    stored = np.load(os.path.join(OUT, 'wrappers.npz'))
+    out = {}
+    for name, cfg in gu.wrapper_configs().items():
+        n_in = gu.wrapper_n_inner(cfg)
+        with f64():
+            if cfg.get('spline'):
+                tr = NeuralSplineTransformer(x0=torch.full((n_in,), -8.0), xf=torch.full((n_in,), 8.0), n_bins=6)
+            else:
+                tr = AffineTransformer()
+            inner = MAF(degrees_in=generate_degrees(n_in, order='ascending'), transformer=tr, initialize_identity=False)
+            m = gu.build_wrapped(cfg, inner, ref_flows)
+            m.load_state_dict(to_double_sd({k[len(name) + 4:]: torch.from_numpy(stored[k]) for k in stored.files
+                                            if k.startswith(name + '/sd/')}), strict=False)
+            xg = torch.from_numpy(stored[f'{name}/x']).double().requires_grad_(True)
+            y, ldj = m(xg)
+            assert np.array_equal(npy(y), stored[f'{name}/y_f64']) and np.array_equal(npy(ldj), stored[f'{name}/ldj_f64']), name
+            (y.sum() + ldj.sum()).backward()
+            out[f'{name}/y_f64'], out[f'{name}/ldj_f64'] = npy(y), npy(ldj)
+            out[f'{name}/gsum_x_f64'] = npy(xg.grad)
+            for k, prm in m.named_parameters():
+                out[f'{name}/gsum_p/{k}'] = npy(prm.grad)
+    np.savez_compressed(os.path.join(OUT, 'wrappers_f64.npz'), **out)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
     if len(sys.argv) > 1:
