@@ -16,7 +16,6 @@ def rel(a, b):
 
 def test_masked_linear_function_gradients():
     """MaskedLinearFunc.backward semantics (masked.py:279-302) through tfep_masked_linear_gemm."""
-    from tfep_amd.nn.flows import _backward as bw
     from tfep_amd import ops
     g = gu.load('grads.npz')
     x, w, b, m, gy = (torch.from_numpy(g[f'ml/{k}']).float().cuda() for k in ('x', 'w', 'b', 'mask', 'gy'))
@@ -27,15 +26,15 @@ def test_masked_linear_function_gradients():
     wp = ops.masked_weight_prepare(w, None, m, n_rows_padded=npad, k_padded=kp)
     f32 = dict(dtype=torch.float32, device='cuda')
     # grad_input = g (W o M)
-    wt = bw._transpose(wp, npad, kp, torch.zeros(kp, npad, **f32))
+    wt = ops.transpose(wp, npad, kp, torch.zeros(kp, npad, **f32))
     gpad = ops.pad_columns(gy, npad)
-    gx = bw._gemm(gpad, wt, torch.empty(B, kp, **f32), B, kp, kp)
+    gx = ops.gemm(gpad, wt, torch.empty(B, kp, **f32), B, kp, kp)
     assert rel(gx[:, :K].cpu(), g['ml/gx']) < 1e-6
     # grad_weight = (g^T x) o M, grad_bias = column sums
     Bp = ops.round_up(B, tk)
-    gT = bw._transpose(gpad, B, npad, torch.zeros(npad, Bp, **f32))
-    xT = bw._transpose(ops.pad_columns(x, kp), B, kp, torch.zeros(kp, Bp, **f32))
-    gw = bw._gemm(gT, xT, torch.zeros(npad, kp, **f32), npad, kp, kp, accumulate=1)
+    gT = ops.transpose(gpad, B, npad, torch.zeros(npad, Bp, **f32))
+    xT = ops.transpose(ops.pad_columns(x, kp), B, kp, torch.zeros(kp, Bp, **f32))
+    gw = ops.gemm(gT, xT, torch.zeros(npad, kp, **f32), npad, kp, kp, accumulate=1)
     gw = gw[:N, :K] * m
     assert rel(gw.cpu(), g['ml/gw']) < 1e-6
 

@@ -144,9 +144,9 @@ def test_gemm_f64_helpers():
     g = torch.Generator().manual_seed(6)
     R, C = 70, 45
     a = torch.randn(R, C, generator=g, dtype=F64)
-    out = ops.transpose_f64(a.cuda(), R, C, ops.zeros(64, 96, dtype=F64, device='cuda'))
+    out = ops.transpose(a.cuda(), R, C, ops.zeros(64, 96, dtype=F64, device='cuda'))
     assert torch.equal(out[:C, :R].cpu(), a.T) and not out[C:].any() and not out[:, R:].any()
-    s = ops.column_sums_f64(a.cuda(), R, C)
+    s = ops.column_sums(a.cuda(), R, C)
     assert rel(s, a.sum(0).numpy()) <= 1e-14
 
 

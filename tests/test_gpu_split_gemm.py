@@ -622,13 +622,12 @@ def test_transpose_split_equals_split_of_the_transpose():
     """``tfep_transpose_split`` (one pass, the per-tensor scale taken from the split of the matrix itself) writes the bits
     of ``tfep_transpose`` followed by ``tfep_split_rows(per_tensor)``; ragged tiles, a padded row stride; misuse rejected."""
     from tfep_amd import _lib, ops
-    from tfep_amd.nn.flows._backward import _transpose
     torch.manual_seed(4)
     R, C, ld = 224, 333, 352                      # R a multiple of 32 (split rows); C and the strides not multiples of the 64 x 64 tile
     src = torch.zeros(R, ld, device='cuda')
     src[:, :C] = torch.randn(R, C, device='cuda') * torch.logspace(-3, 2, C, device='cuda')
     ws, w_inv = ops.split_rows(src[:, :C], ld, per_tensor=True)
-    wt = _transpose(src, R, C, torch.zeros(C, R, device='cuda'))
+    wt = ops.transpose(src, R, C, torch.zeros(C, R, device='cuda'))
     ref, ref_inv = ops.split_rows(wt, R, per_tensor=True)
     assert float(ref_inv[0]) == float(w_inv[0])
     out = torch.full((C, R), 7.0, device='cuda')
@@ -647,7 +646,7 @@ def test_transpose_split_equals_split_of_the_transpose():
     assert lib.tfep_column_sums_absmax(_lib.ptr(src), ld, Rv, C, _lib.ptr(sums), 1, _lib.ptr(cmax), None) == 0
     assert torch.equal(cmax, src[:Rv, :C].abs().amax(dim=0))
     assert torch.allclose(sums, src[:Rv, :C].double().sum(dim=0).float(), rtol=1e-6, atol=1e-6)
-    wt2 = _transpose(src, Rv, C, torch.zeros(C, Rp, device='cuda'))
+    wt2 = ops.transpose(src, Rv, C, torch.zeros(C, Rp, device='cuda'))
     ref2, ref2_inv = ops.split_rows(wt2, Rp)
     out2, inv2 = torch.full((C, Rp), 7.0, device='cuda'), torch.zeros(C, device='cuda')
     assert lib.tfep_transpose_split(_lib.ptr(src), ld, Rv, C, _lib.ptr(out2), Rp, Rp, 2, _lib.ptr(cmax), _lib.ptr(inv2), None) == 0

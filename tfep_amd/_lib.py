@@ -1,7 +1,8 @@
 """ctypes binding of libtfep_hip.so (the C ABI declared in include/tfep_hip.h).
 
-There is NO CPU fallback: if the library is missing or a tensor is not a float32
-HIP tensor, calls raise.  ``import torch`` happens first so that the library binds
+There is NO CPU fallback: if the library is missing or a tensor is not a HIP tensor
+of the dtype its entry point takes (float32, or float64 for the ``_f64`` entry points),
+calls raise.  ``import torch`` happens first so that the library binds
 to the HIP runtime PyTorch-ROCm already loaded (same ``libamdhip64.so.7`` soname),
 which is what makes ``tensor.data_ptr()`` and the current stream valid on our side.
 """
@@ -130,7 +131,6 @@ _SIGNATURES = {
     'tfep_last_error': (c_char_p, []),
     'tfep_masked_weight_prepare': (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int64, _P]),
     'tfep_masked_weight_prepare_prefix': (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, c_int, c_int64, _P]),
-    'tfep_mask_k_ranges': (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     'tfep_masked_linear_forward': (c_int, [_P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_int64,
                                            c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'tfep_masked_linear_narrow_tile_n': (c_int, []),
@@ -139,11 +139,6 @@ _SIGNATURES = {
     'tfep_split_half_wide_tile_n': (c_int, []),
     'tfep_masked_linear_tile_k': (c_int, []),
     'tfep_masked_linear_tile_m': (c_int, []),
-    'tfep_affine_forward': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
-    'tfep_affine_inverse': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
-    'tfep_sos_forward': (c_int, [_P, c_int64, _P, ParamLayout, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
-    'tfep_sos_backward': (c_int, [_P, c_int64, _P, ParamLayout, c_int, _P, c_int64, _P, ParamLayout, _P, c_int64,
-                                  c_int, c_int, _P]),
     'tfep_volume_preserving_shift': (c_int, [_P, c_int64, _P, c_int64, _P, c_float, c_float, c_int,
                                              _P, c_int64, c_int, c_int, _P]),
     'tfep_spline_n_parameters_per_feature': (c_int, [POINTER(SplineDesc)]),
@@ -153,26 +148,10 @@ _SIGNATURES = {
                                     _P, c_int, c_int, c_int, _P]),
     'tfep_moebius_forward': (c_int, [_P, c_int64, _P, c_int64, c_int, c_float, c_int, c_int,
                                      _P, c_int64, _P, c_int, c_int, c_int, _P]),
-    'tfep_symmetrized_moebius': (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, c_int, c_int,
-                                         c_int, _P]),
-    'tfep_symmetrized_moebius_backward': (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, _P,
-                                                  c_int64, _P, c_int64, c_int, c_int, _P]),
-    'tfep_symmetrized_moebius_f64': (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, c_int, c_int,
-                                             c_int, _P]),
-    'tfep_symmetrized_moebius_backward_f64': (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, _P,
-                                                      c_int64, _P, c_int64, c_int, c_int, _P]),
-    'tfep_quaternion_product': (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
-    'tfep_quaternion_product_backward': (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int64, _P, c_int64,
-                                                 c_int, c_int, _P]),
-    'tfep_quaternion_product_f64': (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
-    'tfep_quaternion_product_backward_f64': (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int64, _P, c_int64,
-                                                     c_int, c_int, _P]),
     'tfep_moebius_forward_split_out': (c_int, [_P, c_int64, _P, c_int64, c_float, _P, c_int64, _P, c_int, _P, c_int64, _P,
                                                c_int, c_int, _P]),
     'tfep_periodic_embedding': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_float, c_float,
                                         _P, c_int64, c_int, _P]),
-    'tfep_gather_columns': (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, _P]),
-    'tfep_scatter_columns': (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, _P]),
     'tfep_fused_tile_features': (c_int, []),
     'tfep_fused_supported': (c_int, [c_int, POINTER(SplineDesc)]),
     'tfep_fused_tile_columns': (c_int, [c_int, POINTER(SplineDesc)]),
@@ -211,20 +190,15 @@ _SIGNATURES = {
     'tfep_diag_maf_layer_cycles': (c_int, [_P]),
     'tfep_diag_mfma_peak': (c_int, [_P, c_int, c_int, _P]),
     'tfep_masked_linear_gemm': (c_int, [POINTER(GemmDesc), _P]),
-    'tfep_transpose': (c_int, [_P, c_int64, c_int, c_int, _P, c_int64, _P]),
     'tfep_transpose_split': (c_int, [_P, c_int64, c_int, c_int, _P, c_int64, c_int, c_int, _P, _P, _P]),
     'tfep_transpose_split_rows': (c_int, [_P, c_int64, c_int, c_int, _P, c_int64, _P]),
     'tfep_column_sums_absmax': (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P]),
-    'tfep_column_sums': (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P]),
     'tfep_add_inplace': (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, _P]),
-    'tfep_affine_backward': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, _P, ParamLayout, _P, c_int64,
-                                     c_int, c_int, _P]),
     'tfep_spline_backward': (c_int, [_P, c_int64, _P, ParamLayout, POINTER(SplineDesc), _P, c_int64, _P, _P,
                                      ParamLayout, _P, c_int64, c_int, c_int, _P]),
     'tfep_moebius_backward': (c_int, [_P, c_int64, _P, c_int64, c_int, c_float, c_int, c_int, _P, c_int64, _P,
                                       _P, c_int64, _P, c_int64, c_int, c_int, _P]),
     'tfep_copy_2d': (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, _P]),
-    'tfep_weight_norm_backward': (c_int, [_P, c_int64, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     'tfep_weight_norm_backward_prefix': (c_int, [_P, c_int64, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     'tfep_periodic_embedding_backward': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_float, c_float, _P, c_int64,
                                                  _P, c_int64, c_int, _P]),
@@ -247,20 +221,9 @@ _SIGNATURES = {
     'tfep_segment_sum': (c_int, [_P, _P, c_int64, c_int, c_int64, _P, _P]),
     'tfep_ode_axpy': (c_int, [_P, POINTER(c_void_p), POINTER(c_float), c_int, c_int64, _P, _P]),
     'tfep_masked_weight_prepare_f64': (c_int, [_P, _P, _P, c_int, c_int, _P, _P, c_int, _P, c_int, c_int64, _P]),
-    'tfep_mask_k_ranges_f64': (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     'tfep_masked_linear_gemm_f64': (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int, _P, c_int64, c_int, c_int, c_int,
                                             c_int, c_int, c_int, _P, c_int64, _P]),
-    'tfep_transpose_f64': (c_int, [_P, c_int64, c_int, c_int, _P, c_int64, _P]),
-    'tfep_column_sums_f64': (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P]),
-    'tfep_weight_norm_backward_f64': (c_int, [_P, c_int64, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     'tfep_diag_mfma_f64_peak': (c_int, [_P, c_int, c_int, _P]),
-    'tfep_affine_forward_f64': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
-    'tfep_affine_inverse_f64': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
-    'tfep_affine_backward_f64': (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, _P, ParamLayout, _P, c_int64,
-                                         c_int, c_int, _P]),
-    'tfep_sos_forward_f64': (c_int, [_P, c_int64, _P, ParamLayout, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
-    'tfep_sos_backward_f64': (c_int, [_P, c_int64, _P, ParamLayout, c_int, _P, c_int64, _P, ParamLayout, _P, c_int64,
-                                      c_int, c_int, _P]),
     'tfep_volume_preserving_shift_f64': (c_int, [_P, c_int64, _P, c_int64, _P, c_double, c_double, c_int,
                                                  _P, c_int64, c_int, c_int, _P]),
     'tfep_spline_n_parameters_per_feature_f64': (c_int, [POINTER(SplineDescF64)]),
@@ -276,11 +239,33 @@ _SIGNATURES = {
                                             _P, c_int64, c_int, _P]),
     'tfep_periodic_embedding_backward_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double, _P, c_int64,
                                                      _P, c_int64, c_int, _P]),
-    'tfep_gather_columns_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, _P]),
-    'tfep_scatter_columns_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, _P]),
     'tfep_tfep_reduce_f64': (c_int, [_P, _P, _P, _P, _P, c_double, c_int, c_int, _P, _P, _P]),
     'tfep_flip_invariant_embedding_backward_workspace_bytes': (c_int64, [c_int, c_int, c_int, c_int, c_int]),
 }
+# the entry points whose float32 and float64 forms share one signature
+for _s in ('', '_f64'):
+    _SIGNATURES.update({
+        'tfep_transpose' + _s: (c_int, [_P, c_int64, c_int, c_int, _P, c_int64, _P]),
+        'tfep_column_sums' + _s: (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P]),
+        'tfep_weight_norm_backward' + _s: (c_int, [_P, c_int64, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+        'tfep_mask_k_ranges' + _s: (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+        'tfep_gather_columns' + _s: (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, _P]),
+        'tfep_scatter_columns' + _s: (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, _P]),
+        'tfep_affine_forward' + _s: (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+        'tfep_affine_inverse' + _s: (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+        'tfep_affine_backward' + _s: (c_int, [_P, c_int64, _P, ParamLayout, _P, c_int64, _P, _P, ParamLayout, _P, c_int64,
+                                              c_int, c_int, _P]),
+        'tfep_sos_forward' + _s: (c_int, [_P, c_int64, _P, ParamLayout, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+        'tfep_sos_backward' + _s: (c_int, [_P, c_int64, _P, ParamLayout, c_int, _P, c_int64, _P, ParamLayout, _P, c_int64,
+                                           c_int, c_int, _P]),
+        'tfep_symmetrized_moebius' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, c_int, c_int,
+                                                  c_int, _P]),
+        'tfep_symmetrized_moebius_backward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, _P,
+                                                           c_int64, _P, c_int64, c_int, c_int, _P]),
+        'tfep_quaternion_product' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
+        'tfep_quaternion_product_backward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int64, _P, c_int64,
+                                                          c_int, c_int, _P]),
+    })
 # x, ldx, the two index tables, (vector_dim, hidden, emb_dim), the eight parameters; then out, ldo -- or gout, ldg, gx,
 # ldgx, the eight gradients, accumulate, workspace --; B, stream
 _FLIP_HEAD = [_P, c_int64, _P, c_int, _P, c_int, c_int, c_int, c_int] + [_P] * 8
@@ -379,7 +364,7 @@ _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None) or (
 
 
 def check_device_tensor(t, name, dtype=torch.float32):
-    """The kernels take float32 HIP tensors only; anything else is an error (no fallback)."""
+    """The kernels take HIP tensors of one dtype (float32, or ``dtype``); anything else is an error (no fallback)."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f'{name} must be a torch.Tensor')
     if not t.is_cuda:

@@ -365,15 +365,13 @@ class MADE(Conditioner):
         return plan
 
     def _pack_layer(self, plan, li, lin, row_of_out=None, n_rows=None):
-        """Weight norm + mask + permutation + padding of layer ``li`` (every forward)."""
+        """Weight norm + mask + permutation + padding of layer ``li`` (every forward), in the layer's dtype."""
         row_of_out = plan['row_of_out'][li] if row_of_out is None else row_of_out
         n_rows = plan['n_pad'][li] if n_rows is None else n_rows
         if lin.has_weight_norm:
             v, g = lin.weight_v.detach(), lin.weight_g.detach()
         else:
             v, g = lin._parameters['weight'].detach(), None
-        if v.dtype == torch.float64:
-            return self._pack_layer_f64(plan, li, lin, v, g, row_of_out, n_rows)
         # one buffer per (layer, row order): zeroed once -- the kernel rewrites every mapped entry and never touches the
         # padding, so later packs skip the clear (a 4.5 GB write for the cfg2 output layer)
         key = ('w', li, n_rows, None if row_of_out is None else row_of_out.data_ptr())
@@ -384,33 +382,13 @@ class MADE(Conditioner):
         entry = plan.get(key)
         if entry is None:
             # (the entry keeps row_of_out alive: its address, part of the key, cannot be recycled for another mapping)
-            entry = plan[key] = (ops.zeros(n_rows, plan['k_pad'][li], dtype=torch.float32, device=v.device), row_of_out)
+            entry = plan[key] = (ops.zeros(n_rows, plan['k_pad'][li], dtype=v.dtype, device=v.device), row_of_out)
         buf = entry[0]
+        # (the prefix-mask form is float32-only: a float64 layer's mask is read)
+        prefix = {} if v.dtype == torch.float64 else dict(col_cut=self._mask_prefix_cuts(plan, li, lin),
+                                                          in_of_col=plan['in_of_col'][li])
         ops.masked_weight_prepare(v, g, lin.mask, row_of_out, plan['col_of_in'][li], n_rows, plan['k_pad'][li], out=buf,
-                                  col_cut=self._mask_prefix_cuts(plan, li, lin), clear=False, in_of_col=plan['in_of_col'][li])
-        bias = ops.zeros(1, n_rows, dtype=torch.float32, device=v.device)
-        if row_of_out is None:
-            bias[0, :lin.out_features] = lin.bias.detach()
-        else:
-            ops.scatter_columns(lin.bias.detach()[None, :], row_of_out, bias)
-        if keep:
-            plan[ckey] = (buf, bias[0])
-        return buf, bias[0]
-
-    def _pack_layer_f64(self, plan, li, lin, v, g, row_of_out, n_rows):
-        """``_pack_layer`` of a float64 layer: ``masked_weight_prepare_f64`` with the plan's permutations into a float64
-        buffer (no prefix-mask form: the mask is read)."""
-        key = ('w', li, n_rows, None if row_of_out is None else row_of_out.data_ptr())
-        ckey = ('packed',) + key[1:]
-        keep = self._keep_packed(plan)
-        if keep and ckey in plan:
-            return plan[ckey]
-        entry = plan.get(key)
-        if entry is None:
-            entry = plan[key] = (ops.zeros(n_rows, plan['k_pad'][li], dtype=torch.float64, device=v.device), row_of_out)
-        buf = entry[0]
-        ops.masked_weight_prepare_f64(v, g, lin.mask, row_of_out, plan['col_of_in'][li], n_rows, plan['k_pad'][li], out=buf,
-                                      clear=False)
+                                  clear=False, **prefix)
         bias = self._pack_bias(lin, row_of_out, n_rows)
         if keep:
             plan[ckey] = (buf, bias)

@@ -463,45 +463,6 @@ class UnsupportedBackward(torch.autograd.Function):
             'transformer is neither.')
 
 
-def _gemm(x, w, y, B, N, n_rows_w, bias=None, k_ranges=None, act=0, accumulate=0, elu_grad_of=None, tile_live=None,
-          split=False, w_split=None, x_split=None, tile_list=None, tile_n=0):
-    """``split``: run on split-f16 operands (x converted here with one scale per row; ``w_split`` / ``x_split`` = already
-    converted ``(rows, inv_scale)`` of w / x, else w is converted here with one scale for the matrix)."""
-    d = _lib.GemmDesc()
-    if split:
-        xs, x_inv = x_split if x_split is not None else ops.split_rows(x, x.shape[1])
-        ws, w_inv = w_split if w_split is not None else ops.split_rows(w, w.shape[1], per_tensor=True)
-        d.split, d.x_inv_scale, d.w_inv_scale = 1, x_inv.data_ptr(), w_inv.data_ptr()
-        x, w = xs, ws
-    d.x, d.ldx = x.data_ptr(), x.shape[1]
-    d.w, d.ldw = w.data_ptr(), w.shape[1]
-    d.bias = bias.data_ptr() if bias is not None else None
-    d.k_ranges = k_ranges.data_ptr() if k_ranges is not None else None
-    d.tile_order, d.col_map = None, None
-    d.y, d.ldy = y.data_ptr(), y.shape[1]
-    d.B, d.N, d.n_rows_w, d.k_padded, d.act, d.accumulate = B, N, n_rows_w, w.shape[1], act, accumulate
-    if elu_grad_of is not None:
-        d.elu_grad_of, d.ld_elu_grad_of = elu_grad_of.data_ptr(), elu_grad_of.shape[1]
-    d.tile_live = tile_live.data_ptr() if tile_live is not None else None
-    if tile_list is not None:
-        d.tile_list, d.n_tile_list = tile_list.data_ptr(), tile_list.shape[0]
-    d.tile_n = tile_n                  # (0 = the default 256 columns; the tables above count tiles of this width)
-    if not split and ops.few_wide_tiles(B, N):
-        # a cfg1-sized product is one or two 256 x 256 tiles: one workgroup walks the whole k range while 255 CUs idle
-        # (130 us for a 224 x 224 x 1024 grad_weight).  The 32-column tile spreads it over the columns; the mask tables are
-        # per 256-column tile and only save work (masked weights are zeros, masked gradients are dropped later): dense.
-        d.tile_n, d.k_ranges, d.tile_live = ops.narrow_tile_n(), None, None
-        d.tile_list, d.n_tile_list = None, 0
-    _lib.call('tfep_masked_linear_gemm', ctypes.byref(d), _lib.stream_of(x))
-    return y
-
-
-def _transpose(src, rows, cols, out):
-    """out (cols_pad x rows_pad, zero filled by the caller) <- src[:rows, :cols]^T."""
-    _lib.call('tfep_transpose', _lib.ptr(src), src.shape[1], rows, cols, _lib.ptr(out), out.shape[1], _lib.stream_of(src))
-    return out
-
-
 def _backward_plan(layer, device):
     """Host-side plan of the backward GEMMs (built once per device).
 
@@ -633,7 +594,7 @@ def _weights(layer, dev):
         W.append(w)
         bias.append(b)
         if not split:
-            WT.append(_transpose(w, n_pad[l], k_pad[l], ops.zeros(k_pad[l], n_pad[l], **f32)))
+            WT.append(ops.transpose(w, n_pad[l], k_pad[l], ops.zeros(k_pad[l], n_pad[l], **f32)))
             Ws.append(None)
             WTs.append(None)
             continue
@@ -659,13 +620,13 @@ def _conditioner_forward(layer, wts, cin, Bc):
     split = wts['split']
     h = [ops.pad_columns(cin, k_pad[0])]
     for l in range(L):
-        h.append(_gemm(h[-1], wts['W'][l], torch.empty(Bc, n_pad[l], **f32), Bc, n_pad[l], n_pad[l], bias=wts['bias'][l],
-                       k_ranges=mplan['k_ranges'][l], act=1, split=split, w_split=wts['Ws'][l]))
+        h.append(ops.gemm(h[-1], wts['W'][l], torch.empty(Bc, n_pad[l], **f32), Bc, n_pad[l], n_pad[l], bias=wts['bias'][l],
+                          k_ranges=mplan['k_ranges'][l], act=1, split=split, w_split=wts['Ws'][l]))
     theta = torch.empty(Bc, n_out_pad, **f32)
     wide = bplan['wide'] if split else None
-    _gemm(h[-1], wts['W'][L], theta, Bc, n_out_pad, n_pad[L], bias=wts['bias'][L],
-          k_ranges=wide['k_ranges_out'] if wide else bplan['k_ranges'][L], tile_n=wide['tile_n'] if wide else 0,
-          split=split, w_split=wts['Ws'][L])
+    ops.gemm(h[-1], wts['W'][L], theta, Bc, n_out_pad, n_pad[L], bias=wts['bias'][L],
+             k_ranges=wide['k_ranges_out'] if wide else bplan['k_ranges'][L], tile_n=wide['tile_n'] if wide else 0,
+             split=split, w_split=wts['Ws'][L])
     return h, theta
 
 
@@ -751,8 +712,8 @@ def forward_saving(layer, x):
         f32 = dict(dtype=torch.float32, device=dev)
         h = [ops.pad_columns(cin, k_pad[0])]
         for l in range(L):
-            h.append(_gemm(h[-1], wts['W'][l], torch.empty(B, n_pad[l], **f32), B, n_pad[l], n_pad[l], bias=wts['bias'][l],
-                           k_ranges=mplan['k_ranges'][l], act=1, split=True, w_split=wts['Ws'][l]))
+            h.append(ops.gemm(h[-1], wts['W'][l], torch.empty(B, n_pad[l], **f32), B, n_pad[l], n_pad[l], bias=wts['bias'][l],
+                              k_ranges=mplan['k_ranges'][l], act=1, split=True, w_split=wts['Ws'][l]))
         hs, h_inv = ops.split_rows(h[-1], h[-1].shape[1])
         theta = torch.empty(B, n_out_pad, **f32)
         if n_out_pad > n_out:
@@ -888,23 +849,23 @@ def layer_backward(layer, x, gy, gldj, saved=None, need_gx=True):
                           None, _lib.ptr(hT_inv), stream)
                 # grad_weight (packed) += g^T h   [rows n, cols k], masked tiles skipped
                 tbl = bplan['wide'] or bplan
-                _gemm(gTs, hTs, gW[l], n_pad[l], k_pad[l], k_pad[l], accumulate=int(b0 > 0), tile_live=tbl['live'][l], split=True,
-                      x_split=(gTs, gT_inv), w_split=(hTs, hT_inv), tile_list=tbl['live_list'][l], tile_n=tbl.get('tile_n', 0))
+                ops.gemm(gTs, hTs, gW[l], n_pad[l], k_pad[l], k_pad[l], accumulate=int(b0 > 0), tile_live=tbl['live'][l], split=True,
+                         x_split=(gTs, gT_inv), w_split=(hTs, hT_inv), tile_list=tbl['live_list'][l], tile_n=tbl.get('tile_n', 0))
                 del gTs, hTs, cmax
             else:
                 _lib.call('tfep_column_sums', _lib.ptr(g), g.shape[1], Bc, n_pad[l], _lib.ptr(gb[l]), 1, stream)
-                gT = _transpose(g, Bc, n_pad[l], ops.zeros(n_pad[l], Bc_pad, **f32))
-                hT = _transpose(h[l], Bc, k_pad[l], ops.zeros(k_pad[l], Bc_pad, **f32))
-                _gemm(gT, hT, gW[l], n_pad[l], k_pad[l], k_pad[l], accumulate=int(b0 > 0), tile_live=bplan['live'][l],
-                      tile_list=bplan['live_list'][l])
+                gT = ops.transpose(g, Bc, n_pad[l], ops.zeros(n_pad[l], Bc_pad, **f32))
+                hT = ops.transpose(h[l], Bc, k_pad[l], ops.zeros(k_pad[l], Bc_pad, **f32))
+                ops.gemm(gT, hT, gW[l], n_pad[l], k_pad[l], k_pad[l], accumulate=int(b0 > 0), tile_live=bplan['live'][l],
+                         tile_list=bplan['live_list'][l])
                 del gT, hT
             # grad_input = g W  (x ELU'(h) for hidden inputs)
             if l == 0 and not need_gx and not emb_params:
                 break                                   # nothing upstream wants the gradient of the conditioner's input
             gin = torch.empty(Bc, k_pad[l], **f32)
             tbl = (bplan['wide'] if split else None) or bplan
-            _gemm(g, WT[l], gin, Bc, k_pad[l], k_pad[l], k_ranges=tbl['dx_ranges'][l],
-                  elu_grad_of=h[l] if l > 0 else None, split=split, w_split=WTs[l], tile_n=tbl.get('tile_n', 0))
+            ops.gemm(g, WT[l], gin, Bc, k_pad[l], k_pad[l], k_ranges=tbl['dx_ranges'][l],
+                     elu_grad_of=h[l] if l > 0 else None, split=split, w_split=WTs[l], tile_n=tbl.get('tile_n', 0))
             g = gin
 
         # ---- gradient w.r.t. the layer input: through the conditioner + direct

@@ -1944,8 +1944,8 @@ class AutoregressiveFlow(torch.nn.Module):
         bias = []
         for l, lin in enumerate(lins):             # packed on every call, like the reference's pre-hook
             v, g = (lin.weight_v.detach(), lin.weight_g.detach()) if lin.has_weight_norm else (lin._parameters['weight'].detach(), None)
-            ops.masked_weight_prepare_f64(v, g, lin.mask, dp['rows'][l], dp['cols'][l], dp['n_rows'][l], dp['k_pad'][l],
-                                          out=dp['w'][l], clear=False)
+            ops.masked_weight_prepare(v, g, lin.mask, dp['rows'][l], dp['cols'][l], dp['n_rows'][l], dp['k_pad'][l],
+                                      out=dp['w'][l], clear=False)
             bias.append(made._pack_bias(lin, dp['rows'][l], dp['n_rows'][l]))
         a = [ops.zeros(B, dp['k_pad'][l], **f64) for l in range(L + 1)]
         cols_f, pos_f = dp['fixed_plain']

@@ -55,69 +55,23 @@ class MaskedLinearFunc(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, weight, bias=None, mask=None, weight_g=None):
         x2 = input.detach().reshape(-1, input.shape[-1])
-        n_out, k = weight.shape
-        tm, tn, tk = ops.tile_sizes()
-        k_pad, n_pad = ops.round_up(k, tk), ops.round_up(n_out, tk)
-        if weight.dtype == torch.float64:        # float64 parameters: the fp64-MFMA GEMM, float64 input required
-            w = ops.masked_weight_prepare_f64(weight.detach(), None if weight_g is None else weight_g.detach(), mask,
-                                              n_rows_padded=n_pad, k_padded=k_pad)
-            xp = ops.pad_columns(x2, k_pad, torch.float64)
-            y = ops.masked_linear_f64(xp, w, None if bias is None else bias.detach(), n_out,
-                                      k_ranges=ops.masked_k_ranges_f64(mask, n_pad, k_pad))
-            ctx.save_for_backward(xp, w, weight, mask, weight_g)
-            ctx.has_bias = bias is not None
-            ctx.in_shape = input.shape
-            return y.reshape(*input.shape[:-1], n_out)
-        w = ops.masked_weight_prepare(weight.detach(), None if weight_g is None else weight_g.detach(), mask,
-                                      n_rows_padded=n_pad, k_padded=k_pad)
-        xp = ops.pad_columns(x2, k_pad)
-        y = ops.masked_linear_packed(xp, w, None if bias is None else bias.detach(), n_out)
+        # (float64 parameters take the fp64-MFMA GEMM and a float64 input)
+        y, xp, w = ops.masked_linear_layer(x2, weight.detach(), None if weight_g is None else weight_g.detach(), mask,
+                                           None if bias is None else bias.detach())
         ctx.save_for_backward(xp, w, weight, mask, weight_g)
         ctx.has_bias = bias is not None
         ctx.in_shape = input.shape
-        return y.reshape(*input.shape[:-1], n_out)
+        return y.reshape(*input.shape[:-1], weight.shape[0])
 
     @staticmethod
     def backward(ctx, grad_output):
-        from .flows._backward import _gemm, _transpose
-        from .. import _lib
         xp, w, weight, mask, weight_g = ctx.saved_tensors
         n_out, k = weight.shape
-        n_pad, k_pad = w.shape
-        if weight.dtype == torch.float64:
-            want_w = ctx.needs_input_grad[1] or (weight_g is not None and ctx.needs_input_grad[4])
-            gi, gv, gg, gb = ops.masked_linear_backward_f64(
-                ops._f64(grad_output, 'grad_output'), xp, w, weight.detach(),
-                None if weight_g is None else weight_g.detach(), mask, n_out, k, want_input=ctx.needs_input_grad[0],
-                want_weight=want_w, want_bias=ctx.has_bias and ctx.needs_input_grad[2])
-            return (None if gi is None else gi.reshape(ctx.in_shape)), gv, gb, None, gg
-        tm, tn, tk = ops.tile_sizes()
-        f32 = dict(dtype=torch.float32, device=xp.device)
-        g2 = grad_output.reshape(-1, n_out).float()
-        B = g2.shape[0]
-        gp = ops.pad_columns(g2, n_pad)
-        grad_input = grad_weight = grad_bias = grad_g = None
-        if ctx.needs_input_grad[0]:
-            wt = _transpose(w, n_pad, k_pad, torch.zeros(k_pad, n_pad, **f32))
-            gx = _gemm(gp, wt, torch.empty(B, k_pad, **f32), B, k_pad, k_pad)
-            grad_input = gx[:, :k].reshape(ctx.in_shape)
-        if ctx.needs_input_grad[1] or (weight_g is not None and ctx.needs_input_grad[4]):
-            Bp = ops.round_up(B, tk)
-            gT = _transpose(gp, B, n_pad, torch.zeros(n_pad, Bp, **f32))
-            xT = _transpose(xp, B, k_pad, torch.zeros(k_pad, Bp, **f32))
-            gw = _gemm(gT, xT, torch.zeros(n_pad, k_pad, **f32), n_pad, k_pad, k_pad, accumulate=1)
-            grad_weight = torch.empty_like(weight)
-            if weight_g is not None:
-                grad_g = torch.empty_like(weight_g)
-            w_c = weight.detach().contiguous()
-            g_c = None if weight_g is None else weight_g.detach().contiguous()
-            m_c = None if mask is None else mask.contiguous()
-            _lib.call('tfep_weight_norm_backward', _lib.ptr(gw), k_pad, _lib.ptr(w_c), _lib.ptr(g_c), _lib.ptr(m_c), n_out, k, None, None,
-                      _lib.ptr(grad_weight), _lib.ptr(grad_g), _lib.stream_of(xp))
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            grad_bias = torch.empty(n_out, **f32)
-            _lib.call('tfep_column_sums', _lib.ptr(gp), n_pad, B, n_out, _lib.ptr(grad_bias), 0, _lib.stream_of(xp))
-        return grad_input, grad_weight, grad_bias, None, grad_g
+        want_w = ctx.needs_input_grad[1] or (weight_g is not None and ctx.needs_input_grad[4])
+        gi, gv, gg, gb = ops.masked_linear_layer_backward(
+            grad_output, xp, w, weight.detach(), None if weight_g is None else weight_g.detach(), mask, n_out, k,
+            want_input=ctx.needs_input_grad[0], want_weight=want_w, want_bias=ctx.has_bias and ctx.needs_input_grad[2])
+        return (None if gi is None else gi.reshape(ctx.in_shape)), gv, gb, None, gg
 
 
 def masked_linear(input, weight, bias=None, mask=None):

@@ -1,8 +1,9 @@
-"""Tensor-level wrappers of the C ABI (one function per entry point of include/tfep_hip.h).
+"""Tensor-level wrappers of the C ABI of include/tfep_hip.h.
 
-Every function takes float32 HIP tensors, launches on the current HIP stream of the
-tensor's device and returns fresh output tensors (inputs are never modified, like the
-reference: flows/autoregressive.py:165-166).  No autograd, no CPU path.
+Every function takes float32 HIP tensors or, where the entry point has a ``_f64`` twin, float64 ones (the dtype of its first
+tensor picks the kernels, ``_dtype`` / ``_sfx``; mixed dtypes are a TypeError), launches on the current HIP stream of the
+tensor's device and returns fresh output tensors (inputs are never modified, like the reference:
+flows/autoregressive.py:165-166).  No autograd, no CPU path.
 """
 import ctypes
 import os
@@ -21,6 +22,24 @@ def _dtype(x):
 
 def _sfx(dtype):
     return '_f64' if dtype == torch.float64 else ''
+
+
+_F64 = torch.float64
+
+
+def _f64(t, name):
+    return None if t is None else check_device_tensor(t, name, _F64)
+
+
+def _mask(mask, dtype):
+    """The mask as the kernels of ``dtype`` read it.  float64: any floating-point mask, converted (a 0 / 1 array is exact in
+    any float type: a float32 mask on a float64 layer is fine); float32: the mask as it is."""
+    if mask is None:
+        return None
+    if dtype == _F64:
+        check_device_tensor(mask, 'mask', mask.dtype if mask.is_floating_point() else _F64)
+        return mask.to(_F64).contiguous()
+    return mask.contiguous()
 
 
 def _ldj_out(log_det_J, B, like, dtype=torch.float32):
@@ -541,24 +560,28 @@ def masked_weight_prepare(weight_v, weight_g=None, mask=None, row_of_out=None, c
     """Effective masked weight, permuted + zero padded (reference masked.py:369-371, :433-439, :270).  ``col_cut``:
     prefix mask rows (see ``masked_weight_prepare_split``); ``clear=False``: ``out`` was zeroed once and always holds the
     same layer, so its padding needs no clearing.  With ``col_cut``, ``clear=False`` and ``in_of_col`` (the inverse of
-    ``col_of_in``) long rows take the LDS-staged prefix kernel, which writes only the live prefix of each packed row."""
-    if isinstance(weight_v, torch.Tensor) and weight_v.dtype == torch.float64:
-        if col_cut is not None:
-            raise ValueError('masked_weight_prepare: the prefix-mask form (col_cut) is float32-only')
-        return masked_weight_prepare_f64(weight_v, weight_g, mask, row_of_out, col_of_in, n_rows_padded, k_padded, out,
-                                         clear)
-    check_device_tensor(weight_v, 'weight')
+    ``col_of_in``) long rows take the LDS-staged prefix kernel, which writes only the live prefix of each packed row.
+    float64 parameters take ``tfep_masked_weight_prepare_f64``, which has no prefix form: ``col_cut`` is a ValueError."""
+    dt = _dtype(weight_v)
+    if dt == _F64 and col_cut is not None:
+        raise ValueError('masked_weight_prepare: the prefix-mask form (col_cut) is float32-only')
+    check_device_tensor(weight_v, 'weight', dt)
     N, K = weight_v.shape
     tk = tile_sizes()[2]
     n_rows_padded = N if n_rows_padded is None else n_rows_padded
     k_padded = round_up(K, tk) if k_padded is None else k_padded
     if out is None:
-        out = torch.empty(n_rows_padded, k_padded, dtype=torch.float32, device=weight_v.device)
+        out = torch.empty(n_rows_padded, k_padded, dtype=dt, device=weight_v.device)
+    check_device_tensor(out, 'out', dt)
     # (contiguous copies live in locals until the launch is queued; a temporary freed inside the argument list could be
     # overwritten by the next one)
     v_c = weight_v.contiguous()
-    g_c = None if weight_g is None else weight_g.contiguous()
-    m_c = None if mask is None else mask.contiguous()
+    g_c = None if weight_g is None else check_device_tensor(weight_g, 'weight_g', dt).contiguous()
+    m_c = _mask(mask, dt)
+    if dt == _F64:
+        call('tfep_masked_weight_prepare_f64', ptr(v_c), ptr(g_c), ptr(m_c), N, K, ptr(row_of_out), ptr(col_of_in),
+             int(bool(clear)), ptr(out), n_rows_padded, out.shape[1], stream_of(weight_v))
+        return out
     if col_cut is not None and not clear and (in_of_col is not None or col_of_in is None) and 8192 <= K <= 16384 and \
             out.shape[1] % 4 == 0 and out.shape[1] >= round_up(K, 8) and os.environ.get('TFEP_PACK_LDS', '1') != '0':
         call('tfep_masked_weight_prepare_prefix', ptr(v_c), ptr(g_c), N, K, ptr(row_of_out), ptr(in_of_col), ptr(col_cut),
@@ -570,13 +593,12 @@ def masked_weight_prepare(weight_v, weight_g=None, mask=None, row_of_out=None, c
 
 
 def mask_k_ranges(mask, tile_n, n_tiles, k_padded, row_of_out=None, col_of_in=None):
-    if isinstance(mask, torch.Tensor) and mask.dtype == torch.float64:
-        return mask_k_ranges_f64(mask, tile_n, n_tiles, k_padded, row_of_out, col_of_in)
-    check_device_tensor(mask, 'mask')
+    dt = _dtype(mask)
+    check_device_tensor(mask, 'mask', dt)
     N, K = mask.shape
     out = torch.empty(n_tiles, 2, dtype=torch.int32, device=mask.device)
     m_c = mask.contiguous()
-    call('tfep_mask_k_ranges', ptr(m_c), N, K, ptr(row_of_out), ptr(col_of_in), tile_n,
+    call('tfep_mask_k_ranges' + _sfx(dt), ptr(m_c), N, K, ptr(row_of_out), ptr(col_of_in), tile_n,
          tile_sizes()[2], n_tiles, k_padded, ptr(out), stream_of(mask))
     return out
 
@@ -678,49 +700,6 @@ def gemm_slice(x_padded, w_packed, row0, n_rows, bias, k_ranges, kr_offset, out,
 
 # ----------------------------------------------------------------------------- float64 masked linear
 
-_F64 = torch.float64
-
-
-def _f64(t, name):
-    return None if t is None else check_device_tensor(t, name, _F64)
-
-
-def _mask_f64(mask):
-    """The mask as float64 (a 0 / 1 array: exact in any float type; a float32 mask on a float64 layer is converted)."""
-    if mask is None:
-        return None
-    check_device_tensor(mask, 'mask', mask.dtype if mask.is_floating_point() else _F64)
-    return mask.to(_F64).contiguous()
-
-
-def masked_weight_prepare_f64(weight_v, weight_g=None, mask=None, row_of_out=None, col_of_in=None, n_rows_padded=None,
-                              k_padded=None, out=None, clear=True):
-    """``masked_weight_prepare`` for float64 parameters (``tfep_masked_weight_prepare_f64``)."""
-    _f64(weight_v, 'weight')
-    _f64(weight_g, 'weight_g')
-    N, K = weight_v.shape
-    n_rows_padded = N if n_rows_padded is None else n_rows_padded
-    k_padded = round_up(K, tile_sizes()[2]) if k_padded is None else k_padded
-    if out is None:
-        out = torch.empty(n_rows_padded, k_padded, dtype=_F64, device=weight_v.device)
-    _f64(out, 'out')
-    v_c = weight_v.contiguous()
-    g_c = None if weight_g is None else weight_g.contiguous()
-    m_c = _mask_f64(mask)
-    call('tfep_masked_weight_prepare_f64', ptr(v_c), ptr(g_c), ptr(m_c), N, K, ptr(row_of_out), ptr(col_of_in),
-         int(bool(clear)), ptr(out), n_rows_padded, out.shape[1], stream_of(weight_v))
-    return out
-
-
-def mask_k_ranges_f64(mask, tile_n, n_tiles, k_padded, row_of_out=None, col_of_in=None):
-    m_c = _mask_f64(mask)
-    N, K = m_c.shape
-    out = torch.empty(n_tiles, 2, dtype=torch.int32, device=mask.device)
-    call('tfep_mask_k_ranges_f64', ptr(m_c), N, K, ptr(row_of_out), ptr(col_of_in), tile_n, tile_sizes()[2], n_tiles,
-         k_padded, ptr(out), stream_of(mask))
-    return out
-
-
 def masked_linear_f64(x_padded, w_packed, bias, n_out, k_ranges=None, act=0, accumulate=0, elu_grad_of=None, out=None,
                       out_cols=None, kr_tile_n=None):
     """``y (+)= act(x W^T + b) [* elu'(elu_grad_of)]`` on packed float64 operands, every product on the fp64-MFMA GEMM
@@ -754,66 +733,145 @@ def masked_k_ranges_f64(mask, n_pad, k_pad):
     if mask is None:
         return None
     tn = tile_sizes()[1]
-    return mask_k_ranges_f64(mask, tn, (n_pad + tn - 1) // tn, k_pad)
+    return mask_k_ranges(_mask(mask, _F64), tn, (n_pad + tn - 1) // tn, k_pad)
 
 
-def transpose_f64(src, n_rows, n_cols, out):
-    """out (cols_pad x rows_pad, zero filled by the caller) <- src[:n_rows, :n_cols]^T (``tfep_transpose_f64``)."""
-    _f64(src, 'src')
-    _f64(out, 'out')
-    call('tfep_transpose_f64', ptr(src), src.shape[1], n_rows, n_cols, ptr(out), out.shape[1], stream_of(src))
+# ----------------------------------------------------------------------------- one masked linear layer, forward and backward
+
+def gemm(x, w, y, B, N, n_rows_w, bias=None, k_ranges=None, act=0, accumulate=0, elu_grad_of=None, tile_live=None,
+         split=False, w_split=None, x_split=None, tile_list=None, tile_n=0):
+    """``y (+)= act(x w^T + bias) [* elu'(elu_grad_of)]`` on packed float32 operands (``tfep_masked_linear_gemm``): the
+    product of the backward pass, with nothing checked or copied on the way.  ``split``: run on split-f16 operands (x
+    converted here with one scale per row; ``w_split`` / ``x_split`` = already converted ``(rows, inv_scale)`` of w / x,
+    else w is converted here with one scale for the matrix)."""
+    d = _lib.GemmDesc()
+    if split:
+        xs, x_inv = x_split if x_split is not None else split_rows(x, x.shape[1])
+        ws, w_inv = w_split if w_split is not None else split_rows(w, w.shape[1], per_tensor=True)
+        d.split, d.x_inv_scale, d.w_inv_scale = 1, x_inv.data_ptr(), w_inv.data_ptr()
+        x, w = xs, ws
+    d.x, d.ldx = x.data_ptr(), x.shape[1]
+    d.w, d.ldw = w.data_ptr(), w.shape[1]
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.k_ranges = k_ranges.data_ptr() if k_ranges is not None else None
+    d.tile_order, d.col_map = None, None
+    d.y, d.ldy = y.data_ptr(), y.shape[1]
+    d.B, d.N, d.n_rows_w, d.k_padded, d.act, d.accumulate = B, N, n_rows_w, w.shape[1], act, accumulate
+    if elu_grad_of is not None:
+        d.elu_grad_of, d.ld_elu_grad_of = elu_grad_of.data_ptr(), elu_grad_of.shape[1]
+    d.tile_live = tile_live.data_ptr() if tile_live is not None else None
+    if tile_list is not None:
+        d.tile_list, d.n_tile_list = tile_list.data_ptr(), tile_list.shape[0]
+    d.tile_n = tile_n                  # (0 = the default 256 columns; the tables above count tiles of this width)
+    if not split and few_wide_tiles(B, N):
+        # a cfg1-sized product is one or two 256 x 256 tiles: one workgroup walks the whole k range while 255 CUs idle
+        # (130 us for a 224 x 224 x 1024 grad_weight).  The 32-column tile spreads it over the columns; the mask tables are
+        # per 256-column tile and only save work (masked weights are zeros, masked gradients are dropped later): dense.
+        d.tile_n, d.k_ranges, d.tile_live = narrow_tile_n(), None, None
+        d.tile_list, d.n_tile_list = None, 0
+    call('tfep_masked_linear_gemm', ctypes.byref(d), stream_of(x))
+    return y
+
+
+def transpose(src, n_rows, n_cols, out):
+    """out (cols_pad x rows_pad, zero filled by the caller) <- src[:n_rows, :n_cols]^T (``tfep_transpose[_f64]``)."""
+    dt = _dtype(src)
+    check_device_tensor(src, 'src', dt)
+    check_device_tensor(out, 'out', dt)
+    call('tfep_transpose' + _sfx(dt), ptr(src), src.shape[1], n_rows, n_cols, ptr(out), out.shape[1], stream_of(src))
     return out
 
 
-def column_sums_f64(x, n_rows, n_cols, out=None):
-    """out[c] = sum_{r < n_rows} x[r, c] for c < n_cols (``tfep_column_sums_f64``)."""
-    _f64(x, 'x')
+def column_sums(x, n_rows, n_cols, out=None, accumulate=0):
+    """out[c] (+)= sum_{r < n_rows} x[r, c] for c < n_cols (``tfep_column_sums[_f64]``)."""
+    dt = _dtype(x)
+    check_device_tensor(x, 'x', dt)
     if out is None:
-        out = torch.empty(n_cols, dtype=_F64, device=x.device)
-    call('tfep_column_sums_f64', ptr(x), x.shape[1], n_rows, n_cols, ptr(out), 0, stream_of(x))
+        out = torch.empty(n_cols, dtype=dt, device=x.device)
+    check_device_tensor(out, 'out', dt)
+    call('tfep_column_sums' + _sfx(dt), ptr(x), x.shape[1], n_rows, n_cols, ptr(out), int(accumulate), stream_of(x))
     return out
 
 
-def weight_norm_backward_f64(gw_packed, weight_v, weight_g=None, mask=None, row_of_out=None, col_of_in=None):
+def weight_norm_backward(gw_packed, weight_v, weight_g=None, mask=None, row_of_out=None, col_of_in=None):
     """``(grad_v, grad_g)`` of the masked (weight-normalised) parametrisation from the gradient of the packed weight
-    (``tfep_weight_norm_backward_f64``); ``grad_g`` is None without weight norm."""
-    _f64(gw_packed, 'gw_packed')
-    _f64(weight_v, 'weight')
-    _f64(weight_g, 'weight_g')
+    (``tfep_weight_norm_backward[_f64]``); ``grad_g`` is None without weight norm."""
+    dt = _dtype(weight_v)
+    check_device_tensor(gw_packed, 'gw_packed', dt)
+    check_device_tensor(weight_v, 'weight', dt)
     N, K = weight_v.shape
     v_c = weight_v.contiguous()
-    g_c = None if weight_g is None else weight_g.contiguous()
-    m_c = _mask_f64(mask)
-    grad_v = torch.empty(N, K, dtype=_F64, device=weight_v.device)
-    grad_g = None if weight_g is None else torch.empty(weight_g.shape, dtype=_F64, device=weight_v.device)
-    call('tfep_weight_norm_backward_f64', ptr(gw_packed), gw_packed.shape[1], ptr(v_c), ptr(g_c), ptr(m_c), N, K,
+    g_c = None if weight_g is None else check_device_tensor(weight_g, 'weight_g', dt).contiguous()
+    m_c = _mask(mask, dt)
+    grad_v = torch.empty(N, K, dtype=dt, device=weight_v.device)
+    grad_g = None if weight_g is None else torch.empty(weight_g.shape, dtype=dt, device=weight_v.device)
+    call('tfep_weight_norm_backward' + _sfx(dt), ptr(gw_packed), gw_packed.shape[1], ptr(v_c), ptr(g_c), ptr(m_c), N, K,
          ptr(row_of_out), ptr(col_of_in), ptr(grad_v), ptr(grad_g), stream_of(weight_v))
     return grad_v, grad_g
 
 
-def masked_linear_backward_f64(grad_output, x_padded, w_packed, weight, weight_g, mask, n_out, k, want_input=True,
-                               want_weight=True, want_bias=True):
-    """The analytic backward of a float64 masked linear layer (reference masked.py:220-302, :351-404) from its packed
-    operands: ``(grad_input (B, k), grad_v, grad_g, grad_bias)``, None where not wanted.  Every product runs on the fp64
-    GEMM: ``grad_input = g W`` and ``grad_W = g^T x`` (operands transposed so that both stay K-contiguous)."""
+def masked_linear_operands(x2, weight, weight_g, mask):
+    """``(x_padded, w_packed)``: the input and the effective weight ``M o W`` (``W = g v/||v||`` with ``weight_g``) of one
+    masked linear layer, zero padded to whole k-tiles as the GEMMs take them.  ``x2`` (2-D) must be of the parameters'
+    dtype."""
+    n_out, k = weight.shape
+    tk = tile_sizes()[2]
+    k_pad, n_pad = round_up(k, tk), round_up(n_out, tk)
+    w = masked_weight_prepare(weight, weight_g, mask, n_rows_padded=n_pad, k_padded=k_pad)
+    return pad_columns(x2, k_pad, _dtype(weight)), w
+
+
+def masked_linear_layer(x2, weight, weight_g, mask, bias):
+    """One masked linear layer from its parameters: ``(y, x_padded, w_packed)`` with ``y = x2 (M o W)^T + b`` (reference
+    masked.py:265-277, :351-404) and the packed operands of the product, which ``masked_linear_layer_backward`` takes.
+    float32 parameters run on the fp32-MFMA GEMM, float64 ones on the fp64-MFMA GEMM with the k-ranges of the mask."""
+    xp, w = masked_linear_operands(x2, weight, weight_g, mask)
+    n_out, (n_pad, k_pad) = weight.shape[0], w.shape
+    if xp.dtype == _F64:
+        y = masked_linear_f64(xp, w, bias, n_out, k_ranges=masked_k_ranges_f64(mask, n_pad, k_pad))
+    else:
+        y = masked_linear_packed(xp, w, bias, n_out)
+    return y, xp, w
+
+
+def _plain_product(x, w, out, accumulate=0):
+    """``out (+)= x w^T`` on packed operands of either dtype, every column of ``out``."""
+    if x.dtype == _F64:
+        return masked_linear_f64(x, w, None, out.shape[1], accumulate=accumulate, out=out)
+    return gemm(x, w, out, x.shape[0], out.shape[1], out.shape[1], accumulate=accumulate)
+
+
+def masked_linear_layer_backward(grad_output, x_padded, w_packed, weight, weight_g, mask, n_out, k, want_input=True,
+                                 want_weight=True, want_bias=True):
+    """The analytic backward of ``masked_linear_layer`` (reference masked.py:220-302, :351-404) from its packed operands:
+    ``(grad_input (B, k), grad_v, grad_g, grad_bias)``, None where not wanted (``grad_g`` also without weight norm).  Every
+    product runs on the MFMA GEMM of the parameters' dtype: ``grad_input = g W`` and ``grad_W = g^T x`` (operands transposed
+    so that both stay K-contiguous).  A float32 layer converts a ``grad_output`` of another dtype; for a float64 layer it is a
+    TypeError."""
+    dt = _dtype(weight)
     n_pad, k_pad = w_packed.shape
     tk = tile_sizes()[2]
-    f64 = dict(dtype=_F64, device=x_padded.device)
+    kw = dict(dtype=dt, device=x_padded.device)
     g2 = grad_output.reshape(-1, n_out)
+    if dt != _F64:
+        g2 = g2.float()
     B = g2.shape[0]
-    gp = pad_columns(g2, n_pad, _F64)
+    gp = pad_columns(g2, n_pad, dt)
     grad_input = grad_v = grad_g = grad_bias = None
     if want_input:
-        wt = transpose_f64(w_packed, n_pad, k_pad, zeros(k_pad, n_pad, **f64))
-        grad_input = masked_linear_f64(gp, wt, None, k_pad, out=torch.empty(B, k_pad, **f64))[:, :k]
+        wt = transpose(w_packed, n_pad, k_pad, zeros(k_pad, n_pad, **kw))
+        grad_input = _plain_product(gp, wt, torch.empty(B, k_pad, **kw))[:, :k]
     if want_weight:
         Bp = round_up(max(B, 1), tk)
-        gT = transpose_f64(gp, B, n_pad, zeros(n_pad, Bp, **f64))
-        xT = transpose_f64(x_padded, B, k_pad, zeros(k_pad, Bp, **f64))
-        gw = masked_linear_f64(gT, xT, None, k_pad, out=torch.empty(n_pad, k_pad, **f64))
-        grad_v, grad_g = weight_norm_backward_f64(gw, weight, weight_g, mask)
+        gT = transpose(gp, B, n_pad, zeros(n_pad, Bp, **kw))
+        xT = transpose(x_padded, B, k_pad, zeros(k_pad, Bp, **kw))
+        # float32 adds the product to a cleared buffer, float64 writes it: ``0 + s`` and ``s`` differ in the sign of a zero
+        # sum, and each dtype keeps the bits it has always given
+        add = int(dt != _F64)
+        gw = _plain_product(gT, xT, (zeros if add else torch.empty)(n_pad, k_pad, **kw), accumulate=add)
+        grad_v, grad_g = weight_norm_backward(gw, weight, weight_g, mask)
     if want_bias:
-        grad_bias = column_sums_f64(gp, B, n_out)
+        grad_bias = column_sums(gp, B, n_out)
     return grad_input, grad_v, grad_g, grad_bias
 
 
@@ -877,23 +935,15 @@ def column_absmax(x):
 def range_flag(tensors, bits=19):
     """Number of rows, over the 2-D fp32 ``tensors``, whose own dynamic range exceeds what the split-f16 operand format
     carries at fp32 accuracy (a non-zero element below ``2^-bits`` of the row maximum, or a non-finite element):
-    ``tfep_range_flag`` into one device counter, read back once (ONE host synchronisation for the whole list)."""
-    tensors = [t for t in tensors if t is not None and t.numel() > 0]
-    if not tensors:
-        return 0
-    count = torch.zeros(1, dtype=torch.int32, device=tensors[0].device)
-    for t in tensors:
-        check_device_tensor(t, 'range_flag input')
-        if t.dim() != 2 or t.stride(1) != 1:
-            t = t.reshape(t.shape[0], -1).contiguous() if t.dim() > 1 else t.reshape(1, -1).contiguous()
-        call('tfep_range_flag', ptr(t), t.stride(0) if t.shape[0] > 1 else t.shape[1], t.shape[0], t.shape[1], int(bits),
-             ptr(count), stream_of(t))
-    return int(count.item())
+    ``range_flag_device`` read back once (ONE host synchronisation for the whole list)."""
+    c = range_flag_device(tensors, bits)
+    return 0 if c is None else int(c.item())
 
 
 def range_flag_device(tensors, bits=19, count=None):
-    """``range_flag`` without the read-back: the device counter (int32, 1 element) itself, a new one or ``count`` added to --
-    capturable in a HIP graph (a new counter is cleared by a fill kernel, see ``zeros``).  ``None`` when there is nothing to check."""
+    """``tfep_range_flag`` on every tensor into one device counter (int32, 1 element), a new one or ``count`` added to, and
+    no read-back: capturable in a HIP graph (a new counter is cleared by a fill kernel, see ``zeros``).  ``count`` itself
+    (None for a new one) when there is nothing to check."""
     tensors = [t for t in tensors if t is not None and t.numel() > 0]
     if not tensors:
         return count

@@ -552,15 +552,8 @@ def masked_linear(input: Tensor, weight: Tensor, bias: Optional[Tensor], mask: O
         raise RuntimeError(f'masked_linear: bias has {bias.numel()} entries for {n_out} output features')
     if weight_g is not None and weight_g.numel() != n_out:
         raise RuntimeError(f'masked_linear: weight_g has {weight_g.numel()} entries for {n_out} output features')
-    tm, tn, tk = ops.tile_sizes()
-    k_pad, n_pad = ops.round_up(k, tk), ops.round_up(n_out, tk)
-    if weight.dtype == torch.float64:        # the fp64-MFMA GEMM (float64 input and parameters, else TypeError)
-        w = ops.masked_weight_prepare_f64(weight, weight_g, mask, n_rows_padded=n_pad, k_padded=k_pad)
-        y = ops.masked_linear_f64(ops.pad_columns(x2, k_pad, torch.float64), w, bias, n_out,
-                                  k_ranges=ops.masked_k_ranges_f64(mask, n_pad, k_pad))
-        return y.reshape(*input.shape[:-1], n_out)
-    w = ops.masked_weight_prepare(weight, weight_g, mask, n_rows_padded=n_pad, k_padded=k_pad)
-    y = ops.masked_linear_packed(ops.pad_columns(x2, k_pad), w, bias, n_out)
+    # (float64 parameters: the fp64-MFMA GEMM; input and parameters of one dtype, else TypeError)
+    y = ops.masked_linear_layer(x2, weight, weight_g, mask, bias)[0]
     return y.reshape(*input.shape[:-1], n_out)
 
 
@@ -573,41 +566,11 @@ def _(input, weight, bias, mask, weight_g):
 def masked_linear_backward(grad_output: Tensor, input: Tensor, weight: Tensor, mask: Optional[Tensor],
                            weight_g: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """``(grad_input, grad_weight, grad_bias, grad_weight_g)``; grad_weight_g is empty (0 elements) without weight norm."""
-    from .nn.flows._backward import _gemm, _transpose
     n_out, k = weight.shape
-    tm, tn, tk = ops.tile_sizes()
-    k_pad, n_pad = ops.round_up(k, tk), ops.round_up(n_out, tk)
-    if weight.dtype == torch.float64:
-        w = ops.masked_weight_prepare_f64(weight, weight_g, mask, n_rows_padded=n_pad, k_padded=k_pad)
-        xp = ops.pad_columns(input.reshape(-1, k), k_pad, torch.float64)
-        gi, gv, gg, gb = ops.masked_linear_backward_f64(ops._f64(grad_output, 'grad_output'), xp, w, weight, weight_g,
-                                                         mask, n_out, k)
-        gg = gg.reshape(n_out, 1) if weight_g is not None else weight.new_empty((0,))
-        return gi.reshape(input.shape).contiguous(), gv, gb, gg
-    f32 = dict(dtype=torch.float32, device=input.device)
-    w = ops.masked_weight_prepare(weight, weight_g, mask, n_rows_padded=n_pad, k_padded=k_pad)
-    xp = ops.pad_columns(input.reshape(-1, k), k_pad)
-    g2 = grad_output.reshape(-1, n_out).float()
-    B = g2.shape[0]
-    gp = ops.pad_columns(g2, n_pad)
-    stream = _lib.stream_of(xp)
-    wt = _transpose(w, n_pad, k_pad, torch.zeros(k_pad, n_pad, **f32))
-    gx = _gemm(gp, wt, torch.empty(B, k_pad, **f32), B, k_pad, k_pad)
-    grad_input = gx[:, :k].reshape(input.shape).contiguous()
-    Bp = ops.round_up(B, tk)
-    gT = _transpose(gp, B, n_pad, torch.zeros(n_pad, Bp, **f32))
-    xT = _transpose(xp, B, k_pad, torch.zeros(k_pad, Bp, **f32))
-    gw = _gemm(gT, xT, torch.zeros(n_pad, k_pad, **f32), n_pad, k_pad, k_pad, accumulate=1)
-    grad_weight = torch.empty(n_out, k, **f32)
-    grad_g = torch.empty(n_out, 1, **f32) if weight_g is not None else torch.empty(0, **f32)
-    wc = weight.contiguous()
-    gc = None if weight_g is None else weight_g.contiguous()
-    mc = None if mask is None else mask.contiguous()
-    _lib.call('tfep_weight_norm_backward', _lib.ptr(gw), k_pad, _lib.ptr(wc), _lib.ptr(gc), _lib.ptr(mc), n_out, k, None,
-              None, _lib.ptr(grad_weight), _lib.ptr(grad_g) if weight_g is not None else None, stream)
-    grad_bias = torch.empty(n_out, **f32)
-    _lib.call('tfep_column_sums', _lib.ptr(gp), n_pad, B, n_out, _lib.ptr(grad_bias), 0, stream)
-    return grad_input, grad_weight, grad_bias, grad_g
+    xp, w = ops.masked_linear_operands(input.reshape(-1, k), weight, weight_g, mask)      # (the op saved them unpacked)
+    gi, gv, gg, gb = ops.masked_linear_layer_backward(grad_output, xp, w, weight, weight_g, mask, n_out, k)
+    gg = gg.reshape(n_out, 1) if weight_g is not None else weight.new_empty((0,))
+    return gi.reshape(input.shape).contiguous(), gv, gb, gg
 
 
 @masked_linear_backward.register_fake
