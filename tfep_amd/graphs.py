@@ -9,6 +9,34 @@ the graph and reads the CURRENT parameter values at every replay (optimiser upda
 """
 import torch
 
+#: the dtypes a graph can be captured in: those the kernels run in
+_DTYPES = (torch.float32, torch.float64)
+
+
+def flow_dtype(flow):
+    """The floating dtype of ``flow``'s parameters (the first floating-point one decides); float32 for a flow without any."""
+    for p in flow.parameters():
+        if p.is_floating_point():
+            return p.dtype
+    return torch.float32
+
+
+def _resolve_dtype(flow, dtype, who):
+    """The dtype of a graph's static tensors: ``dtype``, or with None the one of the flow's parameters; float32 or float64
+    (ValueError otherwise, before anything touches the device)."""
+    dtype = flow_dtype(flow) if dtype is None else dtype
+    if dtype not in _DTYPES:
+        raise ValueError(f'{who}: dtype must be torch.float32 or torch.float64 (or None: the dtype of the flow\'s parameters), '
+                         f'got {dtype}')
+    return dtype
+
+
+def _check_input_dtype(x, static_in, who):
+    """A float64 graph takes float64 inputs only: ``copy_`` would convert anything else without a word.  (A float32 graph
+    keeps converting, as it always has.)"""
+    if static_in.dtype == torch.float64 and x.dtype != torch.float64:
+        raise TypeError(f'{who} was captured in torch.float64, got an input of {x.dtype}')
+
 
 def _capturing_flags():
     """Context manager: the range guards of the MAF layers captured inside add their flags to the device counter ``['count']`` of
@@ -34,15 +62,22 @@ class GraphedFlow:
     The range guard of the split-f16 default (``AutoregressiveFlow.split_guard``) cannot choose the arithmetic inside a graph:
     the captured call runs on the split kernels and computes every guarded layer's flag on the device; with ``check_range``
     (default) ``g(x)`` reads the flags after the replay -- one host synchronisation -- and, if one is set, repeats the call
-    eagerly, where the guard sends the flagged layers to the exact-fp32 kernels (``last_call_guarded``)."""
+    eagerly, where the guard sends the flagged layers to the exact-fp32 kernels (``last_call_guarded``).
 
-    def __init__(self, flow, batch_size, n_features, inverse=False, device=None, warmup=2, check_range=True):
+    ``dtype``: the dtype of the static input (and with it of the outputs): None takes the dtype of the flow's parameters
+    (float32 for a flow without floating-point parameters), ``torch.float32`` / ``torch.float64`` override it.  A float64
+    flow is captured on its float64 routes -- generic forward, blocked or per-degree inverse (``last_inverse_route`` of the
+    layers says which one the graph holds) --, has no range guard (``n_guarded_calls == 0``: no flag, no synchronisation)
+    and takes float64 inputs only (TypeError otherwise)."""
+
+    def __init__(self, flow, batch_size, n_features, inverse=False, device=None, warmup=2, check_range=True, dtype=None):
+        dtype = _resolve_dtype(flow, dtype, 'GraphedFlow')
         self.flow = flow
         self.inverse = inverse
         self.check_range = check_range
         self.last_call_guarded = False
         device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        self.static_in = torch.zeros(batch_size, n_features, dtype=torch.float32, device=device)
+        self.static_in = torch.zeros(batch_size, n_features, dtype=dtype, device=device)
         fn = flow.inverse if inverse else flow.forward
         # Warm-up off the default stream: builds the execution plans (host-side index work, device->host
         # reads of masks) and sets kernel attributes -- none of which may happen during capture.
@@ -61,6 +96,7 @@ class GraphedFlow:
     def __call__(self, x):
         if x.shape != self.static_in.shape:
             raise ValueError(f'GraphedFlow was captured for shape {tuple(self.static_in.shape)}, got {tuple(x.shape)}')
+        _check_input_dtype(x, self.static_in, 'GraphedFlow')
         self.static_in.copy_(x)
         self.graph.replay()
         self.last_call_guarded = False
@@ -111,9 +147,15 @@ class GraphedTrainingStep:
     and every optimiser state tensor that existed before are then restored IN PLACE (the graph holds their addresses), and
     state the warm-up created (momentum buffers, Adam moments and step counters) is zeroed in place -- the value a fresh
     optimiser starts from.  The first replay is therefore the first step of training.  ``.grad`` of the parameters is
-    owned by the graph afterwards (overwritten by every replay)."""
+    owned by the graph afterwards (overwritten by every replay).
 
-    def __init__(self, flow, loss_fn, optimizer, batch_size, n_features, device=None, warmup=3, sample_input=None):
+    ``dtype``: as for ``GraphedFlow`` (None: the dtype of the flow's parameters).  The step of a float64 flow runs on the
+    float64 kernels throughout: static input, loss, gradients and the optimiser state the warm-up creates are float64, and
+    ``step(x)`` takes float64 inputs only (TypeError otherwise)."""
+
+    def __init__(self, flow, loss_fn, optimizer, batch_size, n_features, device=None, warmup=3, sample_input=None,
+                 dtype=None):
+        dtype = _resolve_dtype(flow, dtype, 'GraphedTrainingStep')
         self.flow, self.loss_fn, self.optimizer = flow, loss_fn, optimizer
         self._flag_total = None
         for group in optimizer.param_groups:
@@ -132,8 +174,9 @@ class GraphedTrainingStep:
             raise RuntimeError('GraphedTrainingStep: an autograd graph over the parameters is still alive (a tensor computed '
                                'from the flow outside torch.no_grad()?): delete it before capturing the step')
         device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        self.static_in = torch.zeros(batch_size, n_features, dtype=torch.float32, device=device)
+        self.static_in = torch.zeros(batch_size, n_features, dtype=dtype, device=device)
         if sample_input is not None:
+            _check_input_dtype(sample_input, self.static_in, 'GraphedTrainingStep')
             self.static_in.copy_(sample_input)
         # what the warm-up steps must not leave behind: parameter values and optimiser state
         saved_params = [p.detach().clone() for p in self.params]
@@ -197,6 +240,7 @@ class GraphedTrainingStep:
     def __call__(self, x):
         if x.shape != self.static_in.shape:
             raise ValueError(f'GraphedTrainingStep was captured for shape {tuple(self.static_in.shape)}, got {tuple(x.shape)}')
+        _check_input_dtype(x, self.static_in, 'GraphedTrainingStep')
         self.static_in.copy_(x)
         self.graph.replay()
         return self.static_loss

@@ -105,7 +105,7 @@ class _PeriodicEmbeddingFn(torch.autograd.Function):
         x, ldx = _lib.rows(x.detach(), 'x', dt)
         g = _lib.check_device_tensor(g.contiguous(), 'grad', dt)
         B, D = x.shape
-        gx = torch.zeros(B, D, dtype=dt, device=x.device)
+        gx = ops.zeros(B, D, dtype=dt, device=x.device)          # (a fill kernel: no memset node in a captured step)
         if B > 0:
             _lib.call('tfep_periodic_embedding_backward' + ops._sfx(dt), _lib.ptr(x), ldx, _lib.ptr(per), per.numel(), _lib.ptr(non),
                       non.numel(), *ctx.limits, _lib.ptr(g), g.shape[1], _lib.ptr(gx), D, B, _lib.stream_of(x))

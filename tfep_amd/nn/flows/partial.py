@@ -22,7 +22,7 @@ class _GatherColumns(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (idx,) = ctx.saved_tensors
-        gx = torch.zeros(g.shape[0], ctx.n, dtype=g.dtype, device=g.device)
+        gx = ops.zeros(g.shape[0], ctx.n, dtype=g.dtype, device=g.device)     # (a fill kernel: no memset node in a captured step)
         ops.scatter_columns(g.contiguous(), idx, gx)
         return gx, None
 
@@ -43,7 +43,7 @@ class _ReplaceColumns(torch.autograd.Function):
         g = g.contiguous()
         gsrc = ops.gather_columns(g, idx)
         gbase = g.clone()
-        ops.scatter_columns(torch.zeros_like(gsrc), idx, gbase)
+        ops.scatter_columns(ops.zeros(*gsrc.shape, dtype=gsrc.dtype, device=gsrc.device), idx, gbase)
         return gbase, gsrc, None
 
 

@@ -30,6 +30,14 @@ class AffineTransformer(MAFTransformer):
         return degrees_in.tile((self.n_parameters_per_feature,))
 
 
+def _stamp(v):
+    """What tells that an attribute is still the one a cache was made from: a tensor's identity, storage and in-place
+    update counter; the values of anything else (a short list)."""
+    if torch.is_tensor(v):
+        return (id(v), v.data_ptr(), v._version)
+    return None if v is None else tuple(v)
+
+
 class VolumePreservingShiftTransformer(MAFTransformer):
     r""":math:`y_i = x_i + b_i` with optional periodic wrap, ``log_det_J = 0`` (reference affine.py:148-274)."""
     n_parameters_per_feature = 1
@@ -43,10 +51,16 @@ class VolumePreservingShiftTransformer(MAFTransformer):
     def _mask(self, x):
         if self.periodic_indices is None:
             return None, (0.0, 1.0)
-        m = torch.zeros(x.shape[1], dtype=torch.int32)
-        m[torch.as_tensor(self.periodic_indices).long().cpu()] = 1
-        lim = [float(v) for v in self.periodic_limits]
-        return m.to(x.device), (lim[0], lim[1])
+        # The device mask and the host limits are made once per device and width and kept while the two attributes are what
+        # they were: a host -> device copy (and, for limits on the device, a read-back) per call cannot be captured in a graph.
+        key = (str(x.device), x.shape[1], _stamp(self.periodic_indices), _stamp(self.periodic_limits))
+        cached = self.__dict__.get('_mask_cache')
+        if cached is None or cached[0] != key:
+            m = torch.zeros(x.shape[1], dtype=torch.int32)
+            m[torch.as_tensor(self.periodic_indices).long().cpu()] = 1
+            lim = [float(v) for v in self.periodic_limits]
+            cached = self.__dict__['_mask_cache'] = (key, m.to(x.device), (lim[0], lim[1]))
+        return cached[1], cached[2]
 
     def forward(self, x, parameters):
         m, lim = self._mask(x)

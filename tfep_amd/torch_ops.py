@@ -85,8 +85,9 @@ def _vjp_inputs(ctx, grads):
     """Upstream gradients of (y, log_det_J), zeros where autograd passes None."""
     x = ctx.saved_tensors[0]
     gy, gl = grads
-    gy = torch.zeros_like(x) if gy is None else gy
-    gl = x.new_zeros(x.shape[0]) if gl is None else gl
+    # (fill kernels, ``ops.zeros``: a captured training step gets no memset node)
+    gy = ops.zeros(*x.shape, dtype=x.dtype, device=x.device) if gy is None else gy
+    gl = ops.zeros(x.shape[0], dtype=x.dtype, device=x.device) if gl is None else gl
     return gy, gl
 
 
@@ -138,7 +139,7 @@ def _sos_setup(ctx, inputs, output):
 
 def _sos_bwd(ctx, gy, gl):
     x, p = ctx.saved_tensors
-    gy = torch.zeros_like(x) if gy is None else gy   # (gl is ignored: the log-det carries no gradient)
+    gy = ops.zeros(*x.shape, dtype=x.dtype, device=x.device) if gy is None else gy   # (gl is ignored: the log-det carries no gradient)
     return (*torch.ops.tfep.sos_backward(x, p, ctx.n_polynomials, gy), None)
 
 
