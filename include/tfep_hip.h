@@ -978,6 +978,51 @@ int tfep_frame_rotate_backward_f64(const double* x, int64_t ldx, const double* R
                                    int64_t ldgy, double* gx, int64_t ldgx, double* gR, int n_points, int B, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Internal coordinates and the polar map (tfep/utils/geometry.py:28-178, 414-471) */
+/* ------------------------------------------------------------------------- */
+
+/*
+ * x is (B, 3 n_atoms) with row stride ldx; fp64 arithmetic for both element types; one wave per row, no atomics, a row's
+ * bits do not depend on its batch.  The index tables are int32 on the device, row-major: pairs (2, n_pairs), triples
+ * (3, n_triples), quads (4, n_quads); a table with no entries may be NULL.  THE CALLER VALIDATES THE TABLES ON THE HOST
+ * (every index in [0, n_atoms)): the kernels cannot reject.  They do not dereference an index out of range -- its entry
+ * is NaN --, skip an item that names no entry and clip an offset to the item list.
+ *   internal_coordinates: one launch (none when all tables are empty) writes, contiguous,
+ *       d (B, n_pairs)    |x[pairs[1]] - x[pairs[0]]|                                  (pdist with pairs)
+ *       a (B, n_triples)  the angle at the middle point, acos of the clamped cosine    (vector_vector_angle(p0 - p1, p2 - p1))
+ *       t (B, n_quads)    proper_dihedral_angle(p1 - p0, p2 - p1, p3 - p2) in the reference's formulation: atan2 of the
+ *                         two rejections, 0 for a collinear quad
+ *   internal_coordinates_backward: (gd, ga, gt) -> gx (B, 3 n_atoms), row stride ldgx, every coordinate written.  A point
+ *       receives its contributions in table order (pairs, triples, quads; within a table by entry) from its incidence
+ *       list: atom_start holds n_atoms + 1 offsets into the n_items of atom_items, an item is 4 * entry + slot with `entry`
+ *       counted through the three tables and `slot` the point's place in the entry; the items of a point ascend.
+ *   polar: element-wise over n contiguous elements, 16-byte accesses when every pointer is 16-byte aligned.
+ *       to_cartesian == 0: (x, y) -> (r, angle), log_det_J = -log r;  != 0: (r, angle) -> (x, y), log_det_J = log r.
+ *       log_det_J may be NULL (not written).  polar_backward: (g0, g1, gl) -> (ga, gb), the cotangents of the two inputs;
+ *       gl (the cotangent of log_det_J) may be NULL.
+ */
+int tfep_internal_coordinates(const float* x, int64_t ldx, const int32_t* pairs, int n_pairs, const int32_t* triples,
+        int n_triples, const int32_t* quads, int n_quads, float* d, float* a, float* t, int n_atoms, int B, void* stream);
+int tfep_internal_coordinates_backward(const float* x, int64_t ldx, const int32_t* pairs, int n_pairs,
+        const int32_t* triples, int n_triples, const int32_t* quads, int n_quads, const int32_t* atom_start,
+        const int32_t* atom_items, int n_items, const float* gd, const float* ga, const float* gt, float* gx, int64_t ldgx,
+        int n_atoms, int B, void* stream);
+int tfep_polar(const float* a, const float* b, int to_cartesian, float* out0, float* out1, float* log_det_J, int64_t n,
+        void* stream);
+int tfep_polar_backward(const float* a, const float* b, int to_cartesian, const float* g0, const float* g1, const float* gl,
+        float* ga, float* gb, int64_t n, void* stream);
+int tfep_internal_coordinates_f64(const double* x, int64_t ldx, const int32_t* pairs, int n_pairs, const int32_t* triples,
+        int n_triples, const int32_t* quads, int n_quads, double* d, double* a, double* t, int n_atoms, int B, void* stream);
+int tfep_internal_coordinates_backward_f64(const double* x, int64_t ldx, const int32_t* pairs, int n_pairs,
+        const int32_t* triples, int n_triples, const int32_t* quads, int n_quads, const int32_t* atom_start,
+        const int32_t* atom_items, int n_items, const double* gd, const double* ga, const double* gt, double* gx, int64_t ldgx,
+        int n_atoms, int B, void* stream);
+int tfep_polar_f64(const double* a, const double* b, int to_cartesian, double* out0, double* out1, double* log_det_J, int64_t n,
+        void* stream);
+int tfep_polar_backward_f64(const double* a, const double* b, int to_cartesian, const double* g0, const double* g1, const double* gl,
+        double* ga, double* gb, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* TFEP reductions (tfep/loss.py, tfep/analysis/estimator.py)                 */
 /* ------------------------------------------------------------------------- */
 

@@ -289,7 +289,17 @@ for _s in ('', '_f64'):
         'tfep_frame_rotate' + _s: (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, c_int, _P]),
         'tfep_frame_rotate_backward' + _s: (c_int, [_P, c_int64, _P, c_int, _P, c_int64, _P, c_int64, _P, c_int, c_int, _P]),
     })
-del _SEL, _FRAME, _s
+# internal coordinates and the polar map (csrc/geometry.hip): the three index tables are (pointer, count) pairs
+_TABLES = [_P, c_int] * 3
+for _s in ('', '_f64'):
+    _SIGNATURES.update({
+        'tfep_internal_coordinates' + _s: (c_int, [_P, c_int64, *_TABLES, _P, _P, _P, c_int, c_int, _P]),
+        'tfep_internal_coordinates_backward' + _s: (c_int, [_P, c_int64, *_TABLES, _P, _P, c_int, _P, _P, _P, _P, c_int64,
+                                                            c_int, c_int, _P]),
+        'tfep_polar' + _s: (c_int, [_P, _P, c_int, _P, _P, _P, c_int64, _P]),
+        'tfep_polar_backward' + _s: (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_int64, _P]),
+    })
+del _SEL, _FRAME, _TABLES, _s
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

@@ -505,6 +505,150 @@ def frame_rotate_backward(x, rot, grad_y, transposed=False):
     return gx, grot
 
 
+# ----------------------------------------------------------------------------- internal coordinates, polar map
+
+_TABLE_ROWS = (('pairs', 2), ('triples', 3), ('quads', 4))
+_TABLE_CACHE = []            # (key, the caller's tables, the prepared device tensors), newest last
+_TABLE_CACHE_SIZE = 8
+
+
+def check_index_table(table, name, n_rows, n_atoms):
+    """One index table on the host: ``(n_rows, count)`` integers in ``[0, n_atoms)`` as a CPU int64 tensor; anything else
+    is a ValueError.  ``None`` is the empty table."""
+    if table is None:
+        return torch.empty(n_rows, 0, dtype=torch.int64)
+    table = torch.as_tensor(table)
+    if table.dim() != 2 or table.shape[0] != n_rows:
+        raise ValueError(f'{name} must have shape ({n_rows}, n), got {tuple(table.shape)}')
+    if table.is_floating_point() or table.is_complex() or table.dtype == torch.bool:
+        raise ValueError(f'{name} must hold integer indices, got {table.dtype}')
+    table = table.detach().to('cpu', torch.int64)
+    if table.numel() and (int(table.min()) < 0 or int(table.max()) >= n_atoms):
+        raise ValueError(f'{name} has an index outside [0, {n_atoms}): min {int(table.min())}, max {int(table.max())}')
+    return table
+
+
+def index_tables(pairs, triples, quads, n_atoms, device):
+    """The three index tables as the internal-coordinate kernels take them: validated HERE, on the host (ValueError on a
+    wrong shape or an index outside ``[0, n_atoms)``; the kernels cannot reject), then ``(pairs, triples, quads,
+    atom_start, atom_items)`` as int32 tensors on ``device``.  ``atom_start`` / ``atom_items`` is the incidence list the
+    backward kernel sums over: for every atom the entries it appears in, in table order, as ``4 * entry + slot``.
+
+    The last few results are kept, keyed by the identity and version of the tensors given, so a table that is used
+    step after step is validated and uploaded once."""
+    given = (pairs, triples, quads)
+    key = (int(n_atoms), str(device)) + tuple(
+        (id(t), t._version, tuple(t.shape)) if isinstance(t, torch.Tensor) else None for t in given)
+    if all(isinstance(t, torch.Tensor) or t is None for t in given):
+        for k, held, prepared in _TABLE_CACHE:
+            if k == key and all(a is b for a, b in zip(held, given)):
+                return prepared
+    host = [check_index_table(t, name, rows_, n_atoms) for t, (name, rows_) in zip(given, _TABLE_ROWS)]
+    counts = [t.shape[1] for t in host]
+    if sum(counts) > (2 ** 31 - 1) // 4 or n_atoms > (2 ** 31 - 1) // 4:
+        raise ValueError(f'{sum(counts)} table entries of {n_atoms} atoms are too many for int32 items')
+    # entry e of a table with slots s: atom table[s, e], item 4 * (offset + e) + s; a stable sort by atom keeps the
+    # items of an atom in table order
+    atoms, items, offset = [], [], 0
+    for t in host:
+        e = torch.arange(t.shape[1]).unsqueeze(1) + offset
+        items.append((4 * e + torch.arange(t.shape[0]).unsqueeze(0)).reshape(-1))
+        atoms.append(t.t().reshape(-1))
+        offset += t.shape[1]
+    atoms, items = torch.cat(atoms), torch.cat(items)
+    order = torch.sort(atoms, stable=True).indices
+    start = torch.zeros(n_atoms + 1, dtype=torch.int64)
+    start[1:] = torch.cumsum(torch.bincount(atoms, minlength=n_atoms), 0)
+    prepared = tuple(t.to(torch.int32).contiguous().to(device) for t in (*host, start, items[order]))
+    if all(isinstance(t, torch.Tensor) or t is None for t in given):
+        _TABLE_CACHE.append((key, given, prepared))
+        del _TABLE_CACHE[:-_TABLE_CACHE_SIZE]
+    return prepared
+
+
+def _table_args(x, tables):
+    """``(n_atoms, pointer / count arguments, counts)`` of prepared tables (``index_tables``) for the rows ``x``."""
+    n = _points(x, 3, 'x')
+    pairs, triples, quads, atom_start, atom_items = tables
+    args, counts = [], []
+    for t, (name, n_rows) in zip((pairs, triples, quads), _TABLE_ROWS):
+        check_device_tensor(t, name, torch.int32)
+        if t.dim() != 2 or t.shape[0] != n_rows or not t.is_contiguous():
+            raise ValueError(f'{name} must be a contiguous ({n_rows}, n) int32 table, got {tuple(t.shape)}')
+        args += [ptr(t), t.shape[1]]
+        counts.append(t.shape[1])
+    check_device_tensor(atom_start, 'atom_start', torch.int32)
+    check_device_tensor(atom_items, 'atom_items', torch.int32)
+    if tuple(atom_start.shape) != (n + 1,) or atom_items.dim() != 1 or not atom_items.is_contiguous():
+        raise ValueError(f'atom_start must be ({n + 1},) and atom_items 1-D: build both with ops.index_tables')
+    return n, args, counts
+
+
+def internal_coordinates(x, pairs, triples, quads, atom_start, atom_items):
+    """``(d, a, t)``: distances over ``pairs``, angles at the middle atom over ``triples``, proper dihedrals over
+    ``quads`` of the rows ``x`` (B, 3 n_atoms; any row stride), in one launch (``tfep_internal_coordinates``).  The five
+    table tensors are those of ``index_tables``, which validates them.  float64 rows run on the float64 kernels."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    n, targs, counts = _table_args(x, (pairs, triples, quads, atom_start, atom_items))
+    B = x.shape[0]
+    d, a, t = (torch.empty(B, c, dtype=dt, device=x.device) for c in counts)
+    call('tfep_internal_coordinates' + _sfx(dt), ptr(x), ldx, *targs, ptr(d), ptr(a), ptr(t), n, B, stream_of(x))
+    return d, a, t
+
+
+def internal_coordinates_backward(x, pairs, triples, quads, atom_start, atom_items, grad_d, grad_a, grad_t):
+    """VJP of ``internal_coordinates`` at ``x``: the cotangent of ``x``, every coordinate written; an atom's
+    contributions are summed in table order, so the result is reproducible bit for bit."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    n, targs, counts = _table_args(x, (pairs, triples, quads, atom_start, atom_items))
+    B = x.shape[0]
+    grads = []
+    for g, c, name in zip((grad_d, grad_a, grad_t), counts, ('grad_d', 'grad_a', 'grad_t')):
+        g = check_device_tensor(g, name, dt).contiguous()
+        if tuple(g.shape) != (B, c):
+            raise ValueError(f'{name} must be ({B}, {c}), got {tuple(g.shape)}')
+        grads.append(g)
+    gx = torch.empty(B, x.shape[1], dtype=dt, device=x.device)
+    call('tfep_internal_coordinates_backward' + _sfx(dt), ptr(x), ldx, *targs, ptr(atom_start), ptr(atom_items),
+         atom_items.numel(), *(ptr(g) for g in grads), ptr(gx), max(x.shape[1], 1), n, B, stream_of(x))
+    return gx
+
+
+def _polar_inputs(dt, *named):
+    out = [check_device_tensor(t, name, dt).contiguous() for t, name in named]
+    if any(t.shape != out[0].shape for t in out):
+        raise ValueError('polar: ' + ', '.join(n for _, n in named) + ' must have one shape')
+    return out
+
+
+def polar(a, b, to_cartesian, with_log_det_J):
+    """The polar map of the plane, element-wise (``tfep_polar``): ``(r, angle, log_det_J)`` of the Cartesian ``(a, b)``,
+    or with ``to_cartesian`` ``(x, y, log_det_J)`` of the polar ``(a, b)``; the log-det is ``-log r`` / ``+log r`` as the
+    reference returns it, and an empty tensor without ``with_log_det_J``."""
+    dt = _dtype(a)
+    a, b = _polar_inputs(dt, (a, 'a'), (b, 'b'))
+    o0, o1 = torch.empty_like(a), torch.empty_like(a)
+    ldj = torch.empty_like(a) if with_log_det_J else a.new_empty(0)
+    call('tfep_polar' + _sfx(dt), ptr(a), ptr(b), int(bool(to_cartesian)), ptr(o0), ptr(o1),
+         ptr(ldj) if with_log_det_J else None, a.numel(), stream_of(a))
+    return o0, o1, ldj
+
+
+def polar_backward(a, b, to_cartesian, grad_0, grad_1, grad_log_det_J):
+    """VJP of ``polar``: the cotangents of ``(a, b)``; ``grad_log_det_J`` may be None."""
+    dt = _dtype(a)
+    named = [(a, 'a'), (b, 'b'), (grad_0, 'grad_0'), (grad_1, 'grad_1')]
+    if grad_log_det_J is not None:
+        named.append((grad_log_det_J, 'grad_log_det_J'))
+    a, b, g0, g1, *gl = _polar_inputs(dt, *named)
+    ga, gb = torch.empty_like(a), torch.empty_like(a)
+    call('tfep_polar_backward' + _sfx(dt), ptr(a), ptr(b), int(bool(to_cartesian)), ptr(g0), ptr(g1),
+         ptr(gl[0]) if gl else None, ptr(ga), ptr(gb), a.numel(), stream_of(a))
+    return ga, gb
+
+
 def gather_columns(src, idx):
     dt = _dtype(src)
     src, lds = rows(src, 'src', dt)

@@ -19,6 +19,9 @@ in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the re
   tfep::centroid_shift / centroid_restore / frame_orient / frame_rotate, each with its _backward
                                                                      reference flows/centroid.py, flows/oriented.py,
                                                                      utils/geometry.py:239-411 (FRAME_OPS)
+  tfep::internal_coordinates / _backward, polar_forward / polar_backward
+                                                                     reference utils/geometry.py:28-178, 414-471
+                                                                     (GEOMETRY_OPS)
   tfep::masked_linear / masked_linear_backward                       reference masked.py:220-302, 351-404
   tfep::fused_output_transformer                                     masked.py:188-208 (last layer) + the transformer
   tfep::tfep_reduce                                                  loss.py:125-140, analysis/estimator.py:73-86
@@ -537,6 +540,70 @@ frame_orient.register_autograd(_frame_orient_bwd, setup_context=_frame_orient_se
 frame_rotate.register_autograd(_frame_rotate_bwd, setup_context=_frame_rotate_setup)
 
 
+# ============================================================================= internal coordinates, polar map
+
+@custom_op('tfep::internal_coordinates', mutates_args=(), device_types=_DEV)
+def internal_coordinates(x: Tensor, pairs: Tensor, triples: Tensor, quads: Tensor, atom_start: Tensor,
+                         atom_items: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(d, a, t)`` of the rows ``x`` (B, 3 n_atoms): distances, angles and proper dihedrals over the int32 tables of
+    ``ops.index_tables`` (which validates them on the host; the incidence list serves the backward)."""
+    return ops.internal_coordinates(x, pairs, triples, quads, atom_start, atom_items)
+
+
+@custom_op('tfep::internal_coordinates_backward', mutates_args=(), device_types=_DEV)
+def internal_coordinates_backward(x: Tensor, pairs: Tensor, triples: Tensor, quads: Tensor, atom_start: Tensor,
+                                  atom_items: Tensor, grad_d: Tensor, grad_a: Tensor, grad_t: Tensor) -> Tensor:
+    return ops.internal_coordinates_backward(x, pairs, triples, quads, atom_start, atom_items, grad_d, grad_a, grad_t)
+
+
+@custom_op('tfep::polar_forward', mutates_args=(), device_types=_DEV)
+def polar_forward(a: Tensor, b: Tensor, to_cartesian: bool, with_log_det_J: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(r, angle, log_det_J)`` of Cartesian ``(a, b)``, or ``(x, y, log_det_J)`` of polar ``(a, b)`` with
+    ``to_cartesian``; the log-det is an empty tensor without ``with_log_det_J``."""
+    return ops.polar(a, b, to_cartesian, with_log_det_J)
+
+
+@custom_op('tfep::polar_backward', mutates_args=(), device_types=_DEV)
+def polar_backward(a: Tensor, b: Tensor, to_cartesian: bool, grad_0: Tensor, grad_1: Tensor,
+                   grad_log_det_J: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    return ops.polar_backward(a, b, to_cartesian, grad_0, grad_1, grad_log_det_J)
+
+
+internal_coordinates.register_fake(lambda x, pairs, triples, quads, atom_start, atom_items: tuple(
+    x.new_empty((x.shape[0], t.shape[1])) for t in (pairs, triples, quads)))
+internal_coordinates_backward.register_fake(lambda x, *rest: x.new_empty(x.shape))
+polar_forward.register_fake(lambda a, b, to_cartesian, with_log_det_J: (
+    a.new_empty(a.shape), a.new_empty(a.shape), a.new_empty(a.shape if with_log_det_J else (0,))))
+polar_backward.register_fake(lambda a, b, to_cartesian, g0, g1, gl: (a.new_empty(a.shape), a.new_empty(a.shape)))
+
+
+def _internal_coordinates_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+    ctx.like = tuple(_meta(o) for o in output)
+
+
+def _internal_coordinates_bwd(ctx, g_d, g_a, g_t):
+    grads = (_or_zeros(g, like) for g, like in zip((g_d, g_a, g_t), ctx.like))
+    return (torch.ops.tfep.internal_coordinates_backward(*ctx.saved_tensors, *grads), *([None] * 5))
+
+
+def _polar_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1])
+    ctx.to_cartesian, ctx.with_log_det_J = inputs[2], inputs[3]
+    ctx.like = _meta(output[0])
+
+
+def _polar_bwd(ctx, g_0, g_1, g_l):
+    a, b = ctx.saved_tensors
+    g_l = _or_zeros(g_l, ctx.like) if ctx.with_log_det_J else None
+    ga, gb = torch.ops.tfep.polar_backward(a, b, ctx.to_cartesian, _or_zeros(g_0, ctx.like), _or_zeros(g_1, ctx.like), g_l)
+    return ga, gb, None, None
+
+
+internal_coordinates.register_autograd(_internal_coordinates_bwd, setup_context=_internal_coordinates_setup)
+polar_forward.register_autograd(_polar_bwd, setup_context=_polar_setup)
+
+
 # ============================================================================= masked linear
 
 @custom_op('tfep::masked_linear', mutates_args=(), device_types=_DEV)
@@ -690,3 +757,4 @@ QUATERNION_PRODUCT_OPS = ('quaternion_product_forward', 'quaternion_product_inve
 FLIP_EMBEDDING_OPS = ('flip_invariant_embedding', 'flip_invariant_embedding_backward')
 FRAME_OPS = ('centroid_shift', 'centroid_restore', 'frame_orient', 'frame_rotate', 'centroid_shift_backward',
              'centroid_restore_backward', 'frame_orient_backward', 'frame_rotate_backward')
+GEOMETRY_OPS = ('internal_coordinates', 'internal_coordinates_backward', 'polar_forward', 'polar_backward')

@@ -1,14 +1,110 @@
-"""Rigid-frame helpers for the flow wrappers (reference ``tfep/utils/geometry.py:185-411``).
+"""Geometry of point coordinates (reference ``tfep/utils/geometry.py``): internal coordinates, rotations, rigid
+frames, the polar map.
 
-Only what ``OrientedFlow`` / ``CenteredCentroidFlow`` need.  The reference composes two Rodrigues
+Rigid frames: only what ``OrientedFlow`` / ``CenteredCentroidFlow`` need.  The reference composes two Rodrigues
 rotations from angles (acos / asin / sin / cos); here both rotations are written in closed form from dot
 and cross products, which gives the same matrices without the inverse-trig round trip and stays
 differentiable.  These are O(batch) 3x3 operations around the hot path and run as
 ordinary torch ops on the input's device.
+
+Internal coordinates: ``internal_coordinates`` (and ``pdist`` without ``return_diff``) compute distances, angles and
+dihedrals from point INDICES in one HIP launch, forward and backward (``csrc/geometry.hip``; HIP tensors only).  The
+functions that take difference VECTORS (``vector_vector_angle``, ``vector_plane_angle``, ``proper_dihedral_angle``) and
+``rotation_matrix_3d`` are torch expressions on the device of their inputs, which are materialised already.
+``cartesian_to_polar`` / ``polar_to_cartesian`` run on the element-wise polar kernel.
 """
-from typing import Optional
+from functools import lru_cache
+from typing import Optional, Tuple
 
 import torch
+
+from .. import ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.tfep.*)
+from .math import batchwise_dot, batchwise_outer
+
+
+# ----------------------------------------------------------------------------- internal coordinates
+
+@lru_cache(maxsize=8)
+def _all_pairs(n_particles):
+    """The (2, n (n - 1) / 2) table of all pairs: one tensor per size, so ``ops.index_tables`` prepares it once."""
+    return torch.triu_indices(n_particles, n_particles, offset=1)
+
+
+def internal_coordinates(x, pairs=None, triples=None, quads=None):
+    """Distances, angles and proper dihedrals of a batch of configurations from atom indices, in one HIP launch.
+
+    ``x``: positions, ``(batch_size, n_particles, 3)`` or flattened ``(batch_size, 3 * n_particles)``, a float32 or float64
+    HIP tensor (a column slice of a wider tensor is read in place).  ``pairs`` ``(2, P)``, ``triples`` ``(3, A)``,
+    ``quads`` ``(4, T)``: integer index tables on any device (validated on the host, ValueError on an index outside
+    ``[0, n_particles)``; pass the same tensor object at every call and it is validated and uploaded once).
+
+    Returns ``(d, a, t)`` of shapes ``(batch_size, P)``, ``(batch_size, A)``, ``(batch_size, T)``; a table not given has
+    no columns.  ``d[b, i]`` is the distance of atoms ``pairs[0, i]`` and ``pairs[1, i]``; ``a[b, i]`` the angle in
+    ``[0, pi]`` at atom ``triples[1, i]`` -- ``vector_vector_angle(p0 - p1, p2 - p1)`` --; ``t[b, i]`` the dihedral in
+    ``(-pi, pi]`` of the four atoms of ``quads[:, i]`` -- ``proper_dihedral_angle(p1 - p0, p2 - p1, p3 - p2)``, zero for
+    collinear atoms.  Differentiable in ``x``; the backward is one launch and reproducible bit for bit.
+    """
+    if x.dim() == 3 and x.shape[2] == 3:
+        x = x.reshape(x.shape[0], -1)
+    if x.dim() != 2 or x.shape[1] % 3 != 0:
+        raise ValueError(f'x must be (batch, n_particles, 3) or (batch, 3 n_particles), got {tuple(x.shape)}')
+    tables = ops.index_tables(pairs, triples, quads, x.shape[1] // 3, x.device)
+    return torch.ops.tfep.internal_coordinates(x, *tables)
+
+
+def pdist(x, pairs=None, return_diff=False):
+    """Euclidean distances between pairs of particles of ``x`` ``(batch_size, n_particles, D)`` (reference
+    geometry.py:28-68).  ``pairs``: ``(2, n_pairs)`` indices, all pairs when not given.  Returns ``(batch_size, n_pairs)``
+    and, with ``return_diff``, the vectors ``p1 - p0`` as ``(batch_size, n_pairs, D)``.
+
+    Without ``return_diff`` this is ``internal_coordinates`` (D = 3, HIP tensors); with it a torch expression, the
+    difference tensor being a result anyway."""
+    if pairs is None:
+        pairs = _all_pairs(x.shape[-2])
+    if return_diff:
+        pairs = torch.as_tensor(pairs, device=x.device)
+        diff = x[:, pairs[1]] - x[:, pairs[0]]
+        return torch.sqrt(torch.sum(diff ** 2, dim=-1)), diff
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError(f'pdist without return_diff takes (batch, n_particles, 3) positions, got {tuple(x.shape)}')
+    return internal_coordinates(x, pairs=pairs)[0]
+
+
+def vector_vector_angle(x1, x2):
+    """Angle in ``[0, pi]`` between the vectors of ``x1`` and ``x2``, both ``(*, D)`` (reference geometry.py:71-99)."""
+    cos_theta = batchwise_dot(x1, x2) / (torch.linalg.vector_norm(x1, dim=-1) * torch.linalg.vector_norm(x2, dim=-1))
+    return torch.acos(torch.clamp(cos_theta, min=-1, max=1))       # (the clamp catches round-off)
+
+
+def vector_plane_angle(x, plane):
+    """Angle between the vectors ``x`` ``(batch_size, N)`` or ``(N,)`` and the plane of normal ``plane`` ``(N,)``
+    (reference geometry.py:102-124)."""
+    cos_theta = batchwise_dot(x, plane) / (torch.linalg.vector_norm(x, dim=-1) * torch.linalg.vector_norm(plane, dim=-1))
+    return torch.asin(torch.clamp(cos_theta, min=-1, max=1))
+
+
+def proper_dihedral_angle(x1, x2, x3):
+    """Proper dihedral between the planes ``x1``-``x2`` and ``x2``-``x3`` for ``x1 = p1 - p0``, ``x2 = p2 - p1``,
+    ``x3 = p3 - p2``, all ``(*, 3)`` (reference geometry.py:127-178): the angle, in the plane perpendicular to ``x2``,
+    from the rejection of ``-x1`` to that of ``x3``."""
+    x2 = x2 / torch.linalg.vector_norm(x2, dim=-1, keepdim=True)
+    v = -x1 - batchwise_dot(-x1, x2, keepdim=True) * x2
+    w = x3 - batchwise_dot(x3, x2, keepdim=True) * x2
+    return torch.atan2(batchwise_dot(torch.linalg.cross(x2, v, dim=-1), w), batchwise_dot(v, w))
+
+
+# ----------------------------------------------------------------------------- rotations and rigid frames
+
+def rotation_matrix_3d(angles, directions):
+    """Matrices ``(batch_size, 3, 3)`` rotating by ``angles`` ``(batch_size,)`` about ``directions`` ``(batch_size, 3)`` or
+    ``(3,)``, by Rodrigues' formula (reference geometry.py:185-236)."""
+    k = torch.nn.functional.normalize(directions, dim=-1)
+    if k.dim() < 2:
+        k = k.unsqueeze(0)
+    k = k.expand(len(angles), 3)
+    cosa = torch.cos(angles)[:, None, None]
+    eye = torch.eye(3, dtype=angles.dtype, device=angles.device)
+    return cosa * eye + (1 - cosa) * batchwise_outer(k, k) + _skew(torch.sin(angles).unsqueeze(-1) * k)
 
 
 def get_axis_from_name(name: str) -> torch.Tensor:
@@ -96,3 +192,19 @@ def reference_frame_rotation_matrix(
     r2 = cos2[:, None, None] * eye + sin2[:, None, None] * kx + (1.0 - cos2)[:, None, None] * aa
 
     return torch.matmul(r2, r1)
+
+
+# ----------------------------------------------------------------------------- polar coordinates
+
+def cartesian_to_polar(x: torch.Tensor, y: torch.Tensor, return_log_det_J: bool = False) -> Tuple[torch.Tensor]:
+    """``(r, angle)`` of the Cartesian ``(x, y)``, element-wise, and with ``return_log_det_J`` the log absolute Jacobian
+    determinant of the map as the reference returns it, ``-log r`` (reference geometry.py:414-441).  HIP tensors."""
+    r, angle, log_det_J = torch.ops.tfep.polar_forward(x, y, False, return_log_det_J)
+    return (r, angle, log_det_J) if return_log_det_J else (r, angle)
+
+
+def polar_to_cartesian(r: torch.Tensor, angle: torch.Tensor, return_log_det_J: bool = False) -> Tuple[torch.Tensor]:
+    """``(x, y)`` of the polar ``(r, angle)``, element-wise, and with ``return_log_det_J`` also ``log r`` (reference
+    geometry.py:444-471).  HIP tensors."""
+    x, y, log_det_J = torch.ops.tfep.polar_forward(r, angle, True, return_log_det_J)
+    return (x, y, log_det_J) if return_log_det_J else (x, y)
