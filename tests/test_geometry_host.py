@@ -1,6 +1,8 @@
 """CPU tests of the geometry layer (reference ``tfep/utils/geometry.py``, ``tfep/utils/math.py``): the public names and
 their signatures, the C ABI symbols, the host-side validation of the index tables, the golden fixture, and the functions
-that are plain torch expressions against the reference's float64 results.  No kernel is launched."""
+that are plain torch expressions against the reference's float64 results; the plain float64 restatement of the kernels
+that the GPU tests compare with (tests/geometry_ref.py) against the same results; the table cache; and the per-entry
+arithmetic of csrc/geometry.h, compiled for the host.  No kernel is launched."""
 import inspect
 import os
 import re
@@ -9,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import geometry_ref as gr
 import golden_util as gu
 from tfep_amd import _lib, ops
 from tfep_amd.utils import geometry, math as tmath
@@ -193,3 +196,118 @@ def test_math_matches_the_reference():
     y = torch.tanh(z @ _t(g['math/w'])) + 2.0 * z
     _close(tmath.batch_autograd_jacobian(z, y, retain_graph=True), g['math/jacobian'])
     _close(tmath.batch_autograd_log_abs_det_J(z, y), g['math/log_abs_det_J'])
+
+
+# ------------------------------------------------------------------ the restatement the GPU tests compare with
+
+def _rel(got, ref, wrap=np.asarray):
+    return gr.rel_l2(wrap(got), wrap(ref))
+
+
+@pytest.mark.parametrize('case', ['main', 'hub'])
+def test_plain_reference_matches_the_golden_internal_coordinates(case):
+    """tests/geometry_ref.py is written from the header of csrc/geometry.h; here it meets the reference's own results."""
+    g = gu.load('geometry.npz')
+    tables = [g[f'{case}/{k}'] for k in ('pairs', 'triples', 'quads')]
+    got = gr.coordinates_and_gradient(g['x'], tables, [g[f'{case}/{k}'] for k in ('gd', 'ga', 'gt')])
+    for k, v, wrap in zip(('d', 'a', 't', 'gx'), got, (np.asarray, gr.circ, gr.circ, np.asarray)):
+        rel = _rel(v, g[f'{case}/{k}'], wrap)
+        print(f'{case} {k}: rel L2 {rel:.3e}')
+        assert v.shape == g[f'{case}/{k}'].shape and rel <= 1e-12, (case, k, rel)
+
+
+def test_plain_reference_matches_the_golden_distances_of_all_pairs():
+    g = gu.load('geometry.npz')
+    d, a, t = gr.internal_coordinates(_t(g['x']), pairs=torch.triu_indices(7, 7, offset=1))
+    rel = _rel(d.numpy(), g['pdist_all/d'])
+    print(f'pdist_all d: rel L2 {rel:.3e}')
+    assert rel <= 1e-12 and a.shape == t.shape == (11, 0)
+
+
+@pytest.mark.parametrize('name', ['cartesian_to_polar', 'polar_to_cartesian'])
+def test_plain_reference_matches_the_golden_polar_maps(name):
+    g = gu.load('geometry.npz')
+    got = gr.polar_and_gradient(g[f'{name}/in0'], g[f'{name}/in1'], name == 'polar_to_cartesian',
+                                [g[f'{name}/cot{i}'] for i in range(3)])
+    for k, v in zip(('out0', 'out1', 'out2', 'g0', 'g1'), got):
+        rel = _rel(v, g[f'{name}/{k}'], gr.circ if (name, k) == ('cartesian_to_polar', 'out1') else np.asarray)
+        print(f'{name} {k}: rel L2 {rel:.3e}')
+        assert rel <= 1e-12, (name, k, rel)
+
+
+def test_wide_tables_have_the_layout_the_gpu_tests_rely_on():
+    pairs, triples, quads = gr.wide_tables()
+    assert [tuple(t.shape) for t in (pairs, triples, quads)] == [(2, 70), (3, 67), (4, 65)]
+    for t in (pairs, triples, quads):
+        assert all(len(set(col)) == t.shape[0] for col in t.t().tolist())          # distinct atoms in every entry
+        assert int(t.min()) >= 0 and int(t.max()) < 125 and bool((t == 3).any())
+    assert pairs[0, 0::2].eq(64).all() and pairs[1, 1::2].eq(64).all()
+    assert bool(((pairs == 64).any(0) & (pairs == 11).any(0)).any())
+    x, _, cots = gr.wide_case()
+    assert x.shape == (6, 130, 3) and [tuple(c.shape) for c in cots] == [(6, 70), (6, 67), (6, 65)]
+    min_d, min_sin, min_rejection = gr.conditioning(x, pairs, triples, quads)
+    print(f'seed {gr.WIDE_SEED}: min d {min_d:.4f}, min sin(a) {min_sin:.4f}, min(|v|, |w|) {min_rejection:.4f}')
+    assert min_d >= gr.MIN_D and min_sin >= gr.MIN_SIN and min_rejection >= gr.MIN_REJECTION
+
+
+# ------------------------------------------------------------------ the table cache
+
+def test_table_cache_sees_an_in_place_write():
+    """The cache keys on the identity, version and shape of the tensors given: a table changed in place is prepared
+    again, and validated again."""
+    n = 9
+    pairs = torch.tensor([[0, 1, 2], [3, 4, 5]])
+    triples = torch.tensor([[0, 1], [2, 3], [4, 5]])
+    first = ops.index_tables(pairs, triples, None, n_atoms=n, device='cpu')
+    assert ops.index_tables(pairs, triples, None, n_atoms=n, device='cpu') is first
+    pairs[1, 2] = 8
+    triples[0, 1] = 7
+    second = ops.index_tables(pairs, triples, None, n_atoms=n, device='cpu')
+    fresh = ops.index_tables(pairs.clone(), triples.clone(), None, n_atoms=n, device='cpu')
+    assert second is not first
+    for got, new, old in zip(second, fresh, first):
+        assert torch.equal(got, new)
+    assert second[0].tolist() == [[0, 1, 2], [3, 4, 8]] and second[1][0].tolist() == [0, 7]
+    start, items = second[3], second[4]
+    assert items[start[8]:start[9]].tolist() == [4 * 2 + 1]                       # atom 8: pair 2, slot 1
+    assert items[start[7]:start[8]].tolist() == [4 * (3 + 1) + 0]                 # atom 7: triple 1, slot 0
+    assert items[start[5]:start[6]].tolist() == [4 * (3 + 1) + 2]                 # atom 5 has left pair 2
+    assert not torch.equal(first[4], items)
+    for bad in (n, -1):
+        pairs[0, 0] = bad
+        with pytest.raises(ValueError, match='outside'):
+            ops.index_tables(pairs, triples, None, n_atoms=n, device='cpu')
+    pairs[0, 0] = 0
+    assert torch.equal(ops.index_tables(pairs, triples, None, n_atoms=n, device='cpu')[4], items)
+
+
+def test_long_incidence_lists_are_in_table_order():
+    """The wide tables: atom 64 has 70 items, five atoms have none, the offsets never decrease."""
+    tables = gr.wide_tables()
+    P, A, T = (t.shape[1] for t in tables)
+    *_, start, items = ops.index_tables(*tables, n_atoms=gr.WIDE_N, device='cpu')
+    assert start.shape == (gr.WIDE_N + 1,) and int(start[0]) == 0
+    assert bool((start[1:] >= start[:-1]).all())
+    assert int(start[-1]) == 2 * P + 3 * A + 4 * T == items.numel()
+    assert start[125:].tolist() == [int(start[-1])] * 6                           # atoms 125..129 are empty
+    flat = [(int(t[s, e]), 4 * (off + e) + s) for t, off in zip(tables, (0, P, P + A)) for e in range(t.shape[1])
+            for s in range(t.shape[0])]
+    for atom in range(gr.WIDE_N):
+        assert items[start[atom]:start[atom + 1]].tolist() == sorted(item for a, item in flat if a == atom), atom
+    hub = items[start[64]:start[65]].tolist()
+    assert hub[:P] == [4 * e + e % 2 for e in range(P)] and all(item >= 4 * P for item in hub[P:])
+
+
+# ------------------------------------------------------------------ csrc/geometry.h on the host
+
+def test_entry_arithmetic_and_its_vjps_on_the_host(tmp_path):
+    """csrc/geometry.h is __host__ __device__: tools/geometry_host_check.cpp, built for the host alone, checks the four VJPs
+    against central differences in long double and the translation invariance of the point cotangents."""
+    import subprocess
+    from tfep_amd.build import _hipcc
+    exe = str(tmp_path / 'geometry_host_check')
+    subprocess.run([_hipcc(), '-std=c++17', '--cuda-host-only', '-x', 'hip', os.path.join(ROOT, 'tools', 'geometry_host_check.cpp'),
+                    '-o', exe], check=True)
+    done = subprocess.run([exe], capture_output=True, text=True)
+    print(done.stdout)
+    assert done.returncode == 0, done.stdout + done.stderr
