@@ -32,14 +32,16 @@ def _estimate(data, kT, weights, process_group, distributed):
         work, bias = data[..., 0], data[..., 1]
     if bias is not None and weights is not None:
         raise NotImplementedError('Bayesian bootstrapping is not supported with biased data.')
+    # float64 work stays float64 (tfep_tfep_reduce_f64: residuals, bias and kT in double); anything else is float32 work
+    dtype = torch.float64 if data.dtype == torch.float64 else torch.float32
     out = []
     for b in range(work.shape[0]):
-        w = work[b].contiguous().float()
+        w = work[b].contiguous().to(dtype)
         # the bias slot of tfep_tfep_reduce is  + bias/kT ; weights enter as log(weights)*kT
         if bias is not None:
-            extra = bias[b].contiguous().float()
+            extra = bias[b].contiguous().to(dtype)
         elif weights is not None:
-            extra = torch.log(weights[b].contiguous().float()) * kT
+            extra = torch.log(weights[b].contiguous().to(dtype)) * kT
         else:
             extra = None
         stats = reduce_stats(w, None, None, None, extra, kT=kT)       # torch.ops.tfep.tfep_reduce

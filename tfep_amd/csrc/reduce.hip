@@ -15,6 +15,10 @@ struct Stats {
     double m_b, s_b;
 };
 
+// exp(a - b) for a <= b, with 1 where the two are equal: two +inf count one each, as in torch.logsumexp, where
+// exp(inf - inf) would be NaN.  For finite a == b this is exp(0) = 1 either way.
+__device__ inline double rescale(double a, double b) { return a == b ? 1.0 : exp(a - b); }
+
 __device__ inline void online_add(double& m, double& s, double v) {
     // s = sum exp(v_i - m), m = running max.  -inf values contribute nothing.
     if (v == -INFINITY) return;
@@ -22,10 +26,12 @@ __device__ inline void online_add(double& m, double& s, double v) {
         s = s * exp(m - v) + 1.0;
         m = v;
     } else {
-        s += exp(v - m);
+        s += rescale(v, m);
     }
 }
 
+// The weight pair keeps exp(m - m): a +inf log-weight makes the sums NaN, as torch.softmax does (its own term too,
+// so that a thread or a batch that holds nothing else says the same).
 __device__ inline void online_add2(double& m, double& s, double& sr, double v, double r) {
     if (v == -INFINITY) return;
     if (v > m) {
@@ -33,6 +39,7 @@ __device__ inline void online_add2(double& m, double& s, double& sr, double v, d
         s = s * c + 1.0;
         sr = sr * c + r;
         m = v;
+        if (v == INFINITY) s = sr = NAN;
     } else {
         const double e = exp(v - m);
         s += e;
@@ -48,7 +55,7 @@ __device__ inline void combine(double& m, double& s, double m2, double s2) {
         return;
     }
     const double mm = fmax(m, m2);
-    s = s * exp(m - mm) + s2 * exp(m2 - mm);
+    s = s * rescale(m, mm) + s2 * rescale(m2, mm);
     m = mm;
 }
 
@@ -150,11 +157,9 @@ __global__ void __launch_bounds__(256) tfep_reduce_partial_kernel(const T* __res
         }
         if (lw) {
             // softmax over the whole batch (loss.py:133); NaN r skipped by nansum when ignore_nan
+            // an ignored sample adds 0 to s_wr through the same pair: a new maximum has to rescale s_wr as well
             const double v = (double)lw[i];
-            if (ignore_nan && isn)
-                online_add(st.m_w, st.s_w, v);
-            else
-                online_add2(st.m_w, st.s_w, st.s_wr, v, r);
+            online_add2(st.m_w, st.s_w, st.s_wr, v, (ignore_nan && isn) ? 0.0 : r);
         }
         double e = -r * inv_kT;
         if (bias) {
@@ -207,7 +212,7 @@ struct MaxSum {
 __device__ inline void ms_add(MaxSum& a, double v) {
     if (v == -INFINITY) return;
     if (v <= a.m) {
-        a.s += exp(v - a.m);
+        a.s += rescale(v, a.m);
     } else {
         a.s = a.s * exp(a.m - v) + 1.0;
         a.m = v;
@@ -218,7 +223,7 @@ __device__ inline MaxSum ms_merge(MaxSum a, MaxSum b) {
     if (a.s == 0.0) return b;
     MaxSum r;
     r.m = fmax(a.m, b.m);
-    r.s = a.s * exp(a.m - r.m) + b.s * exp(b.m - r.m);
+    r.s = a.s * rescale(a.m, r.m) + b.s * rescale(b.m, r.m);
     return r;
 }
 __device__ inline MaxSum ms_block_reduce(MaxSum v, MaxSum* sh) {
@@ -285,7 +290,8 @@ int tfep_tfep_reduce_workspace_doubles(int N) {
 int tfep_tfep_reduce(const float* target_potentials, const float* log_det_J, const float* ref_potentials,
                      const float* log_weights, const float* bias, float kT, int ignore_nan, int N,
                      double* workspace, double* out, void* stream) {
-    TFEP_REQUIRE(target_potentials && out && workspace, "tfep_reduce: NULL pointer");
+    // an empty batch (its tensor has no storage) gives the identity: nothing is read
+    TFEP_REQUIRE((target_potentials || N == 0) && out && workspace, "tfep_reduce: NULL pointer");
     TFEP_REQUIRE(N >= 0, "tfep_reduce: negative N");
     TFEP_REQUIRE(kT > 0.f, "tfep_reduce: kT must be positive");
     int blocks = (N + 255) / 256;
@@ -301,7 +307,7 @@ int tfep_tfep_reduce(const float* target_potentials, const float* log_det_J, con
 int tfep_tfep_reduce_f64(const double* target_potentials, const double* log_det_J, const double* ref_potentials,
                          const double* log_weights, const double* bias, double kT, int ignore_nan, int N,
                          double* workspace, double* out, void* stream) {
-    TFEP_REQUIRE(target_potentials && out && workspace, "tfep_reduce_f64: NULL pointer");
+    TFEP_REQUIRE((target_potentials || N == 0) && out && workspace, "tfep_reduce_f64: NULL pointer");
     TFEP_REQUIRE(N >= 0, "tfep_reduce_f64: negative N");
     TFEP_REQUIRE(kT > 0.0, "tfep_reduce_f64: kT must be positive");
     int blocks = (N + 255) / 256;

@@ -24,6 +24,10 @@ def combine_stats(stats_list):
         gm = torch.where(torch.isnan(m).any(), torch.full_like(m[0], float('nan')), m.max())
         scale = torch.exp(m - gm)
         scale = torch.where(torch.isinf(m) & (m < 0), torch.zeros_like(scale), scale)   # empty shard
+        if mi != 2:
+            # shards that share a +inf maximum count one each, as in torch.logsumexp (exp(inf - inf) is NaN); the
+            # weight pair keeps the NaN: a +inf log-weight makes the loss NaN, as torch.softmax does
+            scale = torch.where(m == gm, torch.ones_like(scale), scale)
         out[mi] = gm
         for si in sums:
             out[si] = (s[:, si] * scale).sum()

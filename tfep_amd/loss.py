@@ -73,7 +73,9 @@ class _LossFunction(torch.autograd.Function):
         loss, stats = module._value(uB, ldj, lw, uA)
         ctx.module = module
         ctx.stats = stats
-        ctx.loss = loss.detach()          # (not the output tensor itself: output -> grad_fn -> ctx -> output is a reference cycle)
+        # the float64 quotient, not the output rounded to the inputs' dtype: the log-weight gradient w (r - loss) then
+        # carries one rounding, its own (and ctx holds no output tensor: output -> grad_fn -> ctx -> output is a cycle)
+        ctx.loss = stats[4] / stats[3] if lw is not None else None       # (only the log-weight gradient reads it)
         ctx.save_for_backward(uB, ldj, lw, uA)
         return loss
 
