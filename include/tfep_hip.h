@@ -1023,6 +1023,50 @@ int tfep_polar_backward_f64(const double* a, const double* b, int to_cartesian, 
         double* ga, double* gb, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Placement of atoms from a Z-matrix: internal coordinates to Cartesian     */
+/* ------------------------------------------------------------------------- */
+
+/*
+ * The inverse of internal_coordinates on the tables of one Z-matrix.  Row (i, j, k, l) with values (d, a, t) places atom i:
+ *     b1 = unit(x_k - x_j),  w = unit of the rejection of x_l - x_k from b1,
+ *     x_i = x_j + d (cos a b1 + sin a (cos t w - sin t (b1 x w)))
+ * so that the distance i-j is d, the angle i-j-k is a and the dihedral i-j-k-l is t in the conventions above; the log-det
+ * of a row is the sum over its placed atoms of 2 log d + log|sin a|.  fp64 arithmetic for both element types, one wave per
+ * row, no atomics, a row's bits do not depend on its batch.
+ *   d, a, t      (B, n_ic), row strides ldd, lda, ldt; column c holds the values of the caller's Z-matrix row c
+ *   x_fixed      (B, 3 n_fixed), row stride ldf: the positions of the atoms of `fixed`, in its order
+ *   rows         (5, n_ic) int32 on the device, row-major, sorted by level: the atom placed, j, k, l, and the column of
+ *                (d, a, t) with its values.  The fixed atoms are level 0, an atom is one level above the highest of its
+ *                references; level_start holds n_levels + 1 offsets into the sorted rows
+ *   x            (B, 3 n_atoms), row stride ldx, n_atoms = n_fixed + n_ic; log_det_J (B)
+ * THE CALLER VALIDATES THE TABLES ON THE HOST (ops.zmatrix_tables): the kernels cannot reject.  They do not dereference
+ * an index out of range -- its atom is NaN or not written --, skip an item that names no row and clip an offset to its
+ * list.  The positions of a row are kept in fp64 in LDS: 24 n_atoms bytes a row forward, 72 n_ic bytes backward, and a
+ * row that needs more than 160 KiB is TFEP_ERR_INVALID_ARGUMENT before anything is launched.
+ *   zmatrix_place_backward: from x (the forward's output), (d, a, t), gx (B, 3 n_atoms; row stride ldgx) and gl (B), the
+ *       cotangents gd, ga, gt (B, n_ic) and g_fixed (B, 3 n_fixed), contiguous, every element written once.  An atom
+ *       receives the contributions of the atoms placed from it in the order of its incidence list: atom_start holds
+ *       n_atoms + 1 offsets into the n_items of atom_items, an item is 4 * sorted row + slot, slot 0, 1, 2 for a row that
+ *       names the atom as j, k, l; the items of an atom ascend.
+ */
+int tfep_zmatrix_place(const float* d, int64_t ldd, const float* a, int64_t lda, const float* t, int64_t ldt,
+        const float* x_fixed, int64_t ldf, const int32_t* rows, int n_ic, const int32_t* level_start, int n_levels,
+        const int32_t* fixed, int n_fixed, float* x, int64_t ldx, float* log_det_J, int n_atoms, int B, void* stream);
+int tfep_zmatrix_place_backward(const float* x, int64_t ldx, const float* d, int64_t ldd, const float* a, int64_t lda,
+        const float* t, int64_t ldt, const int32_t* rows, int n_ic, const int32_t* level_start, int n_levels,
+        const int32_t* fixed, int n_fixed, const int32_t* atom_start, const int32_t* atom_items, int n_items,
+        const float* gx, int64_t ldgx, const float* gl, float* gd, float* ga, float* gt, float* g_fixed, int n_atoms, int B,
+        void* stream);
+int tfep_zmatrix_place_f64(const double* d, int64_t ldd, const double* a, int64_t lda, const double* t, int64_t ldt,
+        const double* x_fixed, int64_t ldf, const int32_t* rows, int n_ic, const int32_t* level_start, int n_levels,
+        const int32_t* fixed, int n_fixed, double* x, int64_t ldx, double* log_det_J, int n_atoms, int B, void* stream);
+int tfep_zmatrix_place_backward_f64(const double* x, int64_t ldx, const double* d, int64_t ldd, const double* a, int64_t lda,
+        const double* t, int64_t ldt, const int32_t* rows, int n_ic, const int32_t* level_start, int n_levels,
+        const int32_t* fixed, int n_fixed, const int32_t* atom_start, const int32_t* atom_items, int n_items,
+        const double* gx, int64_t ldgx, const double* gl, double* gd, double* ga, double* gt, double* g_fixed, int n_atoms,
+        int B, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* TFEP reductions (tfep/loss.py, tfep/analysis/estimator.py)                 */
 /* ------------------------------------------------------------------------- */
 

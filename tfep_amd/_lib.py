@@ -299,7 +299,16 @@ for _s in ('', '_f64'):
         'tfep_polar' + _s: (c_int, [_P, _P, c_int, _P, _P, _P, c_int64, _P]),
         'tfep_polar_backward' + _s: (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_int64, _P]),
     })
-del _SEL, _FRAME, _TABLES, _s
+# placement from a Z-matrix (csrc/zmatrix.hip): (d, a, t) are (pointer, row stride) pairs, the level-sorted tables are
+# (rows, n_ic, level_start, n_levels, fixed, n_fixed)
+_DAT, _ZTABLES = [_P, c_int64] * 3, [_P, c_int] * 3
+for _s in ('', '_f64'):
+    _SIGNATURES.update({
+        'tfep_zmatrix_place' + _s: (c_int, [*_DAT, _P, c_int64, *_ZTABLES, _P, c_int64, _P, c_int, c_int, _P]),
+        'tfep_zmatrix_place_backward' + _s: (c_int, [_P, c_int64, *_DAT, *_ZTABLES, _P, _P, c_int, _P, c_int64, _P,
+                                                     _P, _P, _P, _P, c_int, c_int, _P]),
+    })
+del _SEL, _FRAME, _TABLES, _DAT, _ZTABLES, _s
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

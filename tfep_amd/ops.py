@@ -5,6 +5,7 @@ tensor picks the kernels, ``_dtype`` / ``_sfx``; mixed dtypes are a TypeError), 
 tensor's device and returns fresh output tensors (inputs are never modified, like the reference:
 flows/autoregressive.py:165-166).  No autograd, no CPU path.
 """
+import collections
 import ctypes
 import os
 
@@ -647,6 +648,201 @@ def polar_backward(a, b, to_cartesian, grad_0, grad_1, grad_log_det_J):
     call('tfep_polar_backward' + _sfx(dt), ptr(a), ptr(b), int(bool(to_cartesian)), ptr(g0), ptr(g1),
          ptr(gl[0]) if gl else None, ptr(ga), ptr(gb), a.numel(), stream_of(a))
     return ga, gb
+
+
+# ----------------------------------------------------------------------------- placement from a Z-matrix
+
+ZMATRIX_LDS_LIMIT = 160 * 1024           # bytes of LDS one sample row may take (csrc/zmatrix.hip)
+ZMATRIX_MAX_ATOMS = ZMATRIX_LDS_LIMIT // 24          # the forward keeps 3 doubles per atom
+ZMATRIX_MAX_PLACED = ZMATRIX_LDS_LIMIT // 72         # the backward keeps 9 doubles per placed atom
+ZMatrixTables = collections.namedtuple('ZMatrixTables', 'rows level_start fixed atom_start atom_items')
+_ZMATRIX_CACHE = []          # (key, the caller's (z_matrix, fixed_atoms), (placement tables, index tables)), newest last
+
+
+def _integer_table(table, name):
+    table = torch.as_tensor(table)
+    if table.is_floating_point() or table.is_complex() or table.dtype == torch.bool:
+        raise ValueError(f'{name} must hold integer indices, got {table.dtype}')
+    return table.detach().to('cpu', torch.int64)
+
+
+def check_zmatrix(z_matrix, fixed_atoms, n_atoms):
+    """A Z-matrix on the host: ``z_matrix`` ``(n_ic, 4)`` integer rows ``(i, j, k, l)`` -- atom ``i`` is placed from the
+    atoms ``j, k, l`` -- in any order, ``fixed_atoms`` ``(n_fixed,)`` the atoms whose positions are given.  Returns both as
+    CPU int64 tensors and the level of every row (the fixed atoms are level 0, an atom is one level above the highest of
+    its references).  ValueError unless: integer dtypes; the shapes above; every index in ``[0, n_atoms)`` (a negative
+    entry, bgflow's ``-1`` of a global row, is not supported); four distinct atoms in a row; no atom placed twice, fixed
+    twice, or both; fixed and placed atoms together exactly ``range(n_atoms)``; at least 3 fixed atoms; no cycle; and a
+    size the kernels hold in LDS."""
+    z, fixed = _integer_table(z_matrix, 'z_matrix'), _integer_table(fixed_atoms, 'fixed_atoms')
+    if z.dim() != 2 or z.shape[1] != 4:
+        raise ValueError(f'z_matrix must have shape (n_ic, 4), got {tuple(z.shape)}')
+    if fixed.dim() != 1:
+        raise ValueError(f'fixed_atoms must have shape (n_fixed,), got {tuple(fixed.shape)}')
+    for t, name in ((z, 'z_matrix'), (fixed, 'fixed_atoms')):
+        if t.numel() and int(t.min()) < 0:
+            raise ValueError(f'{name} has a negative entry ({int(t.min())}): rows that place an atom from the global '
+                             'frame are not supported, every reference must be an atom')
+        if t.numel() and int(t.max()) >= n_atoms:
+            raise ValueError(f'{name} has an index outside [0, {n_atoms}): max {int(t.max())}')
+    if len(fixed) < 3:
+        raise ValueError(f'a Z-matrix needs at least 3 fixed atoms to place the first row from, got {len(fixed)}')
+    srt = z.sort(dim=1).values
+    if bool((srt[:, 1:] == srt[:, :-1]).any()):
+        bad = int((srt[:, 1:] == srt[:, :-1]).any(1).nonzero()[0])
+        raise ValueError(f'z_matrix row {bad} {z[bad].tolist()} does not name four distinct atoms')
+    placed_count = torch.bincount(z[:, 0], minlength=n_atoms)
+    fixed_count = torch.bincount(fixed, minlength=n_atoms)
+    if bool((placed_count > 1).any()):
+        raise ValueError(f'atom {int((placed_count > 1).nonzero()[0])} is placed twice')
+    if bool((fixed_count > 1).any()):
+        raise ValueError(f'atom {int((fixed_count > 1).nonzero()[0])} is fixed twice')
+    if bool(((placed_count > 0) & (fixed_count > 0)).any()):
+        raise ValueError(f'atom {int(((placed_count > 0) & (fixed_count > 0)).nonzero()[0])} is both fixed and placed')
+    if bool((placed_count + fixed_count == 0).any()):
+        raise ValueError(f'atom {int((placed_count + fixed_count == 0).nonzero()[0])} of the {n_atoms} atoms is neither '
+                         'fixed nor placed')
+    if n_atoms > ZMATRIX_MAX_ATOMS or len(z) > ZMATRIX_MAX_PLACED:
+        raise ValueError(f'{n_atoms} atoms, {len(z)} of them placed: the kernels keep a row in {ZMATRIX_LDS_LIMIT} bytes of '
+                         f'LDS, which holds at most {ZMATRIX_MAX_ATOMS} atoms and {ZMATRIX_MAX_PLACED} placed atoms')
+    # levels: a row is ready once its three references have a level
+    atom_level = torch.full((n_atoms,), -1, dtype=torch.int64)
+    atom_level[fixed] = 0
+    row_level = torch.full((len(z),), -1, dtype=torch.int64)
+    while bool((row_level < 0).any()):
+        refs = atom_level[z[:, 1:]]
+        ready = (row_level < 0) & (refs >= 0).all(1)
+        if not bool(ready.any()):
+            raise ValueError(f'z_matrix has a cycle: row {int((row_level < 0).nonzero()[0])} can never be placed')
+        row_level[ready] = refs[ready].max(1).values + 1
+        atom_level[z[ready, 0]] = row_level[ready]
+    return z, fixed, row_level
+
+
+def _zmatrix_prepared(z_matrix, fixed_atoms, n_atoms, device):
+    given = (z_matrix, fixed_atoms)
+    cacheable = all(isinstance(t, torch.Tensor) for t in given)
+    key = (int(n_atoms), str(device)) + tuple((id(t), t._version, tuple(t.shape)) for t in given if cacheable)
+    if cacheable:
+        for k, held, prepared in _ZMATRIX_CACHE:
+            if k == key and all(a is b for a, b in zip(held, given)):
+                return prepared
+    z, fixed, row_level = check_zmatrix(z_matrix, fixed_atoms, int(n_atoms))
+    n_ic = len(z)
+    # rows sorted by level, the caller's order kept within a level
+    order = torch.sort(row_level, stable=True).indices
+    n_levels = int(row_level.max()) if n_ic else 0
+    level_start = torch.zeros(n_levels + 1, dtype=torch.int64)
+    if n_ic:
+        level_start[1:] = torch.cumsum(torch.bincount(row_level - 1, minlength=n_levels), 0)
+    rows_ = torch.cat([z[order].t(), order.unsqueeze(0)])                   # (5, n_ic): i, j, k, l, column
+    # sorted row s names atom rows_[1 + slot, s] as reference `slot`: item 4 * s + slot; a stable sort by atom keeps the
+    # items of an atom in table order
+    items = (4 * torch.arange(n_ic).unsqueeze(1) + torch.arange(3).unsqueeze(0)).reshape(-1)
+    atoms = rows_[1:4].t().reshape(-1)
+    by_atom = torch.sort(atoms, stable=True).indices
+    start = torch.zeros(n_atoms + 1, dtype=torch.int64)
+    start[1:] = torch.cumsum(torch.bincount(atoms, minlength=n_atoms), 0)
+    place = ZMatrixTables(*(t.to(torch.int32).contiguous().to(device) for t in (rows_, level_start, fixed, start,
+                                                                              items[by_atom])))
+    # the same Z-matrix for the way back (internal_coordinates): one entry per row, in the caller's order
+    index = index_tables(z[:, :2].t().contiguous(), z[:, :3].t().contiguous(), z.t().contiguous(), int(n_atoms), device)
+    prepared = (place, index, fixed.to(device))
+    if cacheable:
+        _ZMATRIX_CACHE.append((key, given, prepared))
+        del _ZMATRIX_CACHE[:-_TABLE_CACHE_SIZE]
+    return prepared
+
+
+def zmatrix_tables(z_matrix, fixed_atoms, n_atoms, device):
+    """A Z-matrix as the placement kernels take it: validated HERE, on the host (``check_zmatrix``: the kernels cannot
+    reject), then ``ZMatrixTables(rows, level_start, fixed, atom_start, atom_items)`` as int32 tensors on ``device``:
+
+    ``rows`` ``(5, n_ic)``: the Z-matrix rows sorted by level (the caller's order within a level) as columns ``(i, j, k,
+    l)``, and in the fifth row the permutation back: the caller's row, which is the column of ``(d, a, t)`` with the values
+    of that atom.  ``level_start``: ``n_levels + 1`` offsets into the sorted rows.  ``fixed``: the fixed atoms.
+    ``atom_start`` / ``atom_items``: the incidence list the backward kernel gathers over, for every atom the rows placed
+    from it, in sorted order, as ``4 * sorted row + slot`` (slot 0, 1, 2: the atom is the row's j, k, l).
+
+    The last few results are kept, keyed by the identity, version and shape of the two tensors given."""
+    return _zmatrix_prepared(z_matrix, fixed_atoms, n_atoms, device)[0]
+
+
+def zmatrix_index_tables(z_matrix, fixed_atoms, n_atoms, device):
+    """The same Z-matrix for ``internal_coordinates``: ``(index tables, fixed atoms)`` -- the five tensors of
+    ``index_tables`` for the pairs ``(i, j)``, triples ``(i, j, k)`` and quads ``(i, j, k, l)`` of the rows in the caller's
+    order, and the fixed atoms as an int64 tensor on ``device``.  Validated and cached with ``zmatrix_tables``."""
+    return _zmatrix_prepared(z_matrix, fixed_atoms, n_atoms, device)[1:]
+
+
+def _zmatrix_args(tables, n_atoms=None):
+    """The table arguments of the placement entry points, with the sizes ``(n_ic, n_fixed, n_atoms)``."""
+    rows_, level_start, fixed, atom_start, atom_items = tables
+    for t, name in zip(tables, ZMatrixTables._fields):
+        check_device_tensor(t, name, torch.int32)
+        if not t.is_contiguous():
+            raise ValueError(f'{name} must be contiguous: build the tables with ops.zmatrix_tables')
+    if rows_.dim() != 2 or rows_.shape[0] != 5 or level_start.dim() != 1 or level_start.numel() < 1 or fixed.dim() != 1:
+        raise ValueError('rows must be (5, n_ic), level_start (n_levels + 1,) and fixed (n_fixed,): build them with '
+                         'ops.zmatrix_tables')
+    n_ic, n_fixed = rows_.shape[1], fixed.numel()
+    n = n_ic + n_fixed
+    if tuple(atom_start.shape) != (n + 1,) or atom_items.dim() != 1:
+        raise ValueError(f'atom_start must be ({n + 1},) and atom_items 1-D: build both with ops.zmatrix_tables')
+    args = [ptr(rows_), n_ic, ptr(level_start), level_start.numel() - 1, ptr(fixed), n_fixed]
+    return args, n_ic, n_fixed, n
+
+
+def _zmatrix_values(dt, B, n_ic, *named):
+    """The (pointer, row stride) arguments of ``d, a, t``, and the tensors they point into (to be held until the launch)."""
+    args, held = [], []
+    for t, name in named:
+        t, ld = rows(t, name, dt)
+        if tuple(t.shape) != (B, n_ic):
+            raise ValueError(f'{name} must be ({B}, {n_ic}), got {tuple(t.shape)}')
+        args += [ptr(t), ld]
+        held.append(t)
+    return args, held
+
+
+def zmatrix_place(d, a, t, x_fixed, rows_, level_start, fixed, atom_start, atom_items):
+    """``(x, log_det_J)``: the positions (B, 3 n_atoms) of the rows placed from the internal coordinates ``d, a, t`` (B,
+    n_ic; the caller's Z-matrix row order, any row stride) and the fixed atoms ``x_fixed`` (B, 3 n_fixed; any row stride),
+    and the log-det (B,) of the map, in one launch (``tfep_zmatrix_place``).  The five table tensors are those of
+    ``zmatrix_tables``, which validates them.  float64 rows run on the float64 kernels."""
+    dt = _dtype(d)
+    targs, n_ic, n_fixed, n = _zmatrix_args((rows_, level_start, fixed, atom_start, atom_items))
+    x_fixed, ldf = rows(x_fixed, 'x_fixed', dt)
+    B = x_fixed.shape[0]
+    if x_fixed.shape[1] != 3 * n_fixed:
+        raise ValueError(f'x_fixed must be ({B}, {3 * n_fixed}), got {tuple(x_fixed.shape)}')
+    values, held = _zmatrix_values(dt, B, n_ic, (d, 'd'), (a, 'a'), (t, 't'))  # noqa: F841  (held: alive to the launch)
+    x = torch.empty(B, 3 * n, dtype=dt, device=x_fixed.device)
+    ldj = torch.empty(B, dtype=dt, device=x_fixed.device)
+    call('tfep_zmatrix_place' + _sfx(dt), *values, ptr(x_fixed), ldf, *targs, ptr(x), max(3 * n, 1), ptr(ldj), n, B,
+         stream_of(x_fixed))
+    return x, ldj
+
+
+def zmatrix_place_backward(x, d, a, t, rows_, level_start, fixed, atom_start, atom_items, grad_x, grad_log_det_J):
+    """VJP of ``zmatrix_place`` at its output ``x``: the cotangents ``(g_d, g_a, g_t, g_x_fixed)`` in one launch; an atom's
+    contributions are summed in table order, so the result is reproducible bit for bit."""
+    dt = _dtype(x)
+    targs, n_ic, n_fixed, n = _zmatrix_args((rows_, level_start, fixed, atom_start, atom_items))
+    x, ldx = rows(x, 'x', dt)
+    B = x.shape[0]
+    grad_x, ldgx = rows(grad_x, 'grad_x', dt)
+    if x.shape[1] != 3 * n or tuple(grad_x.shape) != tuple(x.shape):
+        raise ValueError(f'x and grad_x must be ({B}, {3 * n}), got {tuple(x.shape)} and {tuple(grad_x.shape)}')
+    gl = check_device_tensor(grad_log_det_J, 'grad_log_det_J', dt).contiguous()
+    if tuple(gl.shape) != (B,):
+        raise ValueError(f'grad_log_det_J must be ({B},), got {tuple(gl.shape)}')
+    values, held = _zmatrix_values(dt, B, n_ic, (d, 'd'), (a, 'a'), (t, 't'))  # noqa: F841  (held: alive to the launch)
+    gd, ga, gt = (torch.empty(B, n_ic, dtype=dt, device=x.device) for _ in range(3))
+    g_fixed = torch.empty(B, 3 * n_fixed, dtype=dt, device=x.device)
+    call('tfep_zmatrix_place_backward' + _sfx(dt), ptr(x), ldx, *values, *targs, ptr(atom_start), ptr(atom_items),
+         atom_items.numel(), ptr(grad_x), ldgx, ptr(gl), ptr(gd), ptr(ga), ptr(gt), ptr(g_fixed), n, B, stream_of(x))
+    return gd, ga, gt, g_fixed
 
 
 def gather_columns(src, idx):

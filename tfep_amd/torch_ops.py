@@ -22,6 +22,8 @@ in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the re
   tfep::internal_coordinates / _backward, polar_forward / polar_backward
                                                                      reference utils/geometry.py:28-178, 414-471
                                                                      (GEOMETRY_OPS)
+  tfep::zmatrix_place / zmatrix_place_backward                       the inverse of internal_coordinates on a Z-matrix
+                                                                     (ZMATRIX_OPS; the reference imports it from bgflow)
   tfep::masked_linear / masked_linear_backward                       reference masked.py:220-302, 351-404
   tfep::fused_output_transformer                                     masked.py:188-208 (last layer) + the transformer
   tfep::tfep_reduce                                                  loss.py:125-140, analysis/estimator.py:73-86
@@ -604,6 +606,44 @@ internal_coordinates.register_autograd(_internal_coordinates_bwd, setup_context=
 polar_forward.register_autograd(_polar_bwd, setup_context=_polar_setup)
 
 
+# ============================================================================= placement from a Z-matrix
+
+@custom_op('tfep::zmatrix_place', mutates_args=(), device_types=_DEV)
+def zmatrix_place(d: Tensor, a: Tensor, t: Tensor, x_fixed: Tensor, rows: Tensor, level_start: Tensor, fixed: Tensor,
+                  atom_start: Tensor, atom_items: Tensor) -> Tuple[Tensor, Tensor]:
+    """``(x, log_det_J)``: the rows (B, 3 n_atoms) placed from ``d, a, t`` (B, n_ic) and the fixed atoms ``x_fixed`` (B,
+    3 n_fixed) over the int32 tables of ``ops.zmatrix_tables`` (which validates them on the host; the incidence list
+    serves the backward)."""
+    return ops.zmatrix_place(d, a, t, x_fixed, rows, level_start, fixed, atom_start, atom_items)
+
+
+@custom_op('tfep::zmatrix_place_backward', mutates_args=(), device_types=_DEV)
+def zmatrix_place_backward(x: Tensor, d: Tensor, a: Tensor, t: Tensor, rows: Tensor, level_start: Tensor, fixed: Tensor,
+                           atom_start: Tensor, atom_items: Tensor, grad_x: Tensor,
+                           grad_log_det_J: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    return ops.zmatrix_place_backward(x, d, a, t, rows, level_start, fixed, atom_start, atom_items, grad_x, grad_log_det_J)
+
+
+zmatrix_place.register_fake(lambda d, a, t, x_fixed, rows, level_start, fixed, atom_start, atom_items: (
+    d.new_empty((d.shape[0], 3 * (rows.shape[1] + fixed.shape[0]))), d.new_empty((d.shape[0],))))
+zmatrix_place_backward.register_fake(lambda x, d, a, t, rows, level_start, fixed, *rest: (
+    d.new_empty(d.shape), d.new_empty(d.shape), d.new_empty(d.shape), d.new_empty((d.shape[0], 3 * fixed.shape[0]))))
+
+
+def _zmatrix_place_setup(ctx, inputs, output):
+    d, a, t, _, *tables = inputs
+    ctx.save_for_backward(output[0], d, a, t, *tables)
+    ctx.like = tuple(_meta(o) for o in output)
+
+
+def _zmatrix_place_bwd(ctx, g_x, g_l):
+    grads = (_or_zeros(g, like) for g, like in zip((g_x, g_l), ctx.like))
+    return (*torch.ops.tfep.zmatrix_place_backward(*ctx.saved_tensors, *grads), *([None] * 5))
+
+
+zmatrix_place.register_autograd(_zmatrix_place_bwd, setup_context=_zmatrix_place_setup)
+
+
 # ============================================================================= masked linear
 
 @custom_op('tfep::masked_linear', mutates_args=(), device_types=_DEV)
@@ -758,3 +798,4 @@ FLIP_EMBEDDING_OPS = ('flip_invariant_embedding', 'flip_invariant_embedding_back
 FRAME_OPS = ('centroid_shift', 'centroid_restore', 'frame_orient', 'frame_rotate', 'centroid_shift_backward',
              'centroid_restore_backward', 'frame_orient_backward', 'frame_rotate_backward')
 GEOMETRY_OPS = ('internal_coordinates', 'internal_coordinates_backward', 'polar_forward', 'polar_backward')
+ZMATRIX_OPS = ('zmatrix_place', 'zmatrix_place_backward')

@@ -12,6 +12,10 @@ dihedrals from point INDICES in one HIP launch, forward and backward (``csrc/geo
 functions that take difference VECTORS (``vector_vector_angle``, ``vector_plane_angle``, ``proper_dihedral_angle``) and
 ``rotation_matrix_3d`` are torch expressions on the device of their inputs, which are materialised already.
 ``cartesian_to_polar`` / ``polar_to_cartesian`` run on the element-wise polar kernel.
+
+Z-matrices: ``cartesian_to_zmatrix`` is ``internal_coordinates`` on the tables of a Z-matrix, ``zmatrix_to_cartesian`` places
+the atoms back, level by level of the dependency graph, in one HIP launch forward and one backward (``csrc/zmatrix.hip``);
+each returns the log-det of its direction.  The reference takes this step from ``bgflow``.
 """
 from functools import lru_cache
 from typing import Optional, Tuple
@@ -68,6 +72,62 @@ def pdist(x, pairs=None, return_diff=False):
     if x.dim() != 3 or x.shape[2] != 3:
         raise ValueError(f'pdist without return_diff takes (batch, n_particles, 3) positions, got {tuple(x.shape)}')
     return internal_coordinates(x, pairs=pairs)[0]
+
+
+def _n_atoms(z_matrix, fixed_atoms):
+    return len(z_matrix) + len(fixed_atoms)
+
+
+def zmatrix_to_cartesian(d, a, t, x_fixed, z_matrix, fixed_atoms):
+    """Place the atoms of a batch of configurations from a Z-matrix, in one HIP launch: the inverse of
+    ``cartesian_to_zmatrix``.
+
+    ``z_matrix``: ``(n_ic, 4)`` integer rows ``(i, j, k, l)`` in any order -- atom ``i`` is placed at distance ``d`` from
+    ``j``, angle ``a`` (``i``-``j``-``k``) and dihedral ``t`` (``i``-``j``-``k``-``l``), in the conventions of
+    ``internal_coordinates``.  ``fixed_atoms``: ``(n_fixed,)`` the atoms whose positions are given, at least three; fixed
+    and placed atoms together are all ``n_ic + n_fixed`` atoms.  Both on any device, validated on the host (ValueError;
+    ``ops.check_zmatrix``); pass the same tensor objects at every call and they are validated and uploaded once.
+    ``d``, ``a``, ``t``: ``(batch_size, n_ic)``, column ``c`` for row ``c`` of ``z_matrix``; ``x_fixed``: ``(batch_size,
+    n_fixed, 3)`` or ``(batch_size, 3 n_fixed)`` in the order of ``fixed_atoms``.  float32 or float64 HIP tensors of one
+    dtype (column slices of wider tensors are read in place).
+
+    Returns ``(x, log_det_J)``: the positions in the layout of ``x_fixed`` with all atoms, and the log absolute Jacobian
+    determinant ``sum(2 log d + log|sin a|)`` of ``(d, a, t, x_fixed) -> x``.  Differentiable in ``d``, ``a``, ``t`` and
+    ``x_fixed``; the backward is one launch and reproducible bit for bit.  Degenerate input (``d = 0``, ``sin a = 0``,
+    collinear reference atoms) gives NaN or infinite values."""
+    atoms_3d = x_fixed.dim() == 3 and x_fixed.shape[2] == 3
+    if atoms_3d:
+        x_fixed = x_fixed.reshape(x_fixed.shape[0], -1)
+    if x_fixed.dim() != 2 or x_fixed.shape[1] != 3 * len(fixed_atoms):
+        raise ValueError(f'x_fixed must be (batch, {len(fixed_atoms)}, 3) or (batch, {3 * len(fixed_atoms)}), got '
+                         f'{tuple(x_fixed.shape)}')
+    tables = ops.zmatrix_tables(z_matrix, fixed_atoms, _n_atoms(z_matrix, fixed_atoms), x_fixed.device)
+    for v, name in ((d, 'd'), (a, 'a'), (t, 't'), (x_fixed, 'x_fixed')):          # one dtype, on the HIP device
+        ops.check_device_tensor(v, name, ops._dtype(d))
+    x, log_det_J = torch.ops.tfep.zmatrix_place(d, a, t, x_fixed, *tables)
+    return (x.reshape(x.shape[0], -1, 3) if atoms_3d else x), log_det_J
+
+
+def cartesian_to_zmatrix(x, z_matrix, fixed_atoms):
+    """The internal coordinates of a Z-matrix, on the ``internal_coordinates`` kernel: the inverse of
+    ``zmatrix_to_cartesian`` (see there for ``z_matrix`` and ``fixed_atoms``).
+
+    ``x``: ``(batch_size, n_atoms, 3)`` or ``(batch_size, 3 n_atoms)``, float32 or float64 HIP tensor.  Returns ``(d, a, t,
+    x_fixed, log_det_J)``: ``d``, ``a``, ``t`` ``(batch_size, n_ic)`` in the row order of ``z_matrix``, ``a`` in ``[0, pi]``
+    and ``t`` in ``(-pi, pi]``; ``x_fixed`` the positions of ``fixed_atoms`` in the layout of ``x``; and the log absolute
+    Jacobian determinant ``-sum(2 log d + log|sin a|)`` of ``x -> (d, a, t, x_fixed)``.  Differentiable in ``x``."""
+    atoms_3d = x.dim() == 3 and x.shape[2] == 3
+    if atoms_3d:
+        x = x.reshape(x.shape[0], -1)
+    n_atoms = _n_atoms(z_matrix, fixed_atoms)
+    if x.dim() != 2 or x.shape[1] != 3 * n_atoms:
+        raise ValueError(f'x must be (batch, {n_atoms}, 3) or (batch, {3 * n_atoms}), got {tuple(x.shape)}')
+    tables, fixed = ops.zmatrix_index_tables(z_matrix, fixed_atoms, n_atoms, x.device)
+    ops.check_device_tensor(x, 'x', ops._dtype(x))
+    d, a, t = torch.ops.tfep.internal_coordinates(x, *tables)
+    x_fixed = x.reshape(x.shape[0], n_atoms, 3).index_select(1, fixed)
+    log_det_J = -(2.0 * torch.log(d) + torch.log(torch.abs(torch.sin(a)))).sum(1)
+    return d, a, t, (x_fixed if atoms_3d else x_fixed.reshape(x.shape[0], -1)), log_det_J
 
 
 def vector_vector_angle(x1, x2):
