@@ -1067,6 +1067,57 @@ int tfep_zmatrix_place_backward_f64(const double* x, int64_t ldx, const double* 
         int B, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* The relative frame of the mixed coordinates (app/mixedmaf.py:1216-1375)    */
+/* ------------------------------------------------------------------------- */
+
+/*
+ * The Cartesian atoms of a row in the frame of three of them, and back; one launch each, fp64 arithmetic for both element
+ * types (csrc/relframe.h has the formulas).
+ *   x          (B, 3 n_c), row stride ldx: n_c >= 3 atoms, THE LAST THREE the origin, axis and plane atoms, in that order
+ *   remove_*   non-zero: the rototranslational DOFs of that reference atom (origin 3, axis 2, plane 1) are left out of coords
+ *   coords     (B, W), row stride ldc, W = 3 + 3 (n_c - 3) + kept:  [d01, d02, a102n | v_i = R (x_i - o) of the n_c - 3 other
+ *              atoms | kept DOFs: v_origin (3), (v_axis)_y,z (2), (v_plane)_z (1)],  d01 = (v_axis)_x, d02 =
+ *              hypot((v_plane)_x,y), a102n = (atan2((v_plane)_y, (v_plane)_x) + pi) / (2 pi)
+ *   origin     (B, 3) the origin atom;  R (B, 9, row-major 3 x 3) the rotation of reference_frame_rotation_matrix(a - o,
+ *              p - o, e_x, e_y, project_on_positive_axis=True): no flip, and the rotation by pi about -e_z when the axis
+ *              vector is antiparallel to e_x (1 + c <= 1e-12)
+ *   log_det_J  (B):  encode -log d02 - log 2 pi,  decode log 2 pi + log d02
+ *   encode:    x -> (coords, origin, R, log_det_J)
+ *   decode:    (coords, origin, R) -> (x, log_det_J),  x_i = R^T v_i + o; a removed DOF is exactly 0
+ *   *_backward: encode (g_coords, g_origin, g_R, g_log_det_J) -> gx; decode (gx, g_log_det_J) -> (g_coords, g_origin, g_R).
+ *              g_origin, g_R and g_log_det_J may be NULL where they are inputs (no cotangent).
+ * n_c < 3 and a row stride shorter than its row are invalid arguments.  Degenerate geometry is not special-cased: a
+ * zero-length axis vector gives NaN, d02 = 0 an infinite log-det.
+ */
+int tfep_relative_frame_encode(const float* x, int64_t ldx, int n_c, int remove_origin, int remove_axis, int remove_plane,
+                               float* coords, int64_t ldc, float* origin, float* R, float* log_det_J, int B, void* stream);
+int tfep_relative_frame_encode_f64(const double* x, int64_t ldx, int n_c, int remove_origin, int remove_axis,
+                                   int remove_plane, double* coords, int64_t ldc, double* origin, double* R,
+                                   double* log_det_J, int B, void* stream);
+int tfep_relative_frame_encode_backward(const float* x, int64_t ldx, int n_c, int remove_origin, int remove_axis,
+                                        int remove_plane, const float* g_coords, int64_t ldgc, const float* g_origin,
+                                        const float* g_R, const float* g_log_det_J, float* gx, int64_t ldgx, int B,
+                                        void* stream);
+int tfep_relative_frame_encode_backward_f64(const double* x, int64_t ldx, int n_c, int remove_origin, int remove_axis,
+                                            int remove_plane, const double* g_coords, int64_t ldgc, const double* g_origin,
+                                            const double* g_R, const double* g_log_det_J, double* gx, int64_t ldgx, int B,
+                                            void* stream);
+int tfep_relative_frame_decode(const float* coords, int64_t ldc, const float* origin, const float* R, int n_c,
+                               int remove_origin, int remove_axis, int remove_plane, float* x, int64_t ldx,
+                               float* log_det_J, int B, void* stream);
+int tfep_relative_frame_decode_f64(const double* coords, int64_t ldc, const double* origin, const double* R, int n_c,
+                                   int remove_origin, int remove_axis, int remove_plane, double* x, int64_t ldx,
+                                   double* log_det_J, int B, void* stream);
+int tfep_relative_frame_decode_backward(const float* coords, int64_t ldc, const float* origin, const float* R, int n_c,
+                                        int remove_origin, int remove_axis, int remove_plane, const float* gx, int64_t ldgx,
+                                        const float* g_log_det_J, float* g_coords, int64_t ldgc, float* g_origin, float* g_R,
+                                        int B, void* stream);
+int tfep_relative_frame_decode_backward_f64(const double* coords, int64_t ldc, const double* origin, const double* R,
+                                            int n_c, int remove_origin, int remove_axis, int remove_plane, const double* gx,
+                                            int64_t ldgx, const double* g_log_det_J, double* g_coords, int64_t ldgc,
+                                            double* g_origin, double* g_R, int B, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* TFEP reductions (tfep/loss.py, tfep/analysis/estimator.py)                 */
 /* ------------------------------------------------------------------------- */
 

@@ -308,7 +308,18 @@ for _s in ('', '_f64'):
         'tfep_zmatrix_place_backward' + _s: (c_int, [_P, c_int64, *_DAT, *_ZTABLES, _P, _P, c_int, _P, c_int64, _P,
                                                      _P, _P, _P, _P, c_int, c_int, _P]),
     })
-del _SEL, _FRAME, _TABLES, _DAT, _ZTABLES, _s
+# the relative frame of the mixed coordinates (csrc/relframe.hip): (n_c, remove_origin, remove_axis, remove_plane)
+_REL = [c_int] * 4
+for _s in ('', '_f64'):
+    _SIGNATURES.update({
+        'tfep_relative_frame_encode' + _s: (c_int, [_P, c_int64, *_REL, _P, c_int64, _P, _P, _P, c_int, _P]),
+        'tfep_relative_frame_encode_backward' + _s: (c_int, [_P, c_int64, *_REL, _P, c_int64, _P, _P, _P, _P, c_int64, c_int,
+                                                             _P]),
+        'tfep_relative_frame_decode' + _s: (c_int, [_P, c_int64, _P, _P, *_REL, _P, c_int64, _P, c_int, _P]),
+        'tfep_relative_frame_decode_backward' + _s: (c_int, [_P, c_int64, _P, _P, *_REL, _P, c_int64, _P, _P, c_int64, _P, _P,
+                                                             c_int, _P]),
+    })
+del _SEL, _FRAME, _TABLES, _DAT, _ZTABLES, _REL, _s
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

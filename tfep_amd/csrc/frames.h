@@ -12,6 +12,11 @@
 // torch code gives; so does a plane point on the axis with q_p != 0 rounded to it (|(q_p, q_n)| = 0 is reached only with
 // q_p == 0, which is the identity branch).
 //
+// frame_rotation<false> is the project_on_positive_axis=True variant (relframe.h): u = a / |a| with no flip, c in [-1, 1],
+// and when 1 + c <= 1e-12 (a antiparallel to e_axis) R1 is the rotation by pi about e_plane x e_axis, 2 n n^T - I -- a
+// constant, so that branch has zero derivative with respect to a, as torch.where gives it.  The default, <true>, is the
+// arithmetic above, unchanged.
+//
 // frame_rotation_vjp is the reverse-mode derivative of frame_rotation, written out by hand: the cotangent of R (row-major
 // 3 x 3) gives the cotangents of a and p.  The q_p == 0 branch has zero derivative with respect to q, as torch.where
 // gives it.
@@ -21,6 +26,8 @@
 #include <stdint.h>
 
 namespace tfep {
+
+constexpr int FRAME_ROWS = 4;               // rows (waves) per workgroup of the kernels of frames.hip and relframe.hip
 
 // The frame in small integers: `axis` and `plane_axis` in 0..2 (x, y, z), `normal` = +-(1 + index of the third axis), the
 // sign that of the plane normal (for OrientedFlow: e_axis x e_plane).
@@ -37,6 +44,7 @@ __host__ __device__ inline bool frame_axes_valid(const FrameAxes& f) {
 // What frame_rotation_vjp needs of the forward.
 struct FrameState {
     double na, flip, u0[3], K[3][3], s, r1[3][3], r2[3][3], qp, qn, qnorm, sgn;
+    bool antiparallel;          // (frame_rotation<false> only: R1 is the constant rotation by pi)
 };
 
 // v[i] for a run-time i, without indexing a register array dynamically
@@ -56,6 +64,7 @@ __host__ __device__ inline void skew3(const double (&w)[3], double (&K)[3][3]) {
     K[2][0] = -w[1], K[2][1] = w[0], K[2][2] = 0.0;
 }
 
+template <bool FLIP = true>
 __host__ __device__ inline void frame_rotation(const double (&a)[3], const double (&p)[3], const FrameAxes& f,
                                                double (&R)[3][3], FrameState& st) {
     const int ax = f.axis, pl = f.plane_axis, nn = (f.normal < 0 ? -f.normal : f.normal) - 1;
@@ -65,7 +74,7 @@ __host__ __device__ inline void frame_rotation(const double (&a)[3], const doubl
     unit3(ax, e);
 #pragma unroll
     for (int i = 0; i < 3; ++i) st.u0[i] = a[i] / st.na;
-    st.flip = sel3(st.u0, ax) < 0.0 ? -1.0 : 1.0;
+    st.flip = (FLIP && sel3(st.u0, ax) < 0.0) ? -1.0 : 1.0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) u[i] = st.u0[i] * st.flip;
     const double c = sel3(u, ax);
@@ -79,6 +88,13 @@ __host__ __device__ inline void frame_rotation(const double (&a)[3], const doubl
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) st.r1[i][j] = (i == j ? 1.0 : 0.0) + st.K[i][j] + KK[i][j] * st.s;
+    st.antiparallel = !FLIP && !(denom > 1e-12);
+    if (st.antiparallel) {                        // n = e_plane x e_axis = -sn e_normal: 2 n n^T - I
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) st.r1[i][j] = (i == j ? (i == nn ? 1.0 : -1.0) : 0.0);
+    }
     double q[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) q[i] = st.r1[i][0] * p[0] + st.r1[i][1] * p[1] + st.r1[i][2] * p[2];
@@ -103,6 +119,7 @@ __host__ __device__ inline void frame_rotation(const double (&a)[3], const doubl
 }
 
 // Cotangents of the axis point (ga) and the plane point (gp) from the cotangent G of R.
+template <bool FLIP = true>
 __host__ __device__ inline void frame_rotation_vjp(const double (&p)[3], const FrameAxes& f, const FrameState& st,
                                                    const double (&G)[3][3], double (&ga)[3], double (&gp)[3]) {
     const int ax = f.axis, pl = f.plane_axis, nn = (f.normal < 0 ? -f.normal : f.normal) - 1;
@@ -142,6 +159,10 @@ __host__ __device__ inline void frame_rotation_vjp(const double (&p)[3], const F
         gp[i] = st.r1[0][i] * gq[0] + st.r1[1][i] * gq[1] + st.r1[2][i] * gq[2];
 #pragma unroll
         for (int j = 0; j < 3; ++j) G1[i][j] += gq[i] * p[j];
+    }
+    if (!FLIP && st.antiparallel) {               // r1 is a constant
+        ga[0] = ga[1] = ga[2] = 0.0;
+        return;
     }
     // r1 = I + K + s K K
     double KK[3][3], GK[3][3];

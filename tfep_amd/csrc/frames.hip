@@ -17,7 +17,6 @@
 
 namespace tfep {
 
-constexpr int FRAME_ROWS = 4;               // rows (waves) per workgroup
 constexpr int FRAME_MAX_DIM = 3;
 
 __device__ __forceinline__ int frame_row() { return blockIdx.x * FRAME_ROWS + (threadIdx.x >> 6); }

@@ -3,7 +3,8 @@
 The way in is ``cartesian_to_zmatrix`` (the ``internal_coordinates`` kernel), the way back ``zmatrix_to_cartesian`` (the
 placement kernel, ``csrc/zmatrix.hip``), one launch each and one more for each backward.  This is the coordinate change
 of the reference's ``MixedMAFMap`` (``app/mixedmaf.py:954-1400``, which imports it from ``bgflow``) and nothing else of
-it: the removal of the reference frame and the normalisation of the torsions are not part of this module.
+it: the removal of the reference frame and the normalisation of the torsions are not part of this module; they are in
+``CartesianToMixedFlow`` (``nn/flows/mixed.py``), which is the whole coordinate change.
 """
 from typing import Tuple
 

@@ -845,6 +845,113 @@ def zmatrix_place_backward(x, d, a, t, rows_, level_start, fixed, atom_start, at
     return gd, ga, gt, g_fixed
 
 
+# ----------------------------------------------------------------------------- the relative frame of mixed coordinates
+
+def _remove_flags(remove):
+    flags = tuple(int(bool(r)) for r in remove)
+    if len(flags) != 3:
+        raise ValueError(f'remove must hold 3 flags (origin, axis, plane), got {len(flags)}')
+    return flags
+
+
+def relative_frame_width(n_c, remove):
+    """The number of coordinates ``relative_frame_encode`` makes of ``n_c`` atoms: ``d01, d02, a102n``, 3 for every atom
+    that is no reference atom, and the reference DOFs that ``remove`` keeps (origin 3, axis 2, plane 1)."""
+    ro, ra, rp = _remove_flags(remove)
+    return 3 + 3 * (int(n_c) - 3) + 3 * (1 - ro) + 2 * (1 - ra) + (1 - rp)
+
+
+def _relative_frame_atoms(x, name):
+    n_c = _points(x, 3, name)
+    if n_c < 3:
+        raise ValueError(f'{name} holds {n_c} atoms: the relative frame needs the origin, axis and plane atoms (n_c >= 3)')
+    return n_c
+
+
+def _relative_frame_n_c(coords, remove):
+    """The number of atoms behind a row of ``coords``; ValueError when the width disagrees with ``remove``."""
+    extra = coords.shape[1] - relative_frame_width(3, remove)
+    if extra < 0 or extra % 3 != 0:
+        raise ValueError(f'coords has {coords.shape[1]} columns, which is not 3 + 3 (n_c - 3) + the kept reference DOFs '
+                         f'({relative_frame_width(3, remove) - 3}) for remove={tuple(bool(r) for r in remove)}')
+    return 3 + extra // 3
+
+
+def _per_row(t, name, width, B, dt):
+    t = check_device_tensor(t, name, dt).contiguous()
+    if tuple(t.shape) != ((B, width) if width else (B,)):
+        raise ValueError(f'{name} must be ({B}, {width}), got {tuple(t.shape)}' if width else
+                         f'{name} must be ({B},), got {tuple(t.shape)}')
+    return t
+
+
+def relative_frame_encode(x_cart, remove):
+    """``(coords, origin, R, log_det_J)``: the atoms of the rows ``x_cart`` (B, 3 n_c; any row stride), whose LAST THREE are
+    the origin, axis and plane atoms, in the frame of those three (``tfep_relative_frame_encode``; csrc/relframe.h).
+    ``coords`` (B, ``relative_frame_width(n_c, remove)``), ``origin`` (B, 3), ``R`` (B, 9), ``log_det_J`` (B,).  float64 rows
+    run on the float64 kernels."""
+    dt = _dtype(x_cart)
+    x, ldx = rows(x_cart, 'x_cart', dt)
+    B, n_c, remove = x.shape[0], _relative_frame_atoms(x, 'x_cart'), _remove_flags(remove)
+    width = relative_frame_width(n_c, remove)
+    coords = torch.empty(B, width, dtype=dt, device=x.device)
+    origin, rot, ldj = (torch.empty(B, *s, dtype=dt, device=x.device) for s in ((3,), (9,), ()))
+    call('tfep_relative_frame_encode' + _sfx(dt), ptr(x), ldx, n_c, *remove, ptr(coords), width, ptr(origin), ptr(rot),
+         ptr(ldj), B, stream_of(x))
+    return coords, origin, rot, ldj
+
+
+def relative_frame_encode_backward(x_cart, remove, grad_coords, grad_origin, grad_rot, grad_log_det_J):
+    """VJP of ``relative_frame_encode`` at ``x_cart``: the cotangent of ``x_cart`` from those of the four outputs,
+    including the dependence of ``R`` and ``origin`` on the reference atoms."""
+    dt = _dtype(x_cart)
+    x, ldx = rows(x_cart, 'x_cart', dt)
+    B, n_c, remove = x.shape[0], _relative_frame_atoms(x, 'x_cart'), _remove_flags(remove)
+    gc, ldgc = rows(grad_coords, 'grad_coords', dt)
+    if tuple(gc.shape) != (B, relative_frame_width(n_c, remove)):
+        raise ValueError(f'grad_coords must be ({B}, {relative_frame_width(n_c, remove)}), got {tuple(gc.shape)}')
+    go, gr, gl = (_per_row(grad_origin, 'grad_origin', 3, B, dt), _per_row(grad_rot, 'grad_rot', 9, B, dt),
+                  _per_row(grad_log_det_J, 'grad_log_det_J', 0, B, dt))
+    gx = torch.empty(B, 3 * n_c, dtype=dt, device=x.device)
+    call('tfep_relative_frame_encode_backward' + _sfx(dt), ptr(x), ldx, n_c, *remove, ptr(gc), ldgc, ptr(go), ptr(gr),
+         ptr(gl), ptr(gx), 3 * n_c, B, stream_of(x))
+    return gx
+
+
+def relative_frame_decode(coords, origin, rot, remove):
+    """``(x_cart, log_det_J)``: the inverse of ``relative_frame_encode`` (``tfep_relative_frame_decode``) from ``coords`` (B,
+    W; any row stride), ``origin`` (B, 3) and ``R`` (B, 9).  A removed reference DOF is exactly 0 in the frame, a kept one is
+    read from ``coords``.  A width that disagrees with ``remove`` is a ValueError."""
+    dt = _dtype(coords)
+    c, ldc = rows(coords, 'coords', dt)
+    B, remove = c.shape[0], _remove_flags(remove)
+    n_c = _relative_frame_n_c(c, remove)
+    origin, rot = _per_row(origin, 'origin', 3, B, dt), _per_row(rot, 'R', 9, B, dt)
+    x = torch.empty(B, 3 * n_c, dtype=dt, device=c.device)
+    ldj = torch.empty(B, dtype=dt, device=c.device)
+    call('tfep_relative_frame_decode' + _sfx(dt), ptr(c), ldc, ptr(origin), ptr(rot), n_c, *remove, ptr(x), 3 * n_c,
+         ptr(ldj), B, stream_of(c))
+    return x, ldj
+
+
+def relative_frame_decode_backward(coords, origin, rot, remove, grad_x_cart, grad_log_det_J):
+    """VJP of ``relative_frame_decode``: the cotangents ``(g_coords, g_origin, g_R)``."""
+    dt = _dtype(coords)
+    c, ldc = rows(coords, 'coords', dt)
+    B, remove = c.shape[0], _remove_flags(remove)
+    n_c = _relative_frame_n_c(c, remove)
+    origin, rot = _per_row(origin, 'origin', 3, B, dt), _per_row(rot, 'R', 9, B, dt)
+    gx, ldgx = rows(grad_x_cart, 'grad_x_cart', dt)
+    if tuple(gx.shape) != (B, 3 * n_c):
+        raise ValueError(f'grad_x_cart must be ({B}, {3 * n_c}), got {tuple(gx.shape)}')
+    gl = _per_row(grad_log_det_J, 'grad_log_det_J', 0, B, dt)
+    gc = torch.empty(B, c.shape[1], dtype=dt, device=c.device)
+    go, gr = torch.empty(B, 3, dtype=dt, device=c.device), torch.empty(B, 9, dtype=dt, device=c.device)
+    call('tfep_relative_frame_decode_backward' + _sfx(dt), ptr(c), ldc, ptr(origin), ptr(rot), n_c, *remove, ptr(gx), ldgx,
+         ptr(gl), ptr(gc), c.shape[1], ptr(go), ptr(gr), B, stream_of(c))
+    return gc, go, gr
+
+
 def gather_columns(src, idx):
     dt = _dtype(src)
     src, lds = rows(src, 'src', dt)

@@ -24,6 +24,9 @@ in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the re
                                                                      (GEOMETRY_OPS)
   tfep::zmatrix_place / zmatrix_place_backward                       the inverse of internal_coordinates on a Z-matrix
                                                                      (ZMATRIX_OPS; the reference imports it from bgflow)
+  tfep::relative_frame_encode / relative_frame_decode, each with its _backward
+                                                                     reference app/mixedmaf.py:1216-1271, 1321-1375
+                                                                     (RELATIVE_FRAME_OPS)
   tfep::masked_linear / masked_linear_backward                       reference masked.py:220-302, 351-404
   tfep::fused_output_transformer                                     masked.py:188-208 (last layer) + the transformer
   tfep::tfep_reduce                                                  loss.py:125-140, analysis/estimator.py:73-86
@@ -644,6 +647,87 @@ def _zmatrix_place_bwd(ctx, g_x, g_l):
 zmatrix_place.register_autograd(_zmatrix_place_bwd, setup_context=_zmatrix_place_setup)
 
 
+# ============================================================================= relative frame of the mixed coordinates
+
+@custom_op('tfep::relative_frame_encode', mutates_args=(), device_types=_DEV)
+def relative_frame_encode(x_cart: Tensor, remove_origin: bool, remove_axis: bool,
+                          remove_plane: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``(coords, origin, R, log_det_J)`` of the rows ``x_cart`` (B, 3 n_c), whose last three atoms are the origin, axis and
+    plane atoms: ``[d01, d02, a102n | the other atoms in the frame | kept reference DOFs]``, (B, 3), (B, 9), (B,).  float32
+    or float64; fewer than 3 atoms is a ValueError."""
+    return ops.relative_frame_encode(x_cart, (remove_origin, remove_axis, remove_plane))
+
+
+@custom_op('tfep::relative_frame_encode_backward', mutates_args=(), device_types=_DEV)
+def relative_frame_encode_backward(x_cart: Tensor, remove_origin: bool, remove_axis: bool, remove_plane: bool,
+                                   grad_coords: Tensor, grad_origin: Tensor, grad_rot: Tensor,
+                                   grad_log_det_J: Tensor) -> Tensor:
+    return ops.relative_frame_encode_backward(x_cart, (remove_origin, remove_axis, remove_plane), grad_coords, grad_origin,
+                                              grad_rot, grad_log_det_J)
+
+
+@custom_op('tfep::relative_frame_decode', mutates_args=(), device_types=_DEV)
+def relative_frame_decode(coords: Tensor, origin: Tensor, rot: Tensor, remove_origin: bool, remove_axis: bool,
+                          remove_plane: bool) -> Tuple[Tensor, Tensor]:
+    """``(x_cart, log_det_J)`` from the outputs of ``relative_frame_encode``; all of one dtype (else TypeError), a width of
+    ``coords`` that disagrees with the flags is a ValueError."""
+    return ops.relative_frame_decode(coords, origin, rot, (remove_origin, remove_axis, remove_plane))
+
+
+@custom_op('tfep::relative_frame_decode_backward', mutates_args=(), device_types=_DEV)
+def relative_frame_decode_backward(coords: Tensor, origin: Tensor, rot: Tensor, remove_origin: bool, remove_axis: bool,
+                                   remove_plane: bool, grad_x_cart: Tensor,
+                                   grad_log_det_J: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(g_coords, g_origin, g_R)``."""
+    return ops.relative_frame_decode_backward(coords, origin, rot, (remove_origin, remove_axis, remove_plane), grad_x_cart,
+                                              grad_log_det_J)
+
+
+@relative_frame_encode.register_fake
+def _(x_cart, remove_origin, remove_axis, remove_plane):
+    B, n_c = x_cart.shape[0], x_cart.shape[1] // 3
+    width = ops.relative_frame_width(n_c, (remove_origin, remove_axis, remove_plane))
+    return x_cart.new_empty((B, width)), x_cart.new_empty((B, 3)), x_cart.new_empty((B, 9)), x_cart.new_empty((B,))
+
+
+@relative_frame_decode.register_fake
+def _(coords, origin, rot, remove_origin, remove_axis, remove_plane):
+    n_c = 3 + (coords.shape[1] - ops.relative_frame_width(3, (remove_origin, remove_axis, remove_plane))) // 3
+    return coords.new_empty((coords.shape[0], 3 * n_c)), coords.new_empty((coords.shape[0],))
+
+
+relative_frame_encode_backward.register_fake(lambda x_cart, *rest: x_cart.new_empty(x_cart.shape))
+relative_frame_decode_backward.register_fake(lambda coords, origin, rot, *rest: (
+    coords.new_empty(coords.shape), origin.new_empty(origin.shape), rot.new_empty(rot.shape)))
+
+
+def _relative_frame_encode_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0])
+    ctx.remove = tuple(inputs[1:])
+    ctx.like = tuple(_meta(o) for o in output)
+
+
+def _relative_frame_encode_bwd(ctx, g_coords, g_origin, g_rot, g_l):
+    (x_cart,) = ctx.saved_tensors
+    grads = (_or_zeros(g, like) for g, like in zip((g_coords, g_origin, g_rot, g_l), ctx.like))
+    return torch.ops.tfep.relative_frame_encode_backward(x_cart, *ctx.remove, *grads), None, None, None
+
+
+def _relative_frame_decode_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:3])
+    ctx.remove = tuple(inputs[3:])
+    ctx.like = tuple(_meta(o) for o in output)
+
+
+def _relative_frame_decode_bwd(ctx, g_x, g_l):
+    grads = (_or_zeros(g, like) for g, like in zip((g_x, g_l), ctx.like))
+    return (*torch.ops.tfep.relative_frame_decode_backward(*ctx.saved_tensors, *ctx.remove, *grads), None, None, None)
+
+
+relative_frame_encode.register_autograd(_relative_frame_encode_bwd, setup_context=_relative_frame_encode_setup)
+relative_frame_decode.register_autograd(_relative_frame_decode_bwd, setup_context=_relative_frame_decode_setup)
+
+
 # ============================================================================= masked linear
 
 @custom_op('tfep::masked_linear', mutates_args=(), device_types=_DEV)
@@ -799,3 +883,5 @@ FRAME_OPS = ('centroid_shift', 'centroid_restore', 'frame_orient', 'frame_rotate
              'centroid_restore_backward', 'frame_orient_backward', 'frame_rotate_backward')
 GEOMETRY_OPS = ('internal_coordinates', 'internal_coordinates_backward', 'polar_forward', 'polar_backward')
 ZMATRIX_OPS = ('zmatrix_place', 'zmatrix_place_backward')
+RELATIVE_FRAME_OPS = ('relative_frame_encode', 'relative_frame_decode', 'relative_frame_encode_backward',
+                      'relative_frame_decode_backward')

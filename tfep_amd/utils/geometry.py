@@ -16,7 +16,12 @@ functions that take difference VECTORS (``vector_vector_angle``, ``vector_plane_
 Z-matrices: ``cartesian_to_zmatrix`` is ``internal_coordinates`` on the tables of a Z-matrix, ``zmatrix_to_cartesian`` places
 the atoms back, level by level of the dependency graph, in one HIP launch forward and one backward (``csrc/zmatrix.hip``);
 each returns the log-det of its direction.  The reference takes this step from ``bgflow``.
+
+Relative frame: ``cartesian_to_relative_frame`` / ``relative_frame_to_cartesian`` express the Cartesian atoms of the mixed
+coordinates in the frame of three of them and back, one HIP launch each way and one for each backward
+(``csrc/relframe.hip``); ``normalize_angles`` / ``normalize_torsions`` and their inverses are torch expressions.
 """
+import math
 from functools import lru_cache
 from typing import Optional, Tuple
 
@@ -128,6 +133,87 @@ def cartesian_to_zmatrix(x, z_matrix, fixed_atoms):
     x_fixed = x.reshape(x.shape[0], n_atoms, 3).index_select(1, fixed)
     log_det_J = -(2.0 * torch.log(d) + torch.log(torch.abs(torch.sin(a)))).sum(1)
     return d, a, t, (x_fixed if atoms_3d else x_fixed.reshape(x.shape[0], -1)), log_det_J
+
+
+def _remove_flags(remove_ref_rototranslation):
+    flags = torch.as_tensor(remove_ref_rototranslation).reshape(-1).tolist()
+    if len(flags) != 3:
+        raise ValueError(f'remove_ref_rototranslation must hold 3 flags (origin, axis, plane), got {len(flags)}')
+    return tuple(bool(f) for f in flags)
+
+
+def cartesian_to_relative_frame(x_cart, remove_ref_rototranslation):
+    """The Cartesian atoms of a batch in the frame of three of them, in one HIP launch (``csrc/relframe.hip``): the
+    relative frame of the reference's mixed coordinates (``app/mixedmaf.py:1216-1271``).
+
+    ``x_cart``: ``(batch_size, n_c, 3)`` or ``(batch_size, 3 n_c)``, a float32 or float64 HIP tensor (a column slice of a
+    wider tensor is read in place) whose LAST THREE atoms are the origin, axis and plane atoms, in that order; ``n_c >= 3``.
+    The frame has the origin atom at 0, the axis atom on the positive x axis and the plane atom in the x-y plane (the
+    rotation of ``reference_frame_rotation_matrix(..., project_on_positive_axis=True)``).
+    ``remove_ref_rototranslation``: 3 flags, whether the rototranslational DOFs of the origin (3), axis (2) and plane (1) atom,
+    which are zero in the frame, are left out.
+
+    Returns ``(coords, origin, R, log_det_J)``.  ``coords`` ``(batch_size, W)``: ``[d01, d02, a102n | the n_c - 3 other atoms
+    in the frame, 3 each | kept reference DOFs]`` with ``d01`` the axis atom's distance from the origin, ``(d02, a102)`` the
+    polar coordinates of the plane atom, ``a102n = (a102 + pi) / (2 pi)`` in ``[0, 1]``, and the kept DOFs in the order
+    origin ``x, y, z``, axis ``y, z``, plane ``z``.  ``origin`` ``(batch_size, 3)`` and ``R`` ``(batch_size, 3, 3)`` take the
+    way back; ``log_det_J = -log d02 - log 2 pi``.  Differentiable in ``x_cart`` through all four outputs."""
+    if x_cart.dim() == 3 and x_cart.shape[2] == 3:
+        x_cart = x_cart.reshape(x_cart.shape[0], -1)
+    if x_cart.dim() != 2 or x_cart.shape[1] % 3 != 0 or x_cart.shape[1] < 9:
+        raise ValueError(f'x_cart must be (batch, n_c, 3) or (batch, 3 n_c) with n_c >= 3, got {tuple(x_cart.shape)}')
+    remove = _remove_flags(remove_ref_rototranslation)
+    ops.check_device_tensor(x_cart, 'x_cart', ops._dtype(x_cart))
+    coords, origin, rot, log_det_J = torch.ops.tfep.relative_frame_encode(x_cart, *remove)
+    return coords, origin, rot.reshape(-1, 3, 3), log_det_J
+
+
+def relative_frame_to_cartesian(coords, origin, R, remove_ref_rototranslation):
+    """The inverse of ``cartesian_to_relative_frame``, in one HIP launch (reference ``app/mixedmaf.py:1321-1375``).
+
+    ``coords`` ``(batch_size, W)`` in the layout above (a column slice is read in place), ``origin`` ``(batch_size, 3)``,
+    ``R`` ``(batch_size, 3, 3)``: float32 or float64 HIP tensors of one dtype (else TypeError).  A removed reference DOF is
+    exactly 0 in the frame, a kept one is read from ``coords``; a width ``W`` that disagrees with the flags is a ValueError.
+
+    Returns ``(x_cart, log_det_J)``: ``(batch_size, n_c, 3)`` and ``log 2 pi + log d02``.  Differentiable in ``coords``,
+    ``origin`` and ``R``."""
+    if coords.dim() != 2:
+        raise ValueError(f'coords must be (batch, W), got {tuple(coords.shape)}')
+    remove = _remove_flags(remove_ref_rototranslation)
+    for v, name in ((coords, 'coords'), (origin, 'origin'), (R, 'R')):            # one dtype, on the HIP device
+        ops.check_device_tensor(v, name, ops._dtype(coords))
+    x, log_det_J = torch.ops.tfep.relative_frame_decode(coords, origin.reshape(coords.shape[0], 3),
+                                                       R.reshape(coords.shape[0], 9), *remove)
+    return x.reshape(x.shape[0], -1, 3), log_det_J
+
+
+def _scaled(value, shift, scale):
+    """``((value + shift) * scale, log_det_J)`` over the last dimension: the log-det is ``n log scale``."""
+    log_det_J = torch.full(value.shape[:-1], value.shape[-1] * math.log(scale), dtype=value.dtype, device=value.device)
+    return (value + shift) * scale, log_det_J
+
+
+def normalize_angles(angles):
+    """``(angles / pi, log_det_J)``: bond angles ``(*, n)`` in ``[0, pi]`` to ``[0, 1]``; ``log_det_J = -n log pi``, shape
+    ``(*,)``.  (The reference takes this from ``bgflow``; these formulas are this project's definition.)"""
+    return _scaled(angles, 0.0, 1.0 / math.pi)
+
+
+def unnormalize_angles(angles):
+    """The inverse of ``normalize_angles``: ``(angles * pi, +n log pi)``."""
+    return _scaled(angles, 0.0, math.pi)
+
+
+def normalize_torsions(torsions):
+    """``((torsions + pi) / (2 pi), log_det_J)``: torsions ``(*, n)`` in ``[-pi, pi]`` to ``[0, 1]``; ``log_det_J = -n log
+    2 pi``, shape ``(*,)``."""
+    return _scaled(torsions, math.pi, 1.0 / (2.0 * math.pi))
+
+
+def unnormalize_torsions(torsions):
+    """The inverse of ``normalize_torsions``: ``(2 pi torsions - pi, +n log 2 pi)``."""
+    value, log_det_J = _scaled(torsions, 0.0, 2.0 * math.pi)
+    return value - math.pi, log_det_J
 
 
 def vector_vector_angle(x1, x2):
