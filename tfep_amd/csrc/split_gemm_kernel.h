@@ -116,6 +116,54 @@ struct SplitCtx {
     uint32_t piece_a, piece_w;      // bytes between consecutive 8-row chunks
 };
 
+// ------------------------------------------------------------------------------------------
+// The slot table of a k-tile: which ONE companion instruction follows MFMA j (0 .. 11: hi.hi, lo.hi, hi.lo of the four
+// row tiles) of column group n.  One wave per SIMD issues in order and a 16-cycle MFMA keeps the issue port for about half
+// of its cycles: one cheap instruction per gap is free, a clump of them drains the matrix pipe.
+//   gaps 0 and 4 of group n   the two ds_read_b128 (hi, lo) of group n + B_AHEAD
+//   gaps 4i + 1, + 2, + 3     LDS-DMA piece 3n + i of the next k-tile, one instruction each: its vector offset (a v_add that
+//                             steps a running offset from the previous piece of the same operand: no piece keeps a
+//                             register of its own through the tile; none for the first piece of an operand), M0 = its LDS address (an s_add into m0), then the buffer_load ... lds -- the MFMA
+//                             between the last two is the wait state an M0 write needs before the DMA reads it
+// Pieces in issue order: the weights first (their stage is free since the barrier), then the wave's own A rows (free
+// once group 0 has waited for the A fragments: never before group 1).  The loads stand where the old schedule had them.
+// ------------------------------------------------------------------------------------------
+enum : int { SLOT_NONE, SLOT_READ_HI, SLOT_READ_LO, SLOT_DMA_VOFF, SLOT_DMA_M0, SLOT_DMA_LOAD };
+struct KSlot {
+    int kind, arg;      // arg: the column group a read fetches / the piece (issue order) of a DMA instruction
+};
+constexpr int K_GAPS = 3 * SMREP;      // MFMAs (= gaps) per column group
+static_assert(SMREP == 4, "kloop_slot lays a column group out as three runs of four MFMAs");
+
+template <int NREP>
+constexpr KSlot kloop_slot(int n, int j) {
+    using T = STile<NREP>;
+    if (j == 0 || j == 4) {
+        if (n + B_AHEAD >= NREP) return {SLOT_NONE, 0};
+        return {j == 0 ? SLOT_READ_HI : SLOT_READ_LO, n + B_AHEAD};
+    }
+    const int q = 3 * n + j / 4;
+    if (j % 4 == 0 || q >= T::N_DMA) return {SLOT_NONE, 0};
+    if (j % 4 == 1 && (q == 0 || q == T::B_DMA)) return {SLOT_NONE, 0};      // first piece of an operand: the per-lane offset itself
+    return {j % 4 == 1 ? SLOT_DMA_VOFF : j % 4 == 2 ? SLOT_DMA_M0 : SLOT_DMA_LOAD, q};
+}
+
+// every B fragment past the tile head is read exactly once (hi and lo) and every DMA piece has its instructions
+template <int NREP>
+constexpr bool kloop_slots_complete() {
+    using T = STile<NREP>;
+    int reads = 0, dma = 0;
+    for (int n = 0; n < NREP; ++n)
+        for (int j = 0; j < K_GAPS; ++j) {
+            const KSlot s = kloop_slot<NREP>(n, j);
+            reads += s.kind == SLOT_READ_HI || s.kind == SLOT_READ_LO;
+            dma += s.kind >= SLOT_DMA_VOFF;
+        }
+    return reads == 2 * (NREP > B_AHEAD ? NREP - B_AHEAD : 0) && dma == 3 * T::N_DMA - 2;
+}
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
 template <int NREP>
 __device__ inline void split_dma(const SplitCtx& sc, char* a_wave, char* b_stage, int k0, int wave, int d) {
     using T = STile<NREP>;
@@ -129,6 +177,29 @@ __device__ inline void split_dma(const SplitCtx& sc, char* a_wave, char* b_stage
             __builtin_amdgcn_raw_ptr_buffer_load_lds(sc.rw, (lds_ptr)(b_stage + c * 1024), 16,
                                                      sc.vw + (uint32_t)c * sc.piece_w, k0 * 4, 0, 0);
     }
+}
+
+// The three instructions of one LDS-DMA piece as the k-loop places them, one per MFMA gap (kloop_slot).  Hand-written: the
+// builtin above comes as one clump (s_add, s_add m0, [s_nop], buffer_load) wherever it is called.  Same operands as
+// split_dma: per-lane + per-piece bytes in the vector offset, the k-tile's bytes in the scalar one.  M0 is written by one
+// asm and read by the next: nothing between them (an MFMA, scheduling fences) touches it, and the compiler keeps no value
+// of its own in M0 across the k-loop (it sets M0 in front of each of its own uses: the prologue's DMA builtins).
+__device__ __forceinline__ uint32_t kloop_dma_voff(uint32_t piece_bytes, uint32_t lane_bytes) {
+    uint32_t v;
+    asm volatile("v_add_u32 %0, %1, %2" : "=v"(v) : "s"(piece_bytes), "v"(lane_bytes));
+    return v;
+}
+// (M0 is named as clobbered so that the compiler keeps nothing of its own in it across the statement; clang warns about any
+// reserved register in a clobber list)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+template <int IMM>
+__device__ __forceinline__ void kloop_dma_m0(uint32_t lds_base) {
+    asm volatile("s_add_u32 m0, %0, %1" ::"s"(lds_base), "n"(IMM) : "scc", "m0");
+}
+#pragma clang diagnostic pop
+__device__ __forceinline__ void kloop_dma_load(const i32x4& rsrc, uint32_t voff, uint32_t soff) {
+    asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rsrc), "s"(soff) : "memory");
 }
 
 // Fused RQ-spline epilogue of the split kernel (P = 25 parameters per feature, one feature per lane column,
@@ -292,6 +363,11 @@ __global__ void __launch_bounds__(STHREADS, OCC) split_gemm_kernel(GemmArgs g, i
     });
 
     SplitCtx sc;
+    // TFEP_PROBE_OLD_KLOOP: the k-tile schedule before the slot table (B-fragment reads at the head of a column group, every
+    // DMA piece by the builtin after four MFMAs), for a same-tree A/B: python -m tfep_amd.build --probe <lib> -DTFEP_PROBE_OLD_KLOOP
+#ifndef TFEP_PROBE_OLD_KLOOP
+    i32x4 qa, qw;
+#endif
     {
         constexpr int FLAGS = 0x00020000;     // gfx9 raw buffer, 32-bit data; rows past the end read as 0
         const int rows_a = min(g.B - m0, T::BM), rows_w = min(n_rows_w - n0, T::BN);
@@ -306,6 +382,15 @@ __global__ void __launch_bounds__(STHREADS, OCC) split_gemm_kernel(GemmArgs g, i
         sc.vw = (uint32_t)(((int64_t)drow * g.ldw) * 4) + (((wave & 1) ? (p0 ^ 4) : p0) * 16);
         sc.piece_a = (uint32_t)(8 * g.lda * 4);
         sc.piece_w = (uint32_t)(8 * g.ldw * 4);
+#ifndef TFEP_PROBE_OLD_KLOOP
+        // the same two resources as plain words, for the k-loop's hand-placed DMA instructions (kloop_dma_load).  Uniform
+        // values, but the tile indices may have passed through vector instructions (the integer division of split-K): an
+        // asm operand is not moved back to scalar registers by the compiler, so it is done here
+        const uint64_t pa = reinterpret_cast<uint64_t>(g.a + (int64_t)m0 * g.lda), pw = reinterpret_cast<uint64_t>(g.w + (int64_t)n0 * g.ldw);
+        auto sgpr = [](uint32_t v) __attribute__((always_inline)) { return (int)__builtin_amdgcn_readfirstlane(v); };
+        qa = (i32x4){sgpr((uint32_t)pa), sgpr((uint32_t)(pa >> 32) & 0xffffu), sgpr(clamp_u32((int64_t)rows_a * g.lda * 4)), FLAGS};
+        qw = (i32x4){sgpr((uint32_t)pw), sgpr((uint32_t)(pw >> 32) & 0xffffu), sgpr(clamp_u32((int64_t)rows_w * g.ldw * 4)), FLAGS};
+#endif
         if constexpr (SAVE && epi_is_spline(EPI)) {
             {
                 // Tile row q = p * 16 + j (what the accumulator layout wants) sits at packed row j * P + p.  Chunk
@@ -332,6 +417,28 @@ __global__ void __launch_bounds__(STHREADS, OCC) split_gemm_kernel(GemmArgs g, i
     const int off_hi = fr * ROW_BYTES + (((2 * fg) ^ fsw) << 4);
     const int off_lo = fr * ROW_BYTES + (((2 * fg + 1) ^ fsw) << 4);
 
+#ifndef TFEP_PROBE_OLD_KLOOP
+    // The vector offsets of a k-tile's DMA pieces, in issue order (weights, then the wave's A rows), are those of split_dma:
+    // vw + (wave + 4 e) * piece_w and va_even / va_odd + d * piece_a.  Each is one v_add from the previous piece of its
+    // chain (weights; even A chunks; odd A chunks) with a scalar step; the first weight piece and A chunk 0 use the per-lane
+    // offset as it is.  The LDS addresses are scalar: a base per tile plus a constant per piece.
+    static_assert(T::N_DMA <= 3 * NREP && kloop_slots_complete<NREP>(), "the k-tile's companions do not fit into its 12 * NREP gaps");
+    typedef __attribute__((address_space(3))) char* lds_cptr;
+    const uint32_t lds_a = (uint32_t)(uintptr_t)(lds_cptr)a_wave;
+    const uint32_t lds_b = (uint32_t)(uintptr_t)(lds_cptr)b_base + (uint32_t)wave * 1024u;
+    const uint32_t vw0 = sc.vw + (uint32_t)wave * sc.piece_w, step_w = (uint32_t)SWAVES * sc.piece_w, step_a = 2u * sc.piece_a;
+    // (the epilogue's kernel arguments are fetched ahead of the loop: with a scalar load pending the first wait of every
+    // k-tile would have to be for ALL of the head's fragment reads)
+    __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0)
+    // The accumulators enter the k-tiles as the registers zeroed above, on every path (no k-tile, one, many): re-defined here,
+    // they are no longer constants the compiler may materialise again, which it did in a block of its own for the
+    // one-k-tile entry, laid out behind the loop header -- straight after the loop's last MFMAs in the listing, where
+    // tools/scan_hazards.sh (a linear walk) has to count it as an early access to their results.
+    static_for<0, NREP * SMREP>([&](auto ic) __attribute__((always_inline)) {
+        constexpr int n = ic.value / SMREP, m = ic.value % SMREP;
+        redefine<(n < N_ACC_AGPR)>(acc[n][m]);
+    });
+#endif
     // One k-tile.  DMA = true: also issue the LDS-DMA of tile t + 1 (every tile but the last; a separate
     // instantiation, so the k-loop has no branch around the DMA instructions and they sit BETWEEN the MFMAs).
     auto tile = [&](auto dma_c, int t) __attribute__((always_inline)) {
@@ -374,6 +481,64 @@ __global__ void __launch_bounds__(STHREADS, OCC) split_gemm_kernel(GemmArgs g, i
 #else
         const int k_next = kb + (t + 1) * SBK;
 #endif
+#ifndef TFEP_PROBE_OLD_KLOOP
+        // The companions of the MFMAs -- the B-fragment reads of group n + B_AHEAD and the next tile's DMA -- one per gap, by
+        // the slot table (kloop_slot).  The DMA goes out EARLY in the tile (a DMA issued late meets the barrier before it has
+        // landed).  The compiler's s_waitcnt lgkmcnt(n) for a fragment lands in front of the first MFMA that uses it.
+        const uint32_t k_bytes = __builtin_amdgcn_readfirstlane((uint32_t)k_next * 4u);
+        const uint32_t lds_bn = lds_b + (uint32_t)(((t + 1) & 1) * T::B_BYTES);
+        uint32_t voff_w = vw0, voff_a[2] = {sc.va_even, 0};
+        auto companion = [&](auto nc, auto jc) __attribute__((always_inline)) {
+            constexpr KSlot s = kloop_slot<NREP>(decltype(nc)::value, decltype(jc)::value);
+            constexpr bool is_dma = s.kind >= SLOT_DMA_VOFF;
+            if constexpr (s.kind == SLOT_READ_HI) {
+                __builtin_amdgcn_sched_barrier(0);
+                bh[s.arg % (B_AHEAD + 1)] = *(const f16x8*)(Bs + s.arg * 16 * ROW_BYTES + off_hi);
+                __builtin_amdgcn_sched_barrier(0);
+            } else if constexpr (s.kind == SLOT_READ_LO) {
+                __builtin_amdgcn_sched_barrier(0);
+                bl[s.arg % (B_AHEAD + 1)] = *(const f16x8*)(Bs + s.arg * 16 * ROW_BYTES + off_lo);
+                __builtin_amdgcn_sched_barrier(0);
+            } else if constexpr (DMA && is_dma) {
+                constexpr int q = s.arg;
+                constexpr bool is_b = q < T::B_DMA;
+                // the last weight piece of a tile whose chunks are no multiple of the waves belongs to the first waves only
+                constexpr bool ragged = is_b && SWAVES * (q + 1) > T::B_CHUNKS;
+                static_assert(is_b || q / 3 >= 1, "A DMA before the A fragments are read");
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (s.kind == SLOT_DMA_VOFF) {
+                    constexpr int d = q - T::B_DMA;
+                    if constexpr (is_b && q > 0)
+                        voff_w = kloop_dma_voff(step_w, voff_w);
+                    else if constexpr (d == 1)
+                        voff_a[1] = kloop_dma_voff(sc.piece_a, sc.va_odd);
+                    else if constexpr (d >= 2)
+                        voff_a[d & 1] = kloop_dma_voff(step_a, voff_a[d & 1]);
+                } else if constexpr (s.kind == SLOT_DMA_M0) {
+                    if constexpr (is_b)
+                        kloop_dma_m0<SWAVES * q * 1024>(lds_bn);
+                    else
+                        kloop_dma_m0<(q - T::B_DMA) * 1024>(lds_a);
+                } else if constexpr (ragged) {
+                    if (wave < T::B_CHUNKS - SWAVES * q) kloop_dma_load(qw, voff_w, k_bytes);
+                } else {
+                    kloop_dma_load(is_b ? qw : qa, is_b ? voff_w : voff_a[(q - T::B_DMA) & 1], k_bytes);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        // Column groups as a compile-time loop: the accumulator indices must be constants in the frontend,
+        // or the 400-register array is not promoted out of scratch memory.
+        static_for<0, NREP>([&](auto nc) __attribute__((always_inline)) {
+            constexpr int n = decltype(nc)::value;
+            static_for<0, K_GAPS>([&](auto jc) __attribute__((always_inline)) {
+                constexpr int j = decltype(jc)::value, m = j % SMREP;
+                // hi.hi, lo.hi, hi.lo of every accumulator, in this order
+                mfma16<(n < N_ACC_AGPR)>(acc[n][m], j / SMREP == 1 ? al[m] : ah[m], j / SMREP == 2 ? bl[n % (B_AHEAD + 1)] : bh[n % (B_AHEAD + 1)]);
+                companion(nc, jc);
+            });
+        });
+#else
         // The next tile's DMA goes out EARLY in this tile (a DMA issued late meets the barrier before it has landed),
         // one instruction after each group of four MFMAs -- a lone wave that issues a clump of DMA instructions
         // starves its matrix pipe meanwhile.  Weights first: their stage is free since the barrier; then the wave's
@@ -405,6 +570,7 @@ __global__ void __launch_bounds__(STHREADS, OCC) split_gemm_kernel(GemmArgs g, i
             static_for<0, SMREP>([&](auto mc) __attribute__((always_inline)) { mfma16<(n < N_ACC_AGPR)>(acc[n][mc.value], ah[mc.value], l); });
             dma_slot(std::integral_constant<int, 3 * n + 2>{});
         });
+#endif
     };
     static_assert(T::N_DMA <= 3 * NREP, "not enough DMA slots in a k-tile");
     for (int t = 0; t + 1 < nk; ++t) tile(std::true_type{}, t);
