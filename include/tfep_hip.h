@@ -1334,6 +1334,43 @@ int tfep_radial_expansion(const float* r, int64_t n, const float* means, const f
 int tfep_segment_sum(const float* data, const int64_t* segment_ids, int64_t n_rows, int n_cols, int64_t n_segments,
                      float* out, void* stream);
 
+/*
+ * The differentiable forms of the two helpers above (csrc/graph_ops.hip), for callers that train their own graph
+ * networks on the public building blocks.
+ *
+ * tfep_radial_expansion_f64: the float64 twin of tfep_radial_expansion (IEEE fp64, library exp / cos).
+ *
+ * tfep_radial_expansion_backward[_f64]: the VJP for the cotangent g (n, n_basis).  With gamma_k = exp(log_gamma_k),
+ * e_k = exp(-gamma_k (r - mean_k)^2), s the switch (1 without switching) and f_k = s e_k:
+ *   g_r[i]          = sum_k g[i, k] (f_k (-2 gamma_k (r_i - mean_k)) + e_k s'(r_i)),  s' = -(pi / 2 r_cutoff) sin(pi r / r_cutoff),
+ *                     s = s' = 0 beyond the cutoff if force_zero_after_cutoff
+ *   g_means[k]      = sum_i g[i, k] f_k 2 gamma_k (r_i - mean_k)
+ *   g_log_gammas[k] = -sum_i g[i, k] f_k gamma_k (r_i - mean_k)^2
+ * Any of the three outputs may be NULL (not computed).  fp64 arithmetic for both element types, one rounding on store; no
+ * atomics: the sums over i go through `workspace` (tfep_radial_expansion_backward_workspace_doubles(n, n_basis) doubles, not
+ * needed when both parameter gradients are NULL) in an order that depends on (n, n_basis) only, so two calls agree bit for
+ * bit, and g_r of a row does not depend on the other rows.  n = 0 writes zero parameter gradients.
+ */
+int tfep_radial_expansion_f64(const double* r, int64_t n, const double* means, const double* log_gammas, int n_basis,
+                              double r_cutoff, int switching, int force_zero_after_cutoff, double* out, void* stream);
+int64_t tfep_radial_expansion_backward_workspace_doubles(int64_t n, int n_basis);
+int tfep_radial_expansion_backward(const float* r, int64_t n, const float* means, const float* log_gammas, int n_basis,
+                                   float r_cutoff, int switching, int force_zero_after_cutoff, const float* g, float* g_r,
+                                   float* g_means, float* g_log_gammas, double* workspace, void* stream);
+int tfep_radial_expansion_backward_f64(const double* r, int64_t n, const double* means, const double* log_gammas, int n_basis,
+                                       double r_cutoff, int switching, int force_zero_after_cutoff, const double* g,
+                                       double* g_r, double* g_means, double* g_log_gammas, double* workspace, void* stream);
+
+/* tfep_segment_sum in float64 (native fp64 global atomics; ids out of range are skipped), and the VJP of the segment sum in
+ * both types: g_data[i, :] = g_out[segment_ids[i], :] if 0 <= segment_ids[i] < n_segments, else 0 (16-byte accesses when the
+ * row length and both pointers allow). */
+int tfep_segment_sum_f64(const double* data, const int64_t* segment_ids, int64_t n_rows, int n_cols, int64_t n_segments,
+                         double* out, void* stream);
+int tfep_segment_gather(const float* g_out, const int64_t* segment_ids, int64_t n_rows, int n_cols, int64_t n_segments,
+                        float* g_data, void* stream);
+int tfep_segment_gather_f64(const double* g_out, const int64_t* segment_ids, int64_t n_rows, int n_cols, int64_t n_segments,
+                            double* g_data, void* stream);
+
 /* y = x + sum_{k < n_terms} a[k] v[k]  (x may be NULL = 0; n_terms <= 4; v, a: HOST arrays of device pointers /
  * coefficients): the stage combinations of the fixed-grid ODE steppers that replace torchdiffeq's
  * (continuous.py:136-169). */

@@ -319,6 +319,17 @@ for _s in ('', '_f64'):
         'tfep_relative_frame_decode_backward' + _s: (c_int, [_P, c_int64, _P, _P, *_REL, _P, c_int64, _P, _P, c_int64, _P, _P,
                                                              c_int, _P]),
     })
+# the differentiable radial expansion and segment sum (csrc/graph_ops.hip); r_cutoff is a float / a double
+_SIGNATURES.update({
+    'tfep_radial_expansion_f64': (c_int, [_P, c_int64, _P, _P, c_int, c_double, c_int, c_int, _P, _P]),
+    'tfep_radial_expansion_backward_workspace_doubles': (c_int64, [c_int64, c_int]),
+    'tfep_radial_expansion_backward': (c_int, [_P, c_int64, _P, _P, c_int, c_float, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    'tfep_radial_expansion_backward_f64': (c_int, [_P, c_int64, _P, _P, c_int, c_double, c_int, c_int, _P, _P, _P, _P, _P,
+                                                   _P]),
+    'tfep_segment_sum_f64': _SIGNATURES['tfep_segment_sum'],
+    'tfep_segment_gather': (c_int, [_P, _P, c_int64, c_int, c_int64, _P, _P]),
+    'tfep_segment_gather_f64': (c_int, [_P, _P, c_int64, c_int, c_int64, _P, _P]),
+})
 del _SEL, _FRAME, _TABLES, _DAT, _ZTABLES, _REL, _s
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))

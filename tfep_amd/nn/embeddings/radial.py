@@ -3,18 +3,28 @@
 ``GaussianBasisExpansion`` (:24-137), ``behler_parrinello_cosine_switching_function`` (:144-176) and
 ``BehlerParrinelloRadialExpansion`` (:179-291): same constructors, ``from_range`` and ``state_dict`` (only
 ``_log_gammas`` / ``_means`` when trainable; the fixed ones are non-persistent buffers here so that ``.to(device)``
-moves them -- the reference keeps plain tensor attributes).  ``forward`` is ``tfep_radial_expansion``; inside
-``EGNNDynamics`` the expansion is fused into the edge kernel and never materialised.
+moves them -- the reference keeps plain tensor attributes).  Inside ``EGNNDynamics`` the expansion is fused into the edge
+kernel and never materialised.
+
+Autograd.  By default ``forward`` is ``tfep_radial_expansion`` on DETACHED float32 parameters: the result is float32, has
+no ``grad_fn``, and ``backward()`` reaches neither ``_means`` / ``_log_gammas`` (even when they are Parameters) nor the
+input -- unlike the reference, whose forward is a torch expression.  An instance that sets ``differentiable = True`` goes
+through ``torch.ops.tfep.radial_expansion`` instead: the parameters themselves, the dtype of the data (float32 or
+float64; fixed buffers are cast to it, a trainable Parameter of another dtype is a TypeError), gradients to the data and to
+the trainable parameters from the VJP kernels of ``csrc/graph_ops.hip`` (first derivatives only).
 """
 import math
 
 import torch
 
-from ... import _lib
+from ... import _lib, ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.tfep.*)
 
 
 class GaussianBasisExpansion(torch.nn.Module):
     """Soft one-hot encoding of a scalar on a Gaussian basis: ``exp(-gamma_k (x - mean_k)^2)``."""
+
+    #: False: ``forward`` is cut off from autograd (float32, detached parameters).  Set True on an instance to train it.
+    differentiable = False
 
     def __init__(self, means, stds, trainable_means=False, trainable_stds=False):
         super().__init__()
@@ -35,7 +45,24 @@ class GaussianBasisExpansion(torch.nn.Module):
         means, stds = cls._get_equidistant_means_and_stds(n_gaussians, max_mean, min_mean, relative_std)
         return cls(means, stds, trainable_means=trainable_means, trainable_stds=trainable_stds)
 
+    def _expand_differentiable(self, data, r_cutoff, switching, force_zero):
+        _lib.check_device_tensor(data, 'data', ops._dtype(data))
+        if data.shape[-1] == 1:
+            data = data.squeeze(-1)
+        params = []
+        for name in ('_means', '_log_gammas'):
+            p = getattr(self, name)
+            if isinstance(p, torch.nn.Parameter):
+                if p.dtype != data.dtype:
+                    raise TypeError(f'{name} is a trainable {p.dtype} parameter, the data is {data.dtype}')
+            else:
+                p = p.to(device=data.device, dtype=data.dtype)
+            params.append(p)
+        return torch.ops.tfep.radial_expansion(data, *params, float(r_cutoff), bool(switching), bool(force_zero))
+
     def _expand(self, data, r_cutoff=0.0, switching=False, force_zero=True):
+        if self.differentiable:
+            return self._expand_differentiable(data, r_cutoff, switching, force_zero)
         _lib.check_device_tensor(data, 'data')
         if data.shape[-1] == 1:
             data = data.squeeze(-1)

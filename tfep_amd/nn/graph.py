@@ -3,14 +3,15 @@
 ``FixedGraph`` (:29-116), ``get_all_edges`` (:119-163), ``fix_node_indices_batch_size`` (:166-218),
 ``compute_edge_distances`` (:222-263), ``prune_long_edges`` (:266-301) and ``unsorted_segment_sum`` (:304-316), kept for
 callers that build their own graph networks.  The edge lists are host-side integer work (plain index arithmetic, no
-floating point); the segment sum is ``tfep_segment_sum``.  ``tfep_amd.nn.dynamics.EGNNDynamics`` itself never builds an
+floating point); the segment sum is ``tfep_segment_sum``, cut off from autograd unless ``differentiable=True`` is passed
+(``torch.ops.tfep.segment_sum``: float32 or float64, with a VJP).  ``tfep_amd.nn.dynamics.EGNNDynamics`` itself never builds an
 edge list: its kernels walk all ordered pairs on the fly (``csrc/egnn.hip``).
 """
 from typing import Optional, Sequence
 
 import torch
 
-from .. import _lib
+from .. import _lib, ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.tfep.*)
 from ..utils.misc import ensure_tensor_sequence
 
 
@@ -88,8 +89,16 @@ def prune_long_edges(r_cutoff, edges, distances, *args):
     return (edges[:, keep], distances[keep], *[a[keep] for a in args])
 
 
-def unsorted_segment_sum(data, segment_ids, n_segments):
-    """``out[s] = sum of the rows of data with segment_ids == s`` on the HIP device (``tfep_segment_sum``)."""
+def unsorted_segment_sum(data, segment_ids, n_segments, differentiable=False):
+    """``out[s] = sum of the rows of data with segment_ids == s`` on the HIP device (``tfep_segment_sum``).
+
+    By default the result is cut off from autograd and ``data`` must be float32.  ``differentiable=True`` goes through
+    ``torch.ops.tfep.segment_sum``: float32 or float64, and ``backward()`` reaches ``data`` (a row gather, first derivatives
+    only).
+    """
+    if differentiable:
+        _lib.check_device_tensor(data, 'data', ops._dtype(data))
+        return torch.ops.tfep.segment_sum(data, segment_ids.to(data.device), int(n_segments))
     _lib.check_device_tensor(data, 'data')
     if data.dim() != 2:
         raise ValueError('data must be (n_rows, n_columns)')

@@ -1497,3 +1497,82 @@ def tfep_reduce(target_potentials, log_det_J=None, ref_potentials=None, log_weig
     call('tfep_tfep_reduce' + _sfx(dt), ptr(t), ptr(opt[0]), ptr(opt[1]), ptr(opt[2]), ptr(opt[3]), float(kT),
          int(bool(ignore_nan)), N, ptr(ws), ptr(out), stream_of(t))
     return out
+
+
+# ----------------------------------------------------------------------------- radial expansion, segment sum
+
+def _radial_inputs(r, means, log_gammas):
+    """``(r flattened, means, log_gammas, dtype)``: contiguous, of the dtype of ``r`` (TypeError otherwise), ``K >= 1``."""
+    dt = _dtype(r)
+    check_device_tensor(r, 'r', dt)
+    check_device_tensor(means, 'means', dt)
+    check_device_tensor(log_gammas, 'log_gammas', dt)
+    if means.dim() != 1 or means.shape != log_gammas.shape or means.numel() < 1:
+        raise ValueError('means and log_gammas must be 1-D, of one length >= 1')
+    return r.contiguous().reshape(-1), means.contiguous(), log_gammas.contiguous(), dt
+
+
+def radial_expansion(r, means, log_gammas, r_cutoff=0.0, switching=False, force_zero=True):
+    """``exp(-exp(log_gamma_k) (r - mean_k)^2)``, times the Behler-Parrinello switch with ``switching``: ``(*r.shape, K)`` of
+    the dtype of ``r``.  float32 is ``tfep_radial_expansion`` (the kernel the modules call), float64 its twin."""
+    flat, means, log_gammas, dt = _radial_inputs(r, means, log_gammas)
+    K = means.numel()
+    out = torch.empty(flat.numel(), K, dtype=dt, device=flat.device)
+    call('tfep_radial_expansion' + _sfx(dt), ptr(flat), flat.numel(), ptr(means), ptr(log_gammas), K, float(r_cutoff),
+         int(bool(switching)), int(bool(force_zero)), ptr(out), stream_of(flat))
+    return out.reshape(*r.shape, K)
+
+
+def radial_expansion_backward(r, means, log_gammas, grad_out, r_cutoff=0.0, switching=False, force_zero=True):
+    """VJP of ``radial_expansion`` for the cotangent ``grad_out (*r.shape, K)``: ``(g_r, g_means, g_log_gammas)``.  The sums
+    over the rows have one order per ``(r.numel(), K)``: two calls give the same bits."""
+    flat, means, log_gammas, dt = _radial_inputs(r, means, log_gammas)
+    n, K = flat.numel(), means.numel()
+    g = check_device_tensor(grad_out, 'grad_out', dt).contiguous()
+    if g.shape != (*r.shape, K):
+        raise ValueError(f'grad_out must be {(*r.shape, K)}, got {tuple(g.shape)}')
+    g_r = torch.empty(n, dtype=dt, device=flat.device)
+    g_means, g_lg = torch.empty_like(means), torch.empty_like(log_gammas)
+    n_ws = _lib.load().tfep_radial_expansion_backward_workspace_doubles(n, K)
+    if n_ws < 0:
+        raise ValueError(_lib.load().tfep_last_error().decode())
+    ws = torch.empty(max(n_ws, 1), dtype=torch.float64, device=flat.device)
+    call('tfep_radial_expansion_backward' + _sfx(dt), ptr(flat), n, ptr(means), ptr(log_gammas), K, float(r_cutoff),
+         int(bool(switching)), int(bool(force_zero)), ptr(g), ptr(g_r), ptr(g_means), ptr(g_lg), ptr(ws), stream_of(flat))
+    return g_r.reshape(r.shape), g_means, g_lg
+
+
+def _segment_ids(segment_ids, n_rows, device):
+    ids = segment_ids.to(device=device, dtype=torch.int64).contiguous()
+    if ids.shape != (n_rows,):
+        raise ValueError('segment_ids must have one entry per row of data')
+    return ids
+
+
+def segment_sum(data, segment_ids, n_segments):
+    """``out[s] = sum of the rows of data with segment_ids == s`` (ids out of range are skipped), float32 or float64."""
+    dt = _dtype(data)
+    check_device_tensor(data, 'data', dt)
+    if data.dim() != 2 or data.shape[1] < 1:
+        raise ValueError('data must be (n_rows, n_columns >= 1)')
+    data = data.contiguous()
+    ids = _segment_ids(segment_ids, data.shape[0], data.device)
+    out = torch.empty(int(n_segments), data.shape[1], dtype=dt, device=data.device)
+    call('tfep_segment_sum' + _sfx(dt), ptr(data), ptr(ids), data.shape[0], data.shape[1], int(n_segments), ptr(out),
+         stream_of(data))
+    return out
+
+
+def segment_gather(grad_out, segment_ids):
+    """VJP of ``segment_sum``: row ``i`` is ``grad_out[segment_ids[i]]``, zeros where the id names no segment."""
+    dt = _dtype(grad_out)
+    check_device_tensor(grad_out, 'grad_out', dt)
+    if grad_out.dim() != 2 or grad_out.shape[1] < 1:
+        raise ValueError('grad_out must be (n_segments, n_columns >= 1)')
+    g = grad_out.contiguous()
+    if segment_ids.dim() != 1:
+        raise ValueError('segment_ids must be 1-D')
+    ids = _segment_ids(segment_ids, segment_ids.shape[0], g.device)
+    out = torch.empty(ids.shape[0], g.shape[1], dtype=dt, device=g.device)
+    call('tfep_segment_gather' + _sfx(dt), ptr(g), ptr(ids), ids.shape[0], g.shape[1], g.shape[0], ptr(out), stream_of(g))
+    return out

@@ -27,6 +27,8 @@ in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the re
   tfep::relative_frame_encode / relative_frame_decode, each with its _backward
                                                                      reference app/mixedmaf.py:1216-1271, 1321-1375
                                                                      (RELATIVE_FRAME_OPS)
+  tfep::radial_expansion / _backward, segment_sum / segment_gather   reference embeddings/radial.py:110-130, 161-176,
+                                                                     graph.py:304-316 (GRAPH_OPS)
   tfep::masked_linear / masked_linear_backward                       reference masked.py:220-302, 351-404
   tfep::fused_output_transformer                                     masked.py:188-208 (last layer) + the transformer
   tfep::tfep_reduce                                                  loss.py:125-140, analysis/estimator.py:73-86
@@ -728,6 +730,69 @@ relative_frame_encode.register_autograd(_relative_frame_encode_bwd, setup_contex
 relative_frame_decode.register_autograd(_relative_frame_decode_bwd, setup_context=_relative_frame_decode_setup)
 
 
+# ============================================================================= radial expansion, segment sum
+
+@custom_op('tfep::radial_expansion', mutates_args=(), device_types=_DEV)
+def radial_expansion(r: Tensor, means: Tensor, log_gammas: Tensor, r_cutoff: float, switching: bool,
+                     force_zero: bool) -> Tensor:
+    """``(*r.shape, K)``: the Gaussian basis of ``GaussianBasisExpansion``, times the Behler-Parrinello switch with
+    ``switching``.  float32 or float64, the dtype of ``r``; ``means`` / ``log_gammas`` of another dtype are a TypeError."""
+    return ops.radial_expansion(r, means, log_gammas, r_cutoff, switching, force_zero)
+
+
+@custom_op('tfep::radial_expansion_backward', mutates_args=(), device_types=_DEV)
+def radial_expansion_backward(r: Tensor, means: Tensor, log_gammas: Tensor, grad_out: Tensor, r_cutoff: float,
+                              switching: bool, force_zero: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(g_r, g_means, g_log_gammas)``; bit-reproducible (no atomics)."""
+    return ops.radial_expansion_backward(r, means, log_gammas, grad_out, r_cutoff, switching, force_zero)
+
+
+@custom_op('tfep::segment_sum', mutates_args=(), device_types=_DEV)
+def segment_sum(data: Tensor, segment_ids: Tensor, n_segments: int) -> Tensor:
+    """``unsorted_segment_sum``: ``(n_segments, n_columns)`` of the dtype of ``data`` (float32 or float64); rows whose id is
+    outside ``[0, n_segments)`` are skipped."""
+    return ops.segment_sum(data, segment_ids, n_segments)
+
+
+@custom_op('tfep::segment_gather', mutates_args=(), device_types=_DEV)
+def segment_gather(grad_out: Tensor, segment_ids: Tensor) -> Tensor:
+    """VJP of ``segment_sum``: ``grad_out[segment_ids]``, zero rows where the id names no segment."""
+    return ops.segment_gather(grad_out, segment_ids)
+
+
+radial_expansion.register_fake(lambda r, means, *rest: r.new_empty((*r.shape, means.shape[0])))
+radial_expansion_backward.register_fake(lambda r, means, log_gammas, *rest: (
+    r.new_empty(r.shape), means.new_empty(means.shape), log_gammas.new_empty(log_gammas.shape)))
+segment_sum.register_fake(lambda data, segment_ids, n_segments: data.new_empty((n_segments, data.shape[1])))
+segment_gather.register_fake(lambda grad_out, segment_ids: grad_out.new_empty((segment_ids.shape[0], grad_out.shape[1])))
+
+
+def _radial_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:3])
+    ctx.cfg = tuple(inputs[3:])
+
+
+# (first derivatives only: the VJP kernels have no VJP of their own, and a second backward raises instead of returning zeros)
+@torch.autograd.function.once_differentiable
+def _radial_bwd(ctx, g):
+    g_r, g_means, g_lg = torch.ops.tfep.radial_expansion_backward(*ctx.saved_tensors, g, *ctx.cfg)
+    return g_r, g_means, g_lg, None, None, None
+
+
+def _segment_sum_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+
+
+@torch.autograd.function.once_differentiable
+def _segment_sum_bwd(ctx, g):
+    (ids,) = ctx.saved_tensors
+    return torch.ops.tfep.segment_gather(g, ids), None, None
+
+
+radial_expansion.register_autograd(_radial_bwd, setup_context=_radial_setup)
+segment_sum.register_autograd(_segment_sum_bwd, setup_context=_segment_sum_setup)
+
+
 # ============================================================================= masked linear
 
 @custom_op('tfep::masked_linear', mutates_args=(), device_types=_DEV)
@@ -885,3 +950,4 @@ GEOMETRY_OPS = ('internal_coordinates', 'internal_coordinates_backward', 'polar_
 ZMATRIX_OPS = ('zmatrix_place', 'zmatrix_place_backward')
 RELATIVE_FRAME_OPS = ('relative_frame_encode', 'relative_frame_decode', 'relative_frame_encode_backward',
                       'relative_frame_decode_backward')
+GRAPH_OPS = ('radial_expansion', 'radial_expansion_backward', 'segment_sum', 'segment_gather')
