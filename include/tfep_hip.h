@@ -1371,6 +1371,58 @@ int tfep_segment_gather(const float* g_out, const int64_t* segment_ids, int64_t 
 int tfep_segment_gather_f64(const double* g_out, const int64_t* segment_ids, int64_t n_rows, int n_cols, int64_t n_segments,
                             double* g_data, void* stream);
 
+/*
+ * The head of a message-passing layer on an explicit edge list (csrc/edge_ops.hip; graph.py:222-301), float32 and float64.
+ * x: (n_nodes, 3) with row stride ldx >= 3; edges: (2, n_edges) int64, contiguous, every index in [0, n_nodes) -- validated by
+ * the caller on the host (tfep_amd.ops.check_edges); the kernels skip an index out of range instead of reading there.  fp64
+ * arithmetic for both element types, one rounding on store, IEEE sqrt and division.  n_edges = 0 and n_nodes = 0 are
+ * successful no-ops, except that the backward still writes its zeros.
+ *
+ * tfep_edge_geometry[_f64]: directions[e] = x[edges[1][e]] - x[edges[0][e]] (negated with inverse), distances[e] =
+ * |directions[e]|, and with normalize directions[e] /= distances[e] (an edge of length 0 gives NaN directions).
+ * distances: (n_edges), directions: (n_edges, 3), contiguous.
+ *
+ * tfep_edge_geometry_backward[_f64]: the VJP for the cotangents g_distances (n_edges) and g_directions (n_edges, 3); either
+ * may be NULL = zero (the same arithmetic, the same bits as an explicit zero).  gx (n_nodes, 3) with row stride ldgx is
+ * written in full, zeros for a node without an edge.  No atomics: node_ptr (n_nodes + 1) / incident (2 n_edges) is the
+ * incidence list of the nodes -- incident[node_ptr[n] .. node_ptr[n + 1]) holds the items 2 e + role of node n in ascending
+ * order, role 0 where n = edges[0][e], role 1 where n = edges[1][e] (tfep_amd.ops.incidence_lists) -- and one lane per node
+ * recomputes the forward of each incident edge and adds the contributions in list order: the gradient of a node has the
+ * same bits whatever else is in the batch.  With u = v / r: g_v = g_d + g_r u, or with normalize (g_d - u (u . g_d)) / r +
+ * g_r u.  An edge of length 0 gives NaN in gx of its two nodes.
+ */
+int tfep_edge_geometry(const float* x, int64_t ldx, const int64_t* edges, int64_t n_nodes, int64_t n_edges, int normalize,
+                       int inverse, float* distances, float* directions, void* stream);
+int tfep_edge_geometry_f64(const double* x, int64_t ldx, const int64_t* edges, int64_t n_nodes, int64_t n_edges, int normalize,
+                           int inverse, double* distances, double* directions, void* stream);
+int tfep_edge_geometry_backward(const float* x, int64_t ldx, const int64_t* edges, int64_t n_nodes, int64_t n_edges,
+                                const int64_t* node_ptr, const int64_t* incident, int normalize, int inverse,
+                                const float* g_distances, const float* g_directions, float* gx, int64_t ldgx, void* stream);
+int tfep_edge_geometry_backward_f64(const double* x, int64_t ldx, const int64_t* edges, int64_t n_nodes, int64_t n_edges,
+                                    const int64_t* node_ptr, const int64_t* incident, int normalize, int inverse,
+                                    const double* g_distances, const double* g_directions, double* gx, int64_t ldgx,
+                                    void* stream);
+
+/*
+ * prune_long_edges (graph.py:266-301) as an ordered stream compaction: the ids of the edges with distances[e] <= r_cutoff
+ * (a NaN distance is dropped) in ascending order.  Deterministic, no atomics, two calls around the one read of the total:
+ *   tfep_edge_prune_count[_f64]    the kept edges of every tile of 256, then their exclusive scan in place: workspace
+ *                                  (tfep_edge_prune_workspace_int64s(n_edges) int64) holds the offset of every tile and,
+ *                                  in its last element, the number of kept edges (0 for n_edges = 0)
+ *   tfep_edge_prune_compact[_f64]  writes keep_index (n_kept) from the same distances, cutoff and workspace
+ * tfep_edge_select_edges: out (2, n_kept) = edges[:, keep_index] ((2, n_edges), contiguous; -1 where keep_index names no
+ * edge).  Floating tensors are pruned with tfep_segment_gather[_f64].
+ */
+int64_t tfep_edge_prune_workspace_int64s(int64_t n_edges);
+int tfep_edge_prune_count(const float* distances, int64_t n_edges, float r_cutoff, int64_t* workspace, void* stream);
+int tfep_edge_prune_count_f64(const double* distances, int64_t n_edges, double r_cutoff, int64_t* workspace, void* stream);
+int tfep_edge_prune_compact(const float* distances, int64_t n_edges, float r_cutoff, const int64_t* workspace,
+                            int64_t* keep_index, int64_t n_kept, void* stream);
+int tfep_edge_prune_compact_f64(const double* distances, int64_t n_edges, double r_cutoff, const int64_t* workspace,
+                                int64_t* keep_index, int64_t n_kept, void* stream);
+int tfep_edge_select_edges(const int64_t* edges, int64_t n_edges, const int64_t* keep_index, int64_t n_kept, int64_t* out,
+                           void* stream);
+
 /* y = x + sum_{k < n_terms} a[k] v[k]  (x may be NULL = 0; n_terms <= 4; v, a: HOST arrays of device pointers /
  * coefficients): the stage combinations of the fixed-grid ODE steppers that replace torchdiffeq's
  * (continuous.py:136-169). */

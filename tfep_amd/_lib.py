@@ -330,7 +330,20 @@ _SIGNATURES.update({
     'tfep_segment_gather': (c_int, [_P, _P, c_int64, c_int, c_int64, _P, _P]),
     'tfep_segment_gather_f64': (c_int, [_P, _P, c_int64, c_int, c_int64, _P, _P]),
 })
-del _SEL, _FRAME, _TABLES, _DAT, _ZTABLES, _REL, _s
+# edge geometry and pruning (csrc/edge_ops.hip); r_cutoff is a float / a double
+for _s, _c in (('', c_float), ('_f64', c_double)):
+    _SIGNATURES.update({
+        'tfep_edge_geometry' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int, c_int, _P, _P, _P]),
+        'tfep_edge_geometry_backward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int64, _P, _P, c_int, c_int, _P, _P, _P,
+                                                     c_int64, _P]),
+        'tfep_edge_prune_count' + _s: (c_int, [_P, c_int64, _c, _P, _P]),
+        'tfep_edge_prune_compact' + _s: (c_int, [_P, c_int64, _c, _P, _P, c_int64, _P]),
+    })
+_SIGNATURES.update({
+    'tfep_edge_prune_workspace_int64s': (c_int64, [c_int64]),
+    'tfep_edge_select_edges': (c_int, [_P, c_int64, _P, c_int64, _P, _P]),
+})
+del _SEL, _FRAME, _TABLES, _DAT, _ZTABLES, _REL, _s, _c
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

@@ -1576,3 +1576,151 @@ def segment_gather(grad_out, segment_ids):
     out = torch.empty(ids.shape[0], g.shape[1], dtype=dt, device=g.device)
     call('tfep_segment_gather' + _sfx(dt), ptr(g), ptr(ids), ids.shape[0], g.shape[1], g.shape[0], ptr(out), stream_of(g))
     return out
+
+
+# ----------------------------------------------------------------------------- edge geometry, pruning
+
+_EDGE_CACHE = []             # (key, the caller's edges, [contiguous int64 edges, incidence list or None]), newest last
+_EDGE_CACHE_SIZE = 4
+
+
+def incidence_lists(edges, n_nodes):
+    """The node-incidence list (CSR) of a ``(2, E)`` edge list, the host logic of the backward of ``edge_geometry``:
+    ``(node_ptr (n_nodes + 1,), incident (2 E,))`` as int64 tensors on the device of ``edges`` (CPU tensors, numpy arrays and
+    lists stay on the CPU).  ``incident[node_ptr[n]:node_ptr[n + 1]]`` holds the items ``2 e + role`` of node ``n`` in
+    ascending order: role 0 where ``n`` is the source ``edges[0, e]``, role 1 where it is the destination ``edges[1, e]`` --
+    ascending edges, the source entry first on a tie.  A stable sort by node of the items in ascending order.  The indices
+    are taken as given (``check_edges`` validates them)."""
+    edges = torch.as_tensor(edges)
+    if edges.dim() != 2 or edges.shape[0] != 2:
+        raise ValueError(f'edges must have shape (2, n_edges), got {tuple(edges.shape)}')
+    nodes = edges.to(torch.int64).t().reshape(-1)                     # item i = 2 e + role names node edges[role, e]
+    incident = torch.sort(nodes, stable=True).indices
+    node_ptr = torch.zeros(int(n_nodes) + 1, dtype=torch.int64, device=nodes.device)
+    node_ptr[1:] = torch.cumsum(torch.bincount(nodes, minlength=int(n_nodes)), 0)
+    return node_ptr, incident
+
+
+def _edge_entry(edges, n_nodes):
+    """The cache entry of a validated ``edges`` tensor: ``[contiguous int64 edges, incidence list or None]``.  Validation
+    happens HERE, on the host (ValueError; the kernels never launch with a bad index), once per tensor: the last few
+    entries are kept, keyed by the data pointer, version, layout and device of the tensor (which is held, so the pointer
+    cannot be reused), and an edge list that is used step after step is read back once."""
+    if not isinstance(edges, torch.Tensor):
+        raise TypeError('edges must be a torch.Tensor')
+    if edges.dim() != 2 or edges.shape[0] != 2:
+        raise ValueError(f'edges must have shape (2, n_edges), got {tuple(edges.shape)}')
+    if edges.numel() and (edges.is_floating_point() or edges.is_complex() or edges.dtype == torch.bool):
+        raise ValueError(f'edges must hold integer indices, got {edges.dtype}')
+    try:
+        key = (edges.data_ptr(), edges._version, tuple(edges.shape), edges.stride(), edges.dtype, str(edges.device),
+               int(n_nodes))
+    except RuntimeError:                                              # (an inference tensor has no version: not cached)
+        key = None
+    if key is not None:
+        for k, _, entry in _EDGE_CACHE:
+            if k == key:
+                return entry
+    if edges.numel():
+        lo, hi = torch.stack([edges.min(), edges.max()]).tolist()
+        if lo < 0 or hi >= n_nodes:
+            raise ValueError(f'edges has an index outside [0, {int(n_nodes)}): min {lo}, max {hi}')
+    entry = [edges.detach().to(torch.int64).contiguous(), None]
+    if key is not None:
+        _EDGE_CACHE.append((key, edges, entry))
+        del _EDGE_CACHE[:-_EDGE_CACHE_SIZE]
+    return entry
+
+
+def check_edges(edges, n_nodes):
+    """``edges`` validated on the host -- shape ``(2, E)``, integers, every index in ``[0, n_nodes)``, else ValueError -- as a
+    contiguous int64 tensor on its device.  Cached per tensor (``_edge_entry``)."""
+    return _edge_entry(edges, n_nodes)[0]
+
+
+def edge_incidence(edges, n_nodes):
+    """``incidence_lists`` of a validated ``edges`` tensor on its device, built once per tensor and rebuilt when the tensor
+    changes (its version counts in-place writes)."""
+    return _entry_incidence(_edge_entry(edges, n_nodes), n_nodes)
+
+
+def _entry_incidence(entry, n_nodes):
+    if entry[1] is None:
+        entry[1] = incidence_lists(entry[0], n_nodes)
+    return entry[1]
+
+
+def _edge_inputs(x, edges):
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
+    if x.shape[1] != 3:
+        raise ValueError(f'x must be (n_nodes, 3), got {tuple(x.shape)}')
+    if not isinstance(edges, torch.Tensor) or edges.device != x.device:
+        raise ValueError('edges must be a tensor on the device of x')
+    return dt, x, ldx, _edge_entry(edges, x.shape[0])
+
+
+def edge_geometry(x, edges, normalize=False, inverse=False):
+    """``(distances (E,), directions (E, 3))`` across the edges ``(2, E)`` of the nodes ``x`` (n_nodes, 3; any row stride):
+    ``x[edges[1]] - x[edges[0]]`` (negated with ``inverse``), its length, and with ``normalize`` the unit vector (NaN for an
+    edge of length 0).  One launch (``tfep_edge_geometry``); float32 or float64, the dtype of ``x``."""
+    dt, x, ldx, entry = _edge_inputs(x, edges)
+    edges = entry[0]
+    E = edges.shape[1]
+    distances = torch.empty(E, dtype=dt, device=x.device)
+    directions = torch.empty(E, 3, dtype=dt, device=x.device)
+    call('tfep_edge_geometry' + _sfx(dt), ptr(x), ldx, ptr(edges), x.shape[0], E, int(bool(normalize)), int(bool(inverse)),
+         ptr(distances), ptr(directions), stream_of(x))
+    return distances, directions
+
+
+def edge_geometry_backward(x, edges, grad_distances, grad_directions, normalize=False, inverse=False):
+    """VJP of ``edge_geometry`` at ``x``: the cotangent of ``x``, every row written.  Either cotangent may be ``None`` (zero).
+    One lane per node over ``edge_incidence(edges)``, the contributions added in list order: no atomics, and the gradient of
+    a node has the same bits whatever else is in the batch."""
+    dt, x, ldx, entry = _edge_inputs(x, edges)
+    edges = entry[0]
+    N, E = x.shape[0], edges.shape[1]
+    grads = []
+    for g, shape, name in ((grad_distances, (E,), 'grad_distances'), (grad_directions, (E, 3), 'grad_directions')):
+        if g is not None:
+            g = check_device_tensor(g, name, dt).contiguous()
+            if tuple(g.shape) != shape:
+                raise ValueError(f'{name} must be {shape}, got {tuple(g.shape)}')
+        grads.append(g)
+    node_ptr, incident = _entry_incidence(entry, N) if E else (None, None)
+    gx = torch.empty(N, 3, dtype=dt, device=x.device)
+    call('tfep_edge_geometry_backward' + _sfx(dt), ptr(x), ldx, ptr(edges), N, E, ptr(node_ptr), ptr(incident),
+         int(bool(normalize)), int(bool(inverse)), ptr(grads[0]), ptr(grads[1]), ptr(gx), 3, stream_of(x))
+    return gx
+
+
+def edge_prune(distances, r_cutoff):
+    """The ids of the edges with ``distances <= r_cutoff`` in ascending order, int64 (a NaN distance is dropped): an ordered
+    stream compaction without atomics (``tfep_edge_prune_count``, one read of the total, ``tfep_edge_prune_compact``).  The
+    cutoff is compared in the dtype of ``distances``, as torch compares a tensor with a Python number."""
+    dt = _dtype(distances)
+    d = check_device_tensor(distances, 'distances', dt).detach().contiguous()
+    if d.dim() != 1:
+        raise ValueError(f'distances must be (n_edges,), got {tuple(d.shape)}')
+    E = d.shape[0]
+    if E == 0:
+        return torch.empty(0, dtype=torch.int64, device=d.device)
+    ws = torch.empty(_lib.load().tfep_edge_prune_workspace_int64s(E), dtype=torch.int64, device=d.device)
+    call('tfep_edge_prune_count' + _sfx(dt), ptr(d), E, float(r_cutoff), ptr(ws), stream_of(d))
+    n_kept = int(ws[-1])                                              # the one synchronisation, as of nonzero()
+    keep_index = torch.empty(n_kept, dtype=torch.int64, device=d.device)
+    call('tfep_edge_prune_compact' + _sfx(dt), ptr(d), E, float(r_cutoff), ptr(ws), ptr(keep_index), n_kept, stream_of(d))
+    return keep_index
+
+
+def edge_select_edges(edges, keep_index):
+    """``edges[:, keep_index]`` of int64 edges ``(2, E)`` on the HIP device (``tfep_edge_select_edges``)."""
+    check_device_tensor(edges, 'edges', torch.int64)
+    check_device_tensor(keep_index, 'keep_index', torch.int64)
+    if edges.dim() != 2 or edges.shape[0] != 2 or keep_index.dim() != 1:
+        raise ValueError('edges must be (2, n_edges) and keep_index 1-D')
+    edges, keep_index = edges.contiguous(), keep_index.contiguous()
+    out = torch.empty(2, keep_index.shape[0], dtype=torch.int64, device=edges.device)
+    call('tfep_edge_select_edges', ptr(edges), edges.shape[1], ptr(keep_index), keep_index.shape[0], ptr(out), stream_of(edges))
+    return out

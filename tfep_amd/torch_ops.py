@@ -29,6 +29,7 @@ in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the re
                                                                      (RELATIVE_FRAME_OPS)
   tfep::radial_expansion / _backward, segment_sum / segment_gather   reference embeddings/radial.py:110-130, 161-176,
                                                                      graph.py:304-316 (GRAPH_OPS)
+  tfep::edge_geometry / _backward, edge_prune, edge_select           reference graph.py:222-301 (EDGE_OPS)
   tfep::masked_linear / masked_linear_backward                       reference masked.py:220-302, 351-404
   tfep::fused_output_transformer                                     masked.py:188-208 (last layer) + the transformer
   tfep::tfep_reduce                                                  loss.py:125-140, analysis/estimator.py:73-86
@@ -793,6 +794,85 @@ radial_expansion.register_autograd(_radial_bwd, setup_context=_radial_setup)
 segment_sum.register_autograd(_segment_sum_bwd, setup_context=_segment_sum_setup)
 
 
+# ============================================================================= edge geometry, pruning
+
+@custom_op('tfep::edge_geometry', mutates_args=(), device_types=_DEV)
+def edge_geometry(x: Tensor, edges: Tensor, normalize: bool, inverse: bool) -> Tuple[Tensor, Tensor]:
+    """``(distances (E,), directions (E, 3))`` of the edges ``(2, E)`` (integers, validated on the host: ValueError) over the
+    nodes ``x`` (n_nodes, 3): ``x[edges[1]] - x[edges[0]]``, negated with ``inverse``, divided by its length with
+    ``normalize``.  float32 or float64, the dtype of ``x``."""
+    return ops.edge_geometry(x, edges, normalize, inverse)
+
+
+@custom_op('tfep::edge_geometry_backward', mutates_args=(), device_types=_DEV)
+def edge_geometry_backward(x: Tensor, edges: Tensor, grad_distances: Optional[Tensor], grad_directions: Optional[Tensor],
+                           normalize: bool, inverse: bool) -> Tensor:
+    """The cotangent of ``x``; a missing cotangent is a zero.  Bit-reproducible (no atomics), and the rows of a sample do not
+    depend on the rest of the batch."""
+    return ops.edge_geometry_backward(x, edges, grad_distances, grad_directions, normalize, inverse)
+
+
+@custom_op('tfep::edge_prune', mutates_args=(), device_types=_DEV)
+def edge_prune(distances: Tensor, r_cutoff: float) -> Tensor:
+    """``keep_index``: the ids of the edges with ``distances <= r_cutoff``, ascending, int64.  Not differentiable."""
+    return ops.edge_prune(distances, r_cutoff)
+
+
+@custom_op('tfep::edge_select', mutates_args=(), device_types=_DEV)
+def edge_select(data: Tensor, keep_index: Tensor) -> Tensor:
+    """``data[keep_index]`` of a float32 / float64 tensor with one leading row per edge (the row gather
+    ``tfep_segment_gather``); its VJP is the segment sum."""
+    flat = ops.segment_gather(data.reshape(data.shape[0], _row_width(data.shape)), keep_index)
+    return flat.reshape(keep_index.shape[0], *data.shape[1:])
+
+
+def _row_width(shape):
+    width = 1
+    for n in shape[1:]:
+        width *= n
+    return width
+
+
+edge_geometry.register_fake(lambda x, edges, normalize, inverse: (
+    x.new_empty((edges.shape[1],)), x.new_empty((edges.shape[1], 3))))
+edge_geometry_backward.register_fake(lambda x, *rest: x.new_empty(x.shape))
+edge_select.register_fake(lambda data, keep_index: data.new_empty((keep_index.shape[0], *data.shape[1:])))
+
+
+@edge_prune.register_fake
+def _(distances, r_cutoff):
+    n_kept = torch.library.get_ctx().new_dynamic_size()
+    return distances.new_empty((n_kept,), dtype=torch.int64)
+
+
+def _edge_geometry_setup(ctx, inputs, output):
+    ctx.set_materialize_grads(False)                                 # an unused output reaches the kernel as NULL
+    ctx.save_for_backward(inputs[0], inputs[1])
+    ctx.flags = tuple(inputs[2:])
+
+
+@torch.autograd.function.once_differentiable
+def _edge_geometry_bwd(ctx, g_distances, g_directions):
+    x, edges = ctx.saved_tensors
+    return torch.ops.tfep.edge_geometry_backward(x, edges, g_distances, g_directions, *ctx.flags), None, None, None
+
+
+def _edge_select_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+    ctx.shape = tuple(inputs[0].shape)
+
+
+@torch.autograd.function.once_differentiable
+def _edge_select_bwd(ctx, g):
+    (keep_index,) = ctx.saved_tensors
+    flat = torch.ops.tfep.segment_sum(g.reshape(g.shape[0], _row_width(ctx.shape)), keep_index, ctx.shape[0])
+    return flat.reshape(ctx.shape), None
+
+
+edge_geometry.register_autograd(_edge_geometry_bwd, setup_context=_edge_geometry_setup)
+edge_select.register_autograd(_edge_select_bwd, setup_context=_edge_select_setup)
+
+
 # ============================================================================= masked linear
 
 @custom_op('tfep::masked_linear', mutates_args=(), device_types=_DEV)
@@ -951,3 +1031,4 @@ ZMATRIX_OPS = ('zmatrix_place', 'zmatrix_place_backward')
 RELATIVE_FRAME_OPS = ('relative_frame_encode', 'relative_frame_decode', 'relative_frame_encode_backward',
                       'relative_frame_decode_backward')
 GRAPH_OPS = ('radial_expansion', 'radial_expansion_backward', 'segment_sum', 'segment_gather')
+EDGE_OPS = ('edge_geometry', 'edge_geometry_backward', 'edge_prune', 'edge_select')
