@@ -5,14 +5,16 @@ tensor picks the kernels, ``_dtype`` / ``_sfx``; mixed dtypes are a TypeError), 
 tensor's device and returns fresh output tensors (inputs are never modified, like the reference:
 flows/autoregressive.py:165-166).  No autograd, no CPU path.
 """
-import collections
 import ctypes
 import os
 
 import torch
 
-from . import _lib
+from . import _lib, _tables
 from ._lib import ParamLayout, SplineDesc, SplineDescF64, call, check_device_tensor, ptr, rows, stream_of
+from ._tables import (ZMATRIX_LDS_LIMIT, ZMATRIX_MAX_ATOMS, ZMATRIX_MAX_PLACED, ZMatrixTables, check_edges,  # noqa: F401
+                      check_index_table, check_zmatrix, edge_incidence, incidence_lists, index_tables,
+                      zmatrix_index_tables, zmatrix_tables)                   # (the host-built integer tables: pure torch)
 
 
 def _dtype(x):
@@ -508,71 +510,12 @@ def frame_rotate_backward(x, rot, grad_y, transposed=False):
 
 # ----------------------------------------------------------------------------- internal coordinates, polar map
 
-_TABLE_ROWS = (('pairs', 2), ('triples', 3), ('quads', 4))
-_TABLE_CACHE = []            # (key, the caller's tables, the prepared device tensors), newest last
-_TABLE_CACHE_SIZE = 8
-
-
-def check_index_table(table, name, n_rows, n_atoms):
-    """One index table on the host: ``(n_rows, count)`` integers in ``[0, n_atoms)`` as a CPU int64 tensor; anything else
-    is a ValueError.  ``None`` is the empty table."""
-    if table is None:
-        return torch.empty(n_rows, 0, dtype=torch.int64)
-    table = torch.as_tensor(table)
-    if table.dim() != 2 or table.shape[0] != n_rows:
-        raise ValueError(f'{name} must have shape ({n_rows}, n), got {tuple(table.shape)}')
-    if table.is_floating_point() or table.is_complex() or table.dtype == torch.bool:
-        raise ValueError(f'{name} must hold integer indices, got {table.dtype}')
-    table = table.detach().to('cpu', torch.int64)
-    if table.numel() and (int(table.min()) < 0 or int(table.max()) >= n_atoms):
-        raise ValueError(f'{name} has an index outside [0, {n_atoms}): min {int(table.min())}, max {int(table.max())}')
-    return table
-
-
-def index_tables(pairs, triples, quads, n_atoms, device):
-    """The three index tables as the internal-coordinate kernels take them: validated HERE, on the host (ValueError on a
-    wrong shape or an index outside ``[0, n_atoms)``; the kernels cannot reject), then ``(pairs, triples, quads,
-    atom_start, atom_items)`` as int32 tensors on ``device``.  ``atom_start`` / ``atom_items`` is the incidence list the
-    backward kernel sums over: for every atom the entries it appears in, in table order, as ``4 * entry + slot``.
-
-    The last few results are kept, keyed by the identity and version of the tensors given, so a table that is used
-    step after step is validated and uploaded once."""
-    given = (pairs, triples, quads)
-    key = (int(n_atoms), str(device)) + tuple(
-        (id(t), t._version, tuple(t.shape)) if isinstance(t, torch.Tensor) else None for t in given)
-    if all(isinstance(t, torch.Tensor) or t is None for t in given):
-        for k, held, prepared in _TABLE_CACHE:
-            if k == key and all(a is b for a, b in zip(held, given)):
-                return prepared
-    host = [check_index_table(t, name, rows_, n_atoms) for t, (name, rows_) in zip(given, _TABLE_ROWS)]
-    counts = [t.shape[1] for t in host]
-    if sum(counts) > (2 ** 31 - 1) // 4 or n_atoms > (2 ** 31 - 1) // 4:
-        raise ValueError(f'{sum(counts)} table entries of {n_atoms} atoms are too many for int32 items')
-    # entry e of a table with slots s: atom table[s, e], item 4 * (offset + e) + s; a stable sort by atom keeps the
-    # items of an atom in table order
-    atoms, items, offset = [], [], 0
-    for t in host:
-        e = torch.arange(t.shape[1]).unsqueeze(1) + offset
-        items.append((4 * e + torch.arange(t.shape[0]).unsqueeze(0)).reshape(-1))
-        atoms.append(t.t().reshape(-1))
-        offset += t.shape[1]
-    atoms, items = torch.cat(atoms), torch.cat(items)
-    order = torch.sort(atoms, stable=True).indices
-    start = torch.zeros(n_atoms + 1, dtype=torch.int64)
-    start[1:] = torch.cumsum(torch.bincount(atoms, minlength=n_atoms), 0)
-    prepared = tuple(t.to(torch.int32).contiguous().to(device) for t in (*host, start, items[order]))
-    if all(isinstance(t, torch.Tensor) or t is None for t in given):
-        _TABLE_CACHE.append((key, given, prepared))
-        del _TABLE_CACHE[:-_TABLE_CACHE_SIZE]
-    return prepared
-
-
 def _table_args(x, tables):
     """``(n_atoms, pointer / count arguments, counts)`` of prepared tables (``index_tables``) for the rows ``x``."""
     n = _points(x, 3, 'x')
     pairs, triples, quads, atom_start, atom_items = tables
     args, counts = [], []
-    for t, (name, n_rows) in zip((pairs, triples, quads), _TABLE_ROWS):
+    for t, (name, n_rows) in zip((pairs, triples, quads), _tables.TABLE_ROWS):
         check_device_tensor(t, name, torch.int32)
         if t.dim() != 2 or t.shape[0] != n_rows or not t.is_contiguous():
             raise ValueError(f'{name} must be a contiguous ({n_rows}, n) int32 table, got {tuple(t.shape)}')
@@ -651,129 +594,6 @@ def polar_backward(a, b, to_cartesian, grad_0, grad_1, grad_log_det_J):
 
 
 # ----------------------------------------------------------------------------- placement from a Z-matrix
-
-ZMATRIX_LDS_LIMIT = 160 * 1024           # bytes of LDS one sample row may take (csrc/zmatrix.hip)
-ZMATRIX_MAX_ATOMS = ZMATRIX_LDS_LIMIT // 24          # the forward keeps 3 doubles per atom
-ZMATRIX_MAX_PLACED = ZMATRIX_LDS_LIMIT // 72         # the backward keeps 9 doubles per placed atom
-ZMatrixTables = collections.namedtuple('ZMatrixTables', 'rows level_start fixed atom_start atom_items')
-_ZMATRIX_CACHE = []          # (key, the caller's (z_matrix, fixed_atoms), (placement tables, index tables)), newest last
-
-
-def _integer_table(table, name):
-    table = torch.as_tensor(table)
-    if table.is_floating_point() or table.is_complex() or table.dtype == torch.bool:
-        raise ValueError(f'{name} must hold integer indices, got {table.dtype}')
-    return table.detach().to('cpu', torch.int64)
-
-
-def check_zmatrix(z_matrix, fixed_atoms, n_atoms):
-    """A Z-matrix on the host: ``z_matrix`` ``(n_ic, 4)`` integer rows ``(i, j, k, l)`` -- atom ``i`` is placed from the
-    atoms ``j, k, l`` -- in any order, ``fixed_atoms`` ``(n_fixed,)`` the atoms whose positions are given.  Returns both as
-    CPU int64 tensors and the level of every row (the fixed atoms are level 0, an atom is one level above the highest of
-    its references).  ValueError unless: integer dtypes; the shapes above; every index in ``[0, n_atoms)`` (a negative
-    entry, bgflow's ``-1`` of a global row, is not supported); four distinct atoms in a row; no atom placed twice, fixed
-    twice, or both; fixed and placed atoms together exactly ``range(n_atoms)``; at least 3 fixed atoms; no cycle; and a
-    size the kernels hold in LDS."""
-    z, fixed = _integer_table(z_matrix, 'z_matrix'), _integer_table(fixed_atoms, 'fixed_atoms')
-    if z.dim() != 2 or z.shape[1] != 4:
-        raise ValueError(f'z_matrix must have shape (n_ic, 4), got {tuple(z.shape)}')
-    if fixed.dim() != 1:
-        raise ValueError(f'fixed_atoms must have shape (n_fixed,), got {tuple(fixed.shape)}')
-    for t, name in ((z, 'z_matrix'), (fixed, 'fixed_atoms')):
-        if t.numel() and int(t.min()) < 0:
-            raise ValueError(f'{name} has a negative entry ({int(t.min())}): rows that place an atom from the global '
-                             'frame are not supported, every reference must be an atom')
-        if t.numel() and int(t.max()) >= n_atoms:
-            raise ValueError(f'{name} has an index outside [0, {n_atoms}): max {int(t.max())}')
-    if len(fixed) < 3:
-        raise ValueError(f'a Z-matrix needs at least 3 fixed atoms to place the first row from, got {len(fixed)}')
-    srt = z.sort(dim=1).values
-    if bool((srt[:, 1:] == srt[:, :-1]).any()):
-        bad = int((srt[:, 1:] == srt[:, :-1]).any(1).nonzero()[0])
-        raise ValueError(f'z_matrix row {bad} {z[bad].tolist()} does not name four distinct atoms')
-    placed_count = torch.bincount(z[:, 0], minlength=n_atoms)
-    fixed_count = torch.bincount(fixed, minlength=n_atoms)
-    if bool((placed_count > 1).any()):
-        raise ValueError(f'atom {int((placed_count > 1).nonzero()[0])} is placed twice')
-    if bool((fixed_count > 1).any()):
-        raise ValueError(f'atom {int((fixed_count > 1).nonzero()[0])} is fixed twice')
-    if bool(((placed_count > 0) & (fixed_count > 0)).any()):
-        raise ValueError(f'atom {int(((placed_count > 0) & (fixed_count > 0)).nonzero()[0])} is both fixed and placed')
-    if bool((placed_count + fixed_count == 0).any()):
-        raise ValueError(f'atom {int((placed_count + fixed_count == 0).nonzero()[0])} of the {n_atoms} atoms is neither '
-                         'fixed nor placed')
-    if n_atoms > ZMATRIX_MAX_ATOMS or len(z) > ZMATRIX_MAX_PLACED:
-        raise ValueError(f'{n_atoms} atoms, {len(z)} of them placed: the kernels keep a row in {ZMATRIX_LDS_LIMIT} bytes of '
-                         f'LDS, which holds at most {ZMATRIX_MAX_ATOMS} atoms and {ZMATRIX_MAX_PLACED} placed atoms')
-    # levels: a row is ready once its three references have a level
-    atom_level = torch.full((n_atoms,), -1, dtype=torch.int64)
-    atom_level[fixed] = 0
-    row_level = torch.full((len(z),), -1, dtype=torch.int64)
-    while bool((row_level < 0).any()):
-        refs = atom_level[z[:, 1:]]
-        ready = (row_level < 0) & (refs >= 0).all(1)
-        if not bool(ready.any()):
-            raise ValueError(f'z_matrix has a cycle: row {int((row_level < 0).nonzero()[0])} can never be placed')
-        row_level[ready] = refs[ready].max(1).values + 1
-        atom_level[z[ready, 0]] = row_level[ready]
-    return z, fixed, row_level
-
-
-def _zmatrix_prepared(z_matrix, fixed_atoms, n_atoms, device):
-    given = (z_matrix, fixed_atoms)
-    cacheable = all(isinstance(t, torch.Tensor) for t in given)
-    key = (int(n_atoms), str(device)) + tuple((id(t), t._version, tuple(t.shape)) for t in given if cacheable)
-    if cacheable:
-        for k, held, prepared in _ZMATRIX_CACHE:
-            if k == key and all(a is b for a, b in zip(held, given)):
-                return prepared
-    z, fixed, row_level = check_zmatrix(z_matrix, fixed_atoms, int(n_atoms))
-    n_ic = len(z)
-    # rows sorted by level, the caller's order kept within a level
-    order = torch.sort(row_level, stable=True).indices
-    n_levels = int(row_level.max()) if n_ic else 0
-    level_start = torch.zeros(n_levels + 1, dtype=torch.int64)
-    if n_ic:
-        level_start[1:] = torch.cumsum(torch.bincount(row_level - 1, minlength=n_levels), 0)
-    rows_ = torch.cat([z[order].t(), order.unsqueeze(0)])                   # (5, n_ic): i, j, k, l, column
-    # sorted row s names atom rows_[1 + slot, s] as reference `slot`: item 4 * s + slot; a stable sort by atom keeps the
-    # items of an atom in table order
-    items = (4 * torch.arange(n_ic).unsqueeze(1) + torch.arange(3).unsqueeze(0)).reshape(-1)
-    atoms = rows_[1:4].t().reshape(-1)
-    by_atom = torch.sort(atoms, stable=True).indices
-    start = torch.zeros(n_atoms + 1, dtype=torch.int64)
-    start[1:] = torch.cumsum(torch.bincount(atoms, minlength=n_atoms), 0)
-    place = ZMatrixTables(*(t.to(torch.int32).contiguous().to(device) for t in (rows_, level_start, fixed, start,
-                                                                              items[by_atom])))
-    # the same Z-matrix for the way back (internal_coordinates): one entry per row, in the caller's order
-    index = index_tables(z[:, :2].t().contiguous(), z[:, :3].t().contiguous(), z.t().contiguous(), int(n_atoms), device)
-    prepared = (place, index, fixed.to(device))
-    if cacheable:
-        _ZMATRIX_CACHE.append((key, given, prepared))
-        del _ZMATRIX_CACHE[:-_TABLE_CACHE_SIZE]
-    return prepared
-
-
-def zmatrix_tables(z_matrix, fixed_atoms, n_atoms, device):
-    """A Z-matrix as the placement kernels take it: validated HERE, on the host (``check_zmatrix``: the kernels cannot
-    reject), then ``ZMatrixTables(rows, level_start, fixed, atom_start, atom_items)`` as int32 tensors on ``device``:
-
-    ``rows`` ``(5, n_ic)``: the Z-matrix rows sorted by level (the caller's order within a level) as columns ``(i, j, k,
-    l)``, and in the fifth row the permutation back: the caller's row, which is the column of ``(d, a, t)`` with the values
-    of that atom.  ``level_start``: ``n_levels + 1`` offsets into the sorted rows.  ``fixed``: the fixed atoms.
-    ``atom_start`` / ``atom_items``: the incidence list the backward kernel gathers over, for every atom the rows placed
-    from it, in sorted order, as ``4 * sorted row + slot`` (slot 0, 1, 2: the atom is the row's j, k, l).
-
-    The last few results are kept, keyed by the identity, version and shape of the two tensors given."""
-    return _zmatrix_prepared(z_matrix, fixed_atoms, n_atoms, device)[0]
-
-
-def zmatrix_index_tables(z_matrix, fixed_atoms, n_atoms, device):
-    """The same Z-matrix for ``internal_coordinates``: ``(index tables, fixed atoms)`` -- the five tensors of
-    ``index_tables`` for the pairs ``(i, j)``, triples ``(i, j, k)`` and quads ``(i, j, k, l)`` of the rows in the caller's
-    order, and the fixed atoms as an int64 tensor on ``device``.  Validated and cached with ``zmatrix_tables``."""
-    return _zmatrix_prepared(z_matrix, fixed_atoms, n_atoms, device)[1:]
-
 
 def _zmatrix_args(tables, n_atoms=None):
     """The table arguments of the placement entry points, with the sizes ``(n_ic, n_fixed, n_atoms)``."""
@@ -1580,76 +1400,6 @@ def segment_gather(grad_out, segment_ids):
 
 # ----------------------------------------------------------------------------- edge geometry, pruning
 
-_EDGE_CACHE = []             # (key, the caller's edges, [contiguous int64 edges, incidence list or None]), newest last
-_EDGE_CACHE_SIZE = 4
-
-
-def incidence_lists(edges, n_nodes):
-    """The node-incidence list (CSR) of a ``(2, E)`` edge list, the host logic of the backward of ``edge_geometry``:
-    ``(node_ptr (n_nodes + 1,), incident (2 E,))`` as int64 tensors on the device of ``edges`` (CPU tensors, numpy arrays and
-    lists stay on the CPU).  ``incident[node_ptr[n]:node_ptr[n + 1]]`` holds the items ``2 e + role`` of node ``n`` in
-    ascending order: role 0 where ``n`` is the source ``edges[0, e]``, role 1 where it is the destination ``edges[1, e]`` --
-    ascending edges, the source entry first on a tie.  A stable sort by node of the items in ascending order.  The indices
-    are taken as given (``check_edges`` validates them)."""
-    edges = torch.as_tensor(edges)
-    if edges.dim() != 2 or edges.shape[0] != 2:
-        raise ValueError(f'edges must have shape (2, n_edges), got {tuple(edges.shape)}')
-    nodes = edges.to(torch.int64).t().reshape(-1)                     # item i = 2 e + role names node edges[role, e]
-    incident = torch.sort(nodes, stable=True).indices
-    node_ptr = torch.zeros(int(n_nodes) + 1, dtype=torch.int64, device=nodes.device)
-    node_ptr[1:] = torch.cumsum(torch.bincount(nodes, minlength=int(n_nodes)), 0)
-    return node_ptr, incident
-
-
-def _edge_entry(edges, n_nodes):
-    """The cache entry of a validated ``edges`` tensor: ``[contiguous int64 edges, incidence list or None]``.  Validation
-    happens HERE, on the host (ValueError; the kernels never launch with a bad index), once per tensor: the last few
-    entries are kept, keyed by the data pointer, version, layout and device of the tensor (which is held, so the pointer
-    cannot be reused), and an edge list that is used step after step is read back once."""
-    if not isinstance(edges, torch.Tensor):
-        raise TypeError('edges must be a torch.Tensor')
-    if edges.dim() != 2 or edges.shape[0] != 2:
-        raise ValueError(f'edges must have shape (2, n_edges), got {tuple(edges.shape)}')
-    if edges.numel() and (edges.is_floating_point() or edges.is_complex() or edges.dtype == torch.bool):
-        raise ValueError(f'edges must hold integer indices, got {edges.dtype}')
-    try:
-        key = (edges.data_ptr(), edges._version, tuple(edges.shape), edges.stride(), edges.dtype, str(edges.device),
-               int(n_nodes))
-    except RuntimeError:                                              # (an inference tensor has no version: not cached)
-        key = None
-    if key is not None:
-        for k, _, entry in _EDGE_CACHE:
-            if k == key:
-                return entry
-    if edges.numel():
-        lo, hi = torch.stack([edges.min(), edges.max()]).tolist()
-        if lo < 0 or hi >= n_nodes:
-            raise ValueError(f'edges has an index outside [0, {int(n_nodes)}): min {lo}, max {hi}')
-    entry = [edges.detach().to(torch.int64).contiguous(), None]
-    if key is not None:
-        _EDGE_CACHE.append((key, edges, entry))
-        del _EDGE_CACHE[:-_EDGE_CACHE_SIZE]
-    return entry
-
-
-def check_edges(edges, n_nodes):
-    """``edges`` validated on the host -- shape ``(2, E)``, integers, every index in ``[0, n_nodes)``, else ValueError -- as a
-    contiguous int64 tensor on its device.  Cached per tensor (``_edge_entry``)."""
-    return _edge_entry(edges, n_nodes)[0]
-
-
-def edge_incidence(edges, n_nodes):
-    """``incidence_lists`` of a validated ``edges`` tensor on its device, built once per tensor and rebuilt when the tensor
-    changes (its version counts in-place writes)."""
-    return _entry_incidence(_edge_entry(edges, n_nodes), n_nodes)
-
-
-def _entry_incidence(entry, n_nodes):
-    if entry[1] is None:
-        entry[1] = incidence_lists(entry[0], n_nodes)
-    return entry[1]
-
-
 def _edge_inputs(x, edges):
     dt = _dtype(x)
     x, ldx = rows(x, 'x', dt)
@@ -1657,7 +1407,7 @@ def _edge_inputs(x, edges):
         raise ValueError(f'x must be (n_nodes, 3), got {tuple(x.shape)}')
     if not isinstance(edges, torch.Tensor) or edges.device != x.device:
         raise ValueError('edges must be a tensor on the device of x')
-    return dt, x, ldx, _edge_entry(edges, x.shape[0])
+    return dt, x, ldx, _tables.edge_entry(edges, x.shape[0])
 
 
 def edge_geometry(x, edges, normalize=False, inverse=False):
@@ -1688,7 +1438,7 @@ def edge_geometry_backward(x, edges, grad_distances, grad_directions, normalize=
             if tuple(g.shape) != shape:
                 raise ValueError(f'{name} must be {shape}, got {tuple(g.shape)}')
         grads.append(g)
-    node_ptr, incident = _entry_incidence(entry, N) if E else (None, None)
+    node_ptr, incident = _tables.edge_incidence(edges, N, entry) if E else (None, None)
     gx = torch.empty(N, 3, dtype=dt, device=x.device)
     call('tfep_edge_geometry_backward' + _sfx(dt), ptr(x), ldx, ptr(edges), N, E, ptr(node_ptr), ptr(incident),
          int(bool(normalize)), int(bool(inverse)), ptr(grads[0]), ptr(grads[1]), ptr(gx), 3, stream_of(x))
