@@ -1065,6 +1065,11 @@ int tfep_zmatrix_place_backward_f64(const double* x, int64_t ldx, const double* 
         const int32_t* fixed, int n_fixed, const int32_t* atom_start, const int32_t* atom_items, int n_items,
         const double* gx, int64_t ldgx, const double* gl, double* gd, double* ga, double* gt, double* g_fixed, int n_atoms,
         int B, void* stream);
+/* The launch shape the entry points above choose for a Z-matrix of n_atoms atoms, n_ic of them placed (backward != 0: of
+ * zmatrix_place_backward): the sample rows (waves) of a workgroup -- as many as fit 64 KiB of LDS, four at the most, one
+ * when a row alone needs more -- and the workgroup's dynamic LDS in bytes.  The launchers take their shape from the same
+ * function.  TFEP_ERR_INVALID_ARGUMENT, as they return it, for a row beyond the 160 KiB limit.  Touches no device. */
+int tfep_zmatrix_launch_shape(int n_atoms, int n_ic, int backward, int* rows_per_block, int64_t* lds_bytes);
 
 /* ------------------------------------------------------------------------- */
 /* The relative frame of the mixed coordinates (app/mixedmaf.py:1216-1375)    */

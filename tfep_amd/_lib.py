@@ -308,6 +308,8 @@ for _s in ('', '_f64'):
         'tfep_zmatrix_place_backward' + _s: (c_int, [_P, c_int64, *_DAT, *_ZTABLES, _P, _P, c_int, _P, c_int64, _P,
                                                      _P, _P, _P, _P, c_int, c_int, _P]),
     })
+# (n_atoms, n_ic, backward) -> the rows of a workgroup and its LDS bytes, as the two launchers choose them
+_SIGNATURES['tfep_zmatrix_launch_shape'] = (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int64)])
 # the relative frame of the mixed coordinates (csrc/relframe.hip): (n_c, remove_origin, remove_axis, remove_plane)
 _REL = [c_int] * 4
 for _s in ('', '_f64'):

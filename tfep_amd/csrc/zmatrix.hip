@@ -208,21 +208,25 @@ __global__ void __launch_bounds__(256) zmatrix_place_backward_kernel(
 
 // ---------------------------------------------------------------------------------------------------------------- host
 
-// Rows per workgroup for `row_bytes` of LDS a row, and the workgroup's LDS; an invalid argument when one row does not fit.
-static int zmatrix_rows(const char* who, int64_t row_bytes, int* rows, size_t* lds) {
+// The launch shape of a kernel (the forward keeps 3 doubles per atom, the backward 9 per placed atom): rows per workgroup
+// and the workgroup's LDS; an invalid argument when one row does not fit.  The launchers and the exported query
+// tfep_zmatrix_launch_shape both come through here.
+static int zmatrix_launch_shape(const char* who, int n_atoms, int n_ic, bool backward, int* rows, int64_t* lds) {
+    TFEP_REQUIRE(n_atoms >= 0 && n_ic >= 0, "%s: negative size", who);
+    const int64_t row_bytes = (backward ? (int64_t)9 * n_ic : (int64_t)3 * n_atoms) * (int64_t)sizeof(double);
     TFEP_REQUIRE(row_bytes <= ZMATRIX_LDS_LIMIT,
                  "%s: a row needs %lld bytes of LDS, the limit is %lld (6826 atoms forward, 2275 placed atoms backward)", who,
                  (long long)row_bytes, (long long)ZMATRIX_LDS_LIMIT);
     const int64_t fit = row_bytes > 0 ? ZMATRIX_LDS_SHARED / row_bytes : ZMATRIX_MAX_ROWS;
     *rows = fit < 1 ? 1 : fit > ZMATRIX_MAX_ROWS ? ZMATRIX_MAX_ROWS : (int)fit;
-    *lds = (size_t)(*rows * row_bytes);
+    *lds = *rows * row_bytes;
     return TFEP_OK;
 }
 
 // A workgroup that takes more dynamic LDS than a kernel gets by default (48 KiB is the lowest default of the runtimes in
 // use) needs the attribute; set once per kernel and device, to the whole limit.
 template <typename K>
-static int allow_lds(K kernel, size_t lds, bool (&done)[TFEP_MAX_DEVICES], const char* who) {
+static int allow_lds(K kernel, int64_t lds, bool (&done)[TFEP_MAX_DEVICES], const char* who) {
     bool& set = done[current_device_slot()];
     if (lds > 48 * 1024 && !set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -253,14 +257,14 @@ static int launch_zmatrix_place(const char* who, const T* d, int64_t ldd, const 
     TFEP_REQUIRE(ldd >= tb.n_ic && lda >= tb.n_ic && ldt >= tb.n_ic && ldf >= (int64_t)3 * tb.n_fixed &&
                      ldx >= (int64_t)3 * tb.n_atoms, "%s: a row stride is shorter than the row", who);
     int rows;
-    size_t lds;
-    if (int rc = zmatrix_rows(who, (int64_t)3 * tb.n_atoms * sizeof(double), &rows, &lds)) return rc;
+    int64_t lds;
+    if (int rc = zmatrix_launch_shape(who, tb.n_atoms, tb.n_ic, false, &rows, &lds)) return rc;
     if (B == 0) return TFEP_OK;
     TFEP_REQUIRE(log_det_J && (x || !tb.n_atoms) && (x_fixed || !tb.n_fixed) && ((d && a && t) || !tb.n_ic),
                  "%s: d/a/t/x_fixed/x/log_det_J must be non-NULL", who);
     static bool attr_done[TFEP_MAX_DEVICES] = {};
     if (int rc = allow_lds(zmatrix_place_kernel<T>, lds, attr_done, who)) return rc;
-    zmatrix_place_kernel<T><<<(unsigned)((B + rows - 1) / rows), rows * WAVE, lds, (hipStream_t)stream>>>(
+    zmatrix_place_kernel<T><<<(unsigned)((B + rows - 1) / rows), rows * WAVE, (size_t)lds, (hipStream_t)stream>>>(
         d, ldd, a, lda, t, ldt, x_fixed, ldf, tb, x, ldx, log_det_J, rows, B);
     return check_launch("zmatrix_place_kernel");
 }
@@ -275,14 +279,14 @@ static int launch_zmatrix_place_backward(const char* who, const T* x, int64_t ld
     TFEP_REQUIRE(inc.n_items >= 0 && (inc.atom_items || inc.n_items == 0), "%s: n_items=%d without the items", who,
                  inc.n_items);
     int rows;
-    size_t lds;
-    if (int rc = zmatrix_rows(who, (int64_t)9 * tb.n_ic * sizeof(double), &rows, &lds)) return rc;
+    int64_t lds;
+    if (int rc = zmatrix_launch_shape(who, tb.n_atoms, tb.n_ic, true, &rows, &lds)) return rc;
     if (B == 0 || tb.n_atoms == 0) return TFEP_OK;
     TFEP_REQUIRE(x && gx && gl && inc.atom_start && (g_fixed || !tb.n_fixed) && ((d && a && t && gd && ga && gt) || !tb.n_ic),
                  "%s: x/d/a/t, the cotangents, the outputs and atom_start must be non-NULL", who);
     static bool attr_done[TFEP_MAX_DEVICES] = {};
     if (int rc = allow_lds(zmatrix_place_backward_kernel<T>, lds, attr_done, who)) return rc;
-    zmatrix_place_backward_kernel<T><<<(unsigned)((B + rows - 1) / rows), rows * WAVE, lds, (hipStream_t)stream>>>(
+    zmatrix_place_backward_kernel<T><<<(unsigned)((B + rows - 1) / rows), rows * WAVE, (size_t)lds, (hipStream_t)stream>>>(
         x, ldx, d, ldd, a, lda, t, ldt, tb, inc, gx, ldgx, gl, gd, ga, gt, g_fixed, rows, B);
     return check_launch("zmatrix_place_backward_kernel");
 }
@@ -316,4 +320,9 @@ using namespace tfep;
 extern "C" {
 TFEP_ZMATRIX_ENTRY(float, )
 TFEP_ZMATRIX_ENTRY(double, _f64)
+
+int tfep_zmatrix_launch_shape(int n_atoms, int n_ic, int backward, int* rows_per_block, int64_t* lds_bytes) {
+    TFEP_REQUIRE(rows_per_block && lds_bytes, "zmatrix_launch_shape: rows_per_block and lds_bytes must be non-NULL");
+    return zmatrix_launch_shape("zmatrix_launch_shape", n_atoms, n_ic, backward != 0, rows_per_block, lds_bytes);
+}
 }  // extern "C"

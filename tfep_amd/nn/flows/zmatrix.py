@@ -25,9 +25,10 @@ class ZMatrixFlow(torch.nn.Module):
     ``forward`` converts to that layout, runs ``flow``, places the atoms back and returns ``(y, log_det_J)`` with the
     three log-dets added; ``inverse`` does the same with ``flow.inverse``.
 
-    The wrapped flow is free to move an angle out of ``(0, pi)`` or a distance below zero.  The placement accepts such
-    values, but the way in returns angles in ``[0, pi]`` and distances ``>= 0``, so the composition is then no longer
-    inverted by ``inverse``: keeping the angles inside ``(0, pi)`` (a bounded transformer, for instance) is the caller's
+    The wrapped flow is free to move an angle out of ``(0, pi)``, a distance below zero or a dihedral across ``+-pi``.
+    The placement accepts such values, but the way in returns angles in ``[0, pi]``, distances ``>= 0`` and dihedrals in
+    ``(-pi, pi]``, so the composition is then no longer inverted by ``inverse``: keeping the angles inside ``(0, pi)`` (a
+    bounded transformer, for instance) and treating the dihedrals as periodic (a circular transformer) is the caller's
     concern.  Eager only: the host-side table lookup is not captured by ``GraphedFlow``.
     """
 
