@@ -1159,6 +1159,49 @@ int tfep_tfep_reduce_f64(const double* target_potentials, const double* log_det_
  */
 int tfep_bootstrap_fep(const float* work, const float* bias, const int64_t* indices, const float* weights,
                        int64_t n_data, int64_t n_resamples, int64_t sample_size, float kT, double* out, void* stream);
+/* The same on float64 work values, biases and weights. */
+int tfep_bootstrap_fep_f64(const double* work, const double* bias, const int64_t* indices, const double* weights,
+                           int64_t n_data, int64_t n_resamples, int64_t sample_size, double kT, double* out, void* stream);
+
+/*
+ * The bootstrap with the resamples drawn inside the kernel.  The stream (csrc/bootstrap_rng.h):
+ * Philox4x32-10, key (seed & 0xffffffff, seed >> 32) for a seed in [0, 2^63), counter (q & 0xffffffff, q >> 32, r, stream):
+ * r = offset + row is the global resample number (offset + n_resamples <= 2^31), q the group within the resample;
+ *   stream 0, indices: word k of group q is draw j = 4q + k, i_j = (uint64(word) * high) >> 32, 1 <= high < 2^31;
+ *   stream 1, Bayesian weights: draw j takes words (a, b) = (2 (j % 2), 2 (j % 2) + 1) of group q = j / 2,
+ *     u_j = (((a >> 5) * 2^26 + (b >> 6)) + 0.5) * 2^-53,  E_j = -log u_j,  weights E_j / sum_j E_j.
+ * A draw depends on (seed, r, j) alone.
+ *
+ * The table entry point writes, from work / bias (n) (bias may be NULL), table[i] = exp(a_i - M) with
+ * a_i = -work_i/kT + bias_i/kT and M = max_i a_i, with a bias also table[n + i] = exp(b_i - M_b), b_i = bias_i/kT;
+ * stats[0] = M, stats[1] = M_b; *flag != 0 if some a_i or b_i is NaN or +inf.  table: (n) or (2n) float64, stats: (2) float64,
+ * flag: (1) int, workspace: tfep_bootstrap_table_workspace_doubles(n) float64, all on the device.  Two launches, no atomics.
+ */
+int64_t tfep_bootstrap_table_workspace_doubles(int64_t n);
+int tfep_bootstrap_table(const float* work, const float* bias, int64_t n, float kT, double* table, double* stats, int* flag,
+                         double* workspace, void* stream);
+int tfep_bootstrap_table_f64(const double* work, const double* bias, int64_t n, double kT, double* table, double* stats,
+                             int* flag, double* workspace, void* stream);
+/*
+ * out[row] = the estimate of resample offset + row, one workgroup per resample, from the table of the same (work, bias,
+ * n_data, kT):
+ *   standard:  -kT (M + log sum_j table[i_j] - log sample_size),  with a bias
+ *              -kT ((M + log sum_j table[i_j]) - (M_b + log sum_j table[n_data + i_j]))
+ *   Bayesian (sample_size == high, bias == NULL):  -kT (M + log sum_j E_j table[j] - log sum_j E_j).
+ * If *flag is set, or a sum is below 2^-1000, the workgroup recomputes its resample from work / bias with the arithmetic of
+ * the explicit entry point above on the same draws.  high <= n_data: every index drawn is < high.
+ */
+int tfep_bootstrap_fep_resampled(const float* work, const float* bias, const double* table, const double* stats,
+                                 const int* flag, int64_t n_data, int64_t n_resamples, int64_t sample_size, int64_t high,
+                                 int64_t seed, int64_t offset, int bayesian, float kT, double* out, void* stream);
+int tfep_bootstrap_fep_resampled_f64(const double* work, const double* bias, const double* table, const double* stats,
+                                     const int* flag, int64_t n_data, int64_t n_resamples, int64_t sample_size, int64_t high,
+                                     int64_t seed, int64_t offset, int bayesian, double kT, double* out, void* stream);
+/* The resamples of the same stream: out (n_resamples, sample_size) int64 indices / float64 weights summing to 1 per row. */
+int tfep_bootstrap_resample_indices(int64_t n_resamples, int64_t sample_size, int64_t high, int64_t seed, int64_t offset,
+                                    int64_t* out, void* stream);
+int tfep_bootstrap_resample_weights(int64_t n_resamples, int64_t sample_size, int64_t seed, int64_t offset, double* out,
+                                    void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Config 5: EGNN dynamics of the continuous flow (tfep/nn/dynamics/egnn.py,   */

@@ -345,6 +345,20 @@ _SIGNATURES.update({
     'tfep_edge_prune_workspace_int64s': (c_int64, [c_int64]),
     'tfep_edge_select_edges': (c_int, [_P, c_int64, _P, c_int64, _P, _P]),
 })
+# the bootstrap on float64 data and with in-kernel resampling (csrc/reduce.hip, csrc/bootstrap_rng.h); kT is a float / a
+# double; the resampling arguments are (n_resamples, sample_size[, high], seed, offset)
+for _s, _c in (('', c_float), ('_f64', c_double)):
+    _SIGNATURES.update({
+        'tfep_bootstrap_table' + _s: (c_int, [_P, _P, c_int64, _c, _P, _P, _P, _P, _P]),
+        'tfep_bootstrap_fep_resampled' + _s: (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                                      c_int, _c, _P, _P]),
+    })
+_SIGNATURES.update({
+    'tfep_bootstrap_fep_f64': (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, c_double, _P, _P]),
+    'tfep_bootstrap_table_workspace_doubles': (c_int64, [c_int64]),
+    'tfep_bootstrap_resample_indices': (c_int, [c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P]),
+    'tfep_bootstrap_resample_weights': (c_int, [c_int64, c_int64, c_int64, c_int64, _P, _P]),
+})
 del _SEL, _FRAME, _TABLES, _DAT, _ZTABLES, _REL, _s, _c
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))

@@ -5,6 +5,7 @@
 // Two kernels: per-block partials (online max / rescaled-sum, fp64) then a single-block
 // combine.  No atomics -> bit-reproducible for a fixed N.
 #include "common.h"
+#include "bootstrap_rng.h"
 
 namespace tfep {
 
@@ -243,8 +244,10 @@ __device__ inline MaxSum ms_block_reduce(MaxSum v, MaxSum* sh) {
     return r;
 }
 
-__global__ void __launch_bounds__(256) bootstrap_fep_kernel(const float* __restrict__ work, const float* __restrict__ bias,
-                                                            const int64_t* __restrict__ idx, const float* __restrict__ weights,
+// T = float: the float32 data of the reference's default dtype; T = double: float64 work values, biases and weights.
+template <typename T>
+__global__ void __launch_bounds__(256) bootstrap_fep_kernel(const T* __restrict__ work, const T* __restrict__ bias,
+                                                            const int64_t* __restrict__ idx, const T* __restrict__ weights,
                                                             int64_t n_data, int64_t S, double inv_kT, double kT,
                                                             double* __restrict__ out) {
     __shared__ MaxSum sh[4];
@@ -272,6 +275,291 @@ __global__ void __launch_bounds__(256) bootstrap_fep_kernel(const float* __restr
             lse -= log((double)S);
         out[r] = -kT * lse;
     }
+}
+
+// The loop of bootstrap_fep_kernel with the item of draw j named by item(j, i, lw) instead of read from memory: i is the
+// data item and, where item returns true, lw the log-weight of the draw.  The resampling kernel below replays a resample
+// through it, item j on thread j % 256 as above, so that a replayed resample is what the explicit kernel gives on the same
+// draws.  (The explicit kernel keeps its own loop: its float32 code stays what it was, instruction for instruction.)
+template <typename T, typename Item>
+__device__ inline void replay_online(const T* __restrict__ work, const T* __restrict__ bias, int64_t n_data, int64_t S,
+                                     double inv_kT, Item item, MaxSum& a, MaxSum& b) {
+    for (int64_t j = threadIdx.x; j < S; j += blockDim.x) {
+        int64_t i;
+        double lw = 0.0;
+        const bool weighted = item(j, i, lw);
+        if (i < 0 || i >= n_data) continue;
+        double v = -(double)work[i] * inv_kT;
+        if (weighted) v += lw;
+        if (bias) {
+            const double bb = (double)bias[i] * inv_kT;
+            v += bb;
+            ms_add(b, bb);
+        }
+        ms_add(a, v);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// The same bootstrap with the resamples drawn in the kernel (bootstrap_rng.h) from a table of exponentials:
+//   t_i = exp(a_i - M),  a_i = -work_i / kT (+ bias_i / kT),  M = max_i a_i;   u_i = exp(b_i - M_b),  b_i = bias_i / kT
+// so that a resample is a gather and a sum, sum_j exp(a_{i_j}) = exp(M) sum_j t_{i_j}.  Only n distinct exponentials
+// exist, whatever the number of resamples.  The table is built by two launches: per-workgroup maxima (and a flag for a NaN
+// or +inf item, for which no table exists), then the table itself, each workgroup taking the maximum of the partial
+// maxima on its own -- a maximum does not depend on the order, so no atomics and no third launch.
+// ------------------------------------------------------------------------------------------
+constexpr int TABLE_MAX_BLOCKS = 1024;
+
+// maxima of three values over the workgroup, on every thread
+__device__ inline void block_max3(double& x, double& y, double& z, double (*sh)[4]) {
+    x = wave_max(x);
+    y = wave_max(y);
+    z = wave_max(z);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+        sh[0][wave] = x;
+        sh[1][wave] = y;
+        sh[2][wave] = z;
+    }
+    __syncthreads();
+    x = fmax(fmax(sh[0][0], sh[0][1]), fmax(sh[0][2], sh[0][3]));
+    y = fmax(fmax(sh[1][0], sh[1][1]), fmax(sh[1][2], sh[1][3]));
+    z = fmax(fmax(sh[2][0], sh[2][1]), fmax(sh[2][2], sh[2][3]));
+    __syncthreads();
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) bootstrap_table_max_kernel(const T* __restrict__ work, const T* __restrict__ bias,
+                                                                  int64_t n, double inv_kT, double* __restrict__ partial) {
+    __shared__ double sh[3][4];
+    double ma = -INFINITY, mb = -INFINITY, bad = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        double a = -(double)work[i] * inv_kT;
+        if (bias) {
+            const double bb = (double)bias[i] * inv_kT;
+            a += bb;
+            if (!(bb < INFINITY)) bad = 1.0;                     // NaN or +inf
+            mb = fmax(mb, bb);
+        }
+        if (!(a < INFINITY)) bad = 1.0;
+        ma = fmax(ma, a);
+    }
+    block_max3(ma, mb, bad, sh);
+    if (threadIdx.x == 0) {
+        partial[3 * blockIdx.x + 0] = ma;
+        partial[3 * blockIdx.x + 1] = mb;
+        partial[3 * blockIdx.x + 2] = bad;
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) bootstrap_table_fill_kernel(const T* __restrict__ work, const T* __restrict__ bias,
+                                                                   int64_t n, double inv_kT,
+                                                                   const double* __restrict__ partial, int n_partial,
+                                                                   double* __restrict__ table, double* __restrict__ stats,
+                                                                   int* __restrict__ flag) {
+    __shared__ double sh[3][4];
+    double ma = -INFINITY, mb = -INFINITY, bad = 0.0;
+    for (int p = threadIdx.x; p < n_partial; p += blockDim.x) {
+        ma = fmax(ma, partial[3 * p + 0]);
+        mb = fmax(mb, partial[3 * p + 1]);
+        bad = fmax(bad, partial[3 * p + 2]);
+    }
+    block_max3(ma, mb, bad, sh);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        stats[0] = ma;
+        stats[1] = mb;
+        *flag = bad != 0.0;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        double a = -(double)work[i] * inv_kT;
+        if (bias) {
+            const double bb = (double)bias[i] * inv_kT;
+            a += bb;
+            table[n + i] = exp(bb - mb);
+        }
+        table[i] = exp(a - ma);                                  // NaN where every item is -inf: the resample is replayed
+    }
+}
+
+// sum over the workgroup in a fixed order, on every thread
+__device__ inline double block_sum(double v, double* sh) {
+    v = wave_sum(v);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) sh[wave] = v;
+    __syncthreads();
+    const double total = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    __syncthreads();
+    return total;
+}
+
+// visit(j, E_j) for every draw of the Bayesian stream: thread q % 256 takes group q, that is draws 2q and 2q + 1
+template <typename Visit>
+__device__ inline void for_each_exponential(const BootstrapStream& stream, int64_t S, Visit visit) {
+    for (int64_t q = threadIdx.x; 2 * q < S; q += blockDim.x) {
+        uint32_t w[4];
+        bootstrap_words(stream, q, w);
+        visit(2 * q, bootstrap_exponential(w[0], w[1]));
+        if (2 * q + 1 < S) visit(2 * q + 1, bootstrap_exponential(w[2], w[3]));
+    }
+}
+
+// One workgroup per resample r = offset + blockIdx.x.
+//   standard:  dF_r = -kT (M + log sum_j t[i_j] - log S)          or, with a bias,
+//              dF_r = -kT ((M + log sum_j t[i_j]) - (M_b + log sum_j u[i_j]))
+//   Bayesian:  dF_r = -kT (M + log sum_j E_j t[j] - log sum_j E_j)           (S == high == n_data, no bias)
+// A sum below 2^-1000 (or NaN), or a set flag, sends the whole workgroup to the replay: the same draws through
+// replay_online on the data themselves.  Above 2^-1000 a term that left the normal range is off by at most 2^-1075, all S
+// < 2^31 of them by 2^-1044 together: 2^-44 of the sum.
+template <typename T>
+__global__ void __launch_bounds__(256) bootstrap_fep_resampled_kernel(
+        const T* __restrict__ work, const T* __restrict__ bias, const double* __restrict__ table,
+        const double* __restrict__ stats, const int* __restrict__ flag, int64_t n_data, int64_t S, uint32_t high,
+        int64_t seed, int64_t offset, int bayesian, double inv_kT, double kT, double* __restrict__ out) {
+    __shared__ MaxSum sh[4];
+    __shared__ double sh_sum[4];
+    const int64_t r = offset + blockIdx.x;
+    const BootstrapStream stream = bootstrap_stream(seed, r, bayesian ? BOOTSTRAP_STREAM_WEIGHTS : BOOTSTRAP_STREAM_INDICES);
+    const double* __restrict__ u = table + n_data;
+    double sa = 0.0, sb = 0.0;                                    // sum of t (times E); sum of u, or of E
+    if (bayesian) {
+        for_each_exponential(stream, S, [&](int64_t j, double e) {
+            sa += e * table[j];
+            sb += e;
+        });
+    } else {
+        for (int64_t q = threadIdx.x; 4 * q < S; q += blockDim.x) {
+            uint32_t w[4];
+            bootstrap_words(stream, q, w);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (4 * q + k < S) {
+                    const int64_t i = bootstrap_index(w[k], high);
+                    sa += table[i];
+                    if (bias) sb += u[i];
+                }
+            }
+        }
+    }
+    sa = block_sum(sa, sh_sum);
+    if (bias || bayesian) sb = block_sum(sb, sh_sum);
+    constexpr double TINY = 0x1p-1000;
+    const bool replay = *flag != 0 || !(sa >= TINY) || (bias && !(sb >= TINY));      // the same on every thread
+    double lse;
+    if (!replay) {
+        lse = stats[0] + log(sa);
+        if (bias) lse -= stats[1] + log(sb);
+    } else {
+        MaxSum a = {-INFINITY, 0.0}, b = {-INFINITY, 0.0};
+        if (bayesian)
+            replay_online(work, bias, n_data, S, inv_kT, [&](int64_t j, int64_t& i, double& lw) {
+                i = j;
+                lw = log(bootstrap_exponential_at(stream, j));
+                return true;
+            }, a, b);
+        else
+            replay_online(work, bias, n_data, S, inv_kT, [&](int64_t j, int64_t& i, double&) {
+                i = bootstrap_index_at(stream, j, high);
+                return false;
+            }, a, b);
+        a = ms_block_reduce(a, sh);
+        lse = a.m + log(a.s);
+        if (bias) {
+            b = ms_block_reduce(b, sh);
+            lse -= b.m + log(b.s);
+        }
+    }
+    if (threadIdx.x == 0) {
+        if (!bias) lse -= log(bayesian ? sb : (double)S);
+        out[blockIdx.x] = -kT * lse;
+    }
+}
+
+// The resamples themselves, for the explicit kernel and for users: one workgroup per row.
+__global__ void __launch_bounds__(256) bootstrap_resample_indices_kernel(int64_t S, uint32_t high, int64_t seed,
+                                                                        int64_t offset, int64_t* __restrict__ out) {
+    const BootstrapStream stream = bootstrap_stream(seed, offset + blockIdx.x, BOOTSTRAP_STREAM_INDICES);
+    int64_t* __restrict__ row = out + (int64_t)blockIdx.x * S;
+    for (int64_t q = threadIdx.x; 4 * q < S; q += blockDim.x) {
+        uint32_t w[4];
+        bootstrap_words(stream, q, w);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (4 * q + k < S) row[4 * q + k] = bootstrap_index(w[k], high);
+    }
+}
+
+__global__ void __launch_bounds__(256) bootstrap_resample_weights_kernel(int64_t S, int64_t seed, int64_t offset,
+                                                                        double* __restrict__ out) {
+    __shared__ double sh_sum[4];
+    const BootstrapStream stream = bootstrap_stream(seed, offset + blockIdx.x, BOOTSTRAP_STREAM_WEIGHTS);
+    double* __restrict__ row = out + (int64_t)blockIdx.x * S;
+    double total = 0.0;
+    for_each_exponential(stream, S, [&](int64_t, double e) { total += e; });
+    total = block_sum(total, sh_sum);
+    for_each_exponential(stream, S, [&](int64_t j, double e) { row[j] = e / total; });
+}
+
+inline int table_blocks(int64_t n) {
+    const int64_t blocks = (n + 255) / 256;
+    return blocks > TABLE_MAX_BLOCKS ? TABLE_MAX_BLOCKS : (int)blocks;
+}
+
+template <typename T>
+int bootstrap_fep_launch(const T* work, const T* bias, const int64_t* indices, const T* weights, int64_t n_data,
+                         int64_t n_resamples, int64_t sample_size, T kT, double* out, void* stream) {
+    TFEP_REQUIRE(n_resamples >= 0 && sample_size >= 0 && n_data >= 0, "bootstrap_fep: negative size");
+    if (n_resamples == 0) return TFEP_OK;
+    TFEP_REQUIRE(work && out, "bootstrap_fep: NULL pointer");
+    TFEP_REQUIRE(kT > (T)0, "bootstrap_fep: kT must be positive");
+    TFEP_REQUIRE(indices || sample_size <= n_data, "bootstrap_fep: without indices sample_size must be <= n_data");
+    TFEP_REQUIRE(!(bias && weights), "bootstrap_fep: Bayesian weights are not supported with biased data");
+    TFEP_REQUIRE(n_resamples <= 0x7fffffffLL, "bootstrap_fep: too many resamples");
+    bootstrap_fep_kernel<T><<<(unsigned)n_resamples, 256, 0, (hipStream_t)stream>>>(
+        work, bias, indices, weights, n_data, sample_size, 1.0 / (double)kT, (double)kT, out);
+    return check_launch("bootstrap_fep_kernel");
+}
+
+template <typename T>
+int bootstrap_table_launch(const T* work, const T* bias, int64_t n, T kT, double* table, double* stats, int* flag,
+                           double* workspace, void* stream) {
+    TFEP_REQUIRE(n >= 1, "bootstrap_table: needs at least one item");
+    TFEP_REQUIRE(work && table && stats && flag && workspace, "bootstrap_table: NULL pointer");
+    TFEP_REQUIRE(kT > (T)0, "bootstrap_table: kT must be positive");
+    const int blocks = table_blocks(n);
+    hipStream_t s = (hipStream_t)stream;
+    bootstrap_table_max_kernel<T><<<blocks, 256, 0, s>>>(work, bias, n, 1.0 / (double)kT, workspace);
+    bootstrap_table_fill_kernel<T><<<blocks, 256, 0, s>>>(work, bias, n, 1.0 / (double)kT, workspace, blocks, table, stats,
+                                                          flag);
+    return check_launch("bootstrap_table");
+}
+
+// the checks that the stream definition needs, shared by the three entry points that draw from it
+inline int bootstrap_stream_check(int64_t n_resamples, int64_t sample_size, int64_t seed, int64_t offset) {
+    TFEP_REQUIRE(n_resamples >= 0 && sample_size >= 1, "bootstrap stream: n_resamples >= 0 and sample_size >= 1");
+    TFEP_REQUIRE(seed >= 0, "bootstrap stream: the seed must be in [0, 2^63)");
+    TFEP_REQUIRE(offset >= 0 && offset <= 0x80000000LL && n_resamples <= 0x80000000LL - offset,
+                 "bootstrap stream: offset + n_resamples must be <= 2^31");
+    TFEP_REQUIRE(n_resamples <= 0x7fffffffLL, "bootstrap stream: too many resamples in one launch");
+    return TFEP_OK;
+}
+
+template <typename T>
+int bootstrap_fep_resampled_launch(const T* work, const T* bias, const double* table, const double* stats, const int* flag,
+                                   int64_t n_data, int64_t n_resamples, int64_t sample_size, int64_t high, int64_t seed,
+                                   int64_t offset, int bayesian, T kT, double* out, void* stream) {
+    if (int rc = bootstrap_stream_check(n_resamples, sample_size, seed, offset)) return rc;
+    TFEP_REQUIRE(high >= 1 && high <= 0x7fffffffLL, "bootstrap_fep_resampled: high must be in [1, 2^31)");
+    TFEP_REQUIRE(high <= n_data, "bootstrap_fep_resampled: high must be <= n_data");
+    TFEP_REQUIRE(!bayesian || (sample_size == high && !bias),
+                 "bootstrap_fep_resampled: the Bayesian mode needs sample_size == high and no bias");
+    TFEP_REQUIRE(kT > (T)0, "bootstrap_fep_resampled: kT must be positive");
+    if (n_resamples == 0) return TFEP_OK;
+    TFEP_REQUIRE(work && table && stats && flag && out, "bootstrap_fep_resampled: NULL pointer");
+    bootstrap_fep_resampled_kernel<T><<<(unsigned)n_resamples, 256, 0, (hipStream_t)stream>>>(
+        work, bias, table, stats, flag, n_data, sample_size, (uint32_t)high, seed, offset, bayesian, 1.0 / (double)kT,
+        (double)kT, out);
+    return check_launch("bootstrap_fep_resampled_kernel");
 }
 
 }  // namespace tfep
@@ -322,16 +610,58 @@ int tfep_tfep_reduce_f64(const double* target_potentials, const double* log_det_
 
 int tfep_bootstrap_fep(const float* work, const float* bias, const int64_t* indices, const float* weights,
                        int64_t n_data, int64_t n_resamples, int64_t sample_size, float kT, double* out, void* stream) {
-    TFEP_REQUIRE(n_resamples >= 0 && sample_size >= 0 && n_data >= 0, "bootstrap_fep: negative size");
+    return bootstrap_fep_launch<float>(work, bias, indices, weights, n_data, n_resamples, sample_size, kT, out, stream);
+}
+
+int tfep_bootstrap_fep_f64(const double* work, const double* bias, const int64_t* indices, const double* weights,
+                           int64_t n_data, int64_t n_resamples, int64_t sample_size, double kT, double* out, void* stream) {
+    return bootstrap_fep_launch<double>(work, bias, indices, weights, n_data, n_resamples, sample_size, kT, out, stream);
+}
+
+int64_t tfep_bootstrap_table_workspace_doubles(int64_t n) { return 3 * (int64_t)table_blocks(n < 1 ? 1 : n); }
+
+int tfep_bootstrap_table(const float* work, const float* bias, int64_t n, float kT, double* table, double* stats, int* flag,
+                         double* workspace, void* stream) {
+    return bootstrap_table_launch<float>(work, bias, n, kT, table, stats, flag, workspace, stream);
+}
+
+int tfep_bootstrap_table_f64(const double* work, const double* bias, int64_t n, double kT, double* table, double* stats,
+                             int* flag, double* workspace, void* stream) {
+    return bootstrap_table_launch<double>(work, bias, n, kT, table, stats, flag, workspace, stream);
+}
+
+int tfep_bootstrap_fep_resampled(const float* work, const float* bias, const double* table, const double* stats,
+                                 const int* flag, int64_t n_data, int64_t n_resamples, int64_t sample_size, int64_t high,
+                                 int64_t seed, int64_t offset, int bayesian, float kT, double* out, void* stream) {
+    return bootstrap_fep_resampled_launch<float>(work, bias, table, stats, flag, n_data, n_resamples, sample_size, high, seed,
+                                                 offset, bayesian, kT, out, stream);
+}
+
+int tfep_bootstrap_fep_resampled_f64(const double* work, const double* bias, const double* table, const double* stats,
+                                     const int* flag, int64_t n_data, int64_t n_resamples, int64_t sample_size, int64_t high,
+                                     int64_t seed, int64_t offset, int bayesian, double kT, double* out, void* stream) {
+    return bootstrap_fep_resampled_launch<double>(work, bias, table, stats, flag, n_data, n_resamples, sample_size, high, seed,
+                                                  offset, bayesian, kT, out, stream);
+}
+
+int tfep_bootstrap_resample_indices(int64_t n_resamples, int64_t sample_size, int64_t high, int64_t seed, int64_t offset,
+                                    int64_t* out, void* stream) {
+    if (int rc = bootstrap_stream_check(n_resamples, sample_size, seed, offset)) return rc;
+    TFEP_REQUIRE(high >= 1 && high <= 0x7fffffffLL, "bootstrap_resample_indices: high must be in [1, 2^31)");
     if (n_resamples == 0) return TFEP_OK;
-    TFEP_REQUIRE(work && out, "bootstrap_fep: NULL pointer");
-    TFEP_REQUIRE(kT > 0.f, "bootstrap_fep: kT must be positive");
-    TFEP_REQUIRE(indices || sample_size <= n_data, "bootstrap_fep: without indices sample_size must be <= n_data");
-    TFEP_REQUIRE(!(bias && weights), "bootstrap_fep: Bayesian weights are not supported with biased data");
-    TFEP_REQUIRE(n_resamples <= 0x7fffffffLL, "bootstrap_fep: too many resamples");
-    bootstrap_fep_kernel<<<(unsigned)n_resamples, 256, 0, (hipStream_t)stream>>>(work, bias, indices, weights, n_data, sample_size,
-                                                                              1.0 / (double)kT, (double)kT, out);
-    return check_launch("bootstrap_fep_kernel");
+    TFEP_REQUIRE(out, "bootstrap_resample_indices: NULL pointer");
+    bootstrap_resample_indices_kernel<<<(unsigned)n_resamples, 256, 0, (hipStream_t)stream>>>(sample_size, (uint32_t)high, seed,
+                                                                                           offset, out);
+    return check_launch("bootstrap_resample_indices_kernel");
+}
+
+int tfep_bootstrap_resample_weights(int64_t n_resamples, int64_t sample_size, int64_t seed, int64_t offset, double* out,
+                                    void* stream) {
+    if (int rc = bootstrap_stream_check(n_resamples, sample_size, seed, offset)) return rc;
+    if (n_resamples == 0) return TFEP_OK;
+    TFEP_REQUIRE(out, "bootstrap_resample_weights: NULL pointer");
+    bootstrap_resample_weights_kernel<<<(unsigned)n_resamples, 256, 0, (hipStream_t)stream>>>(sample_size, seed, offset, out);
+    return check_launch("bootstrap_resample_weights_kernel");
 }
 
 }  // extern "C"
