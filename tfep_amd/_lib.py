@@ -445,14 +445,18 @@ def check_device_tensor(t, name, dtype=torch.float32):
     return t
 
 
-def rows(t, name, dtype=torch.float32):
-    """A 2-D float32 (or ``dtype``) HIP tensor with unit column stride (copied if needed); returns (tensor, row stride)."""
+def rows(t, name, dtype=torch.float32, copy=True):
+    """A 2-D float32 (or ``dtype``) HIP tensor with unit column stride (copied if needed); returns (tensor, row stride).
+    ``copy`` False (a tensor the kernel writes): one that would need the copy is a ValueError."""
     check_device_tensor(t, name, dtype)
     if t.dim() != 2:
         raise ValueError(f'{name} must be 2-D (batch, features), got shape {tuple(t.shape)}')
     B, D = t.shape
     ok = (D <= 1 or t.stride(1) == 1) and (B <= 1 or t.stride(0) >= max(D, 1))
     if not ok:
+        if not copy:
+            raise ValueError(f'{name} is written in place: it needs unit column stride and a row stride of at least its '
+                             f'width, got strides {tuple(t.stride())} for shape {tuple(t.shape)}')
         t = t.contiguous()
     ld = t.stride(0) if (B > 1 and D > 0) else max(D, 1)
     return t, ld

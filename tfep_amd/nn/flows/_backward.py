@@ -17,7 +17,6 @@ The reference differentiates the flow with eager autograd plus ``MaskedLinearFun
 PyTorch's role is the autograd graph between layers, the loss and the optimiser.
 """
 import ctypes
-
 import os
 
 import torch
@@ -64,23 +63,20 @@ def _embedding_params(layer):
 
 def _transformer_supported(tr):
     if type(tr) in (AffineTransformer, MoebiusTransformer, VolumePreservingShiftTransformer, SOSPolynomialTransformer,
-                    SymmetrizedMoebiusTransformer, QuaternionProductTransformer):
-        return True
-    if type(tr) is NeuralSplineTransformer:
+                    SymmetrizedMoebiusTransformer, QuaternionProductTransformer, NeuralSplineTransformer):
         return True
     if type(tr) is MixedTransformer:
         return all(_transformer_supported(t) for t in tr._transformers)
     return False
 
 
-def _voidp(t, offset_elems=0):
-    return ctypes.c_void_p(t.data_ptr() + t.element_size() * offset_elems)
-
-
-def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, layout=None, order=None):
-    """VJP of ``tr.forward(x, theta[:, th_off:th_off + n_par])``: writes the matching block of ``gtheta`` and
-    ``gx`` (contiguous (B, D)).  ``theta`` / ``gtheta`` have row stride ``ld_theta``.  The SOS transformer ignores ``gl``:
-    its log-det is non-differentiable in the reference (sos.py:222), so no gradient flows through it."""
+def transformer_vjp(tr, x, theta, th_off, gy, gl, gtheta, gx, layout=None, order=None):
+    """VJP of ``tr.forward(x, theta[:, th_off:th_off + n_par])``: writes the matching block of ``gtheta`` and ``gx``
+    (contiguous (B, D)), float32 or float64 (every tensor alike, else TypeError), on the current stream of ``x``.  The SOS
+    transformer ignores ``gl``: its log-det is non-differentiable in the reference (sos.py:222), so no gradient flows
+    through it.  ``layout``: (row stride, stride between parameters, stride between features) of ``theta`` and ``gtheta``,
+    then the whole buffers (``th_off`` 0); default = reference layout.  ``order``: the features are given in this
+    permutation (slot order), so the per-feature constants follow it (float32)."""
     B, D = x.shape
     dev = x.device
     if type(tr) is MixedTransformer:
@@ -91,62 +87,49 @@ def transformer_vjp(tr, x, theta, th_off, ld_theta, gy, gl, gtheta, gx, stream, 
         for sub, ind, a in zip(tr._transformers, tr._i32[key], splits):
             xs, gys = ops.gather_columns(x, ind), ops.gather_columns(gy, ind)
             gxs = torch.empty_like(xs)
-            transformer_vjp(sub, xs, theta, th_off + a, ld_theta, gys, gl, gtheta, gxs, stream)
+            transformer_vjp(sub, xs, theta, th_off + a, gys, gl, gtheta, gxs)
             ops.scatter_columns(gxs, ind, gx)
         return
-    th, gth = _voidp(theta, th_off), _voidp(gtheta, th_off)
-    # layout: (row stride, stride between parameters, stride between features); default = reference layout.
-    # `order`: the features are given in this permutation (slot order), so per-feature constants follow it.
-    lay = _lib.ParamLayout(*layout) if layout is not None else _lib.ParamLayout(ld_theta, D, 1)
-    if x.dtype == torch.float64:
-        # float64 layers: the float64 VJP kernels (reference layout; every tensor float64, else TypeError)
-        for t, n in ((x, 'x'), (theta, 'theta'), (gy, 'grad_y'), (gl, 'grad_log_det_J'), (gtheta, 'grad_theta'), (gx, 'gx')):
-            _lib.check_device_tensor(t, n, torch.float64)
-        if type(tr) is NeuralSplineTransformer:
-            cfg = tr.config(dev, torch.float64)
-            _lib.call('tfep_spline_backward_f64', _lib.ptr(x), D, th, lay, ctypes.byref(cfg.desc), _lib.ptr(gy), D,
-                      _lib.ptr(gl), gth, lay, _lib.ptr(gx), D, B, D, stream)
-        elif type(tr) is AffineTransformer:
-            _lib.call('tfep_affine_backward_f64', _lib.ptr(x), D, th, lay, _lib.ptr(gy), D, _lib.ptr(gl), gth, lay,
-                      _lib.ptr(gx), D, B, D, stream)
-        elif type(tr) is SOSPolynomialTransformer:
-            _lib.call('tfep_sos_backward_f64', _lib.ptr(x), D, th, lay, int(tr.n_polynomials), _lib.ptr(gy), D, gth, lay,
-                      _lib.ptr(gx), D, B, D, stream)
-        elif type(tr) is SymmetrizedMoebiusTransformer:
-            _lib.call('tfep_symmetrized_moebius_backward_f64', _lib.ptr(x), D, th, ld_theta, int(tr.dimension),
-                      float(tr.max_radius), 0, _lib.ptr(gy), D, _lib.ptr(gl), gth, ld_theta, _lib.ptr(gx), D, B, D, stream)
-        elif type(tr) is QuaternionProductTransformer:      # (log-det 0: gl takes no part)
-            _lib.call('tfep_quaternion_product_backward_f64', _lib.ptr(x), D, th, ld_theta, 0, _lib.ptr(gy), D, gth, ld_theta,
-                      _lib.ptr(gx), D, B, D, stream)
-        elif type(tr) is VolumePreservingShiftTransformer:
-            gtheta[:, th_off:th_off + D].copy_(gy)     # y = x + b: the cotangent passes to b and to x unchanged
+    assert layout is None or th_off == 0
+    f64 = x.dtype == torch.float64
+
+    def block(P):
+        """The transformer's parameters (P per feature) and the outputs ``(gx, their gradient)``."""
+        if layout is not None:
+            return theta, (gx, gtheta)
+        cols = slice(th_off, th_off + P * D)
+        return theta[:, cols], (gx, gtheta[:, cols])
+
+    if type(tr) is NeuralSplineTransformer:
+        cfg = tr.config(dev, torch.float64) if f64 else _slot_config(tr, dev, order)
+        th, out = block(cfg.n_parameters_per_feature)
+        ops.spline_backward(x, th, cfg, gy, gl, layout=layout, out=out)
+    elif type(tr) is AffineTransformer:
+        th, out = block(2)
+        ops.affine_backward(x, th, gy, gl, layout=layout, out=out)
+    elif type(tr) is SOSPolynomialTransformer:
+        th, out = block(2 * tr.n_polynomials + 1)
+        ops.sos_backward(x, th, tr.n_polynomials, gy, layout=layout, out=out)
+    elif type(tr) is MoebiusTransformer:
+        if f64:
+            raise TypeError(f'{type(tr).__name__}: float64 is not supported for this transformer yet (float32 only)')
+        th, out = block(1)
+        ops.moebius_backward(x, th, tr.dimension, tr.max_radius, tr.unit_sphere, gy, gl, out=out)
+    elif type(tr) is SymmetrizedMoebiusTransformer:
+        th, out = block(1)
+        ops.symmetrized_moebius_backward(x, th, tr.dimension, tr.max_radius, False, gy, gl, out=out)
+    elif type(tr) is QuaternionProductTransformer:          # (log-det 0: gl takes no part)
+        th, out = block(1)
+        ops.quaternion_product_backward(x, th, False, gy, out=out)
+    else:   # volume-preserving shift: y = x + b (wrap is piecewise identity), log-det = 0: the cotangent passes to b and to x
+        gth = gtheta[:, th_off:th_off + D]
+        if f64:                                              # (there is no tfep_copy_2d_f64)
+            gth.copy_(gy)
             gx.copy_(gy)
         else:
-            raise TypeError(f'{type(tr).__name__}: float64 is not supported for this transformer yet (float32 only)')
-        return
-    if type(tr) is NeuralSplineTransformer:
-        cfg = _slot_config(tr, dev, order)
-        _lib.call('tfep_spline_backward', _lib.ptr(x), D, th, lay, ctypes.byref(cfg.desc), _lib.ptr(gy), D,
-                  _lib.ptr(gl), gth, lay, _lib.ptr(gx), D, B, D, stream)
-    elif type(tr) is AffineTransformer:
-        _lib.call('tfep_affine_backward', _lib.ptr(x), D, th, lay, _lib.ptr(gy), D, _lib.ptr(gl), gth, lay,
-                  _lib.ptr(gx), D, B, D, stream)
-    elif type(tr) is SOSPolynomialTransformer:
-        _lib.call('tfep_sos_backward', _lib.ptr(x), D, th, lay, int(tr.n_polynomials), _lib.ptr(gy), D, gth, lay,
-                  _lib.ptr(gx), D, B, D, stream)
-    elif type(tr) is MoebiusTransformer:
-        _lib.call('tfep_moebius_backward', _lib.ptr(x), D, th, ld_theta, int(tr.dimension), float(tr.max_radius),
-                  int(bool(tr.unit_sphere)), 1, _lib.ptr(gy), D, _lib.ptr(gl), gth, ld_theta, _lib.ptr(gx), D, B, D,
-                  stream)
-    elif type(tr) is SymmetrizedMoebiusTransformer:
-        _lib.call('tfep_symmetrized_moebius_backward', _lib.ptr(x), D, th, ld_theta, int(tr.dimension), float(tr.max_radius),
-                  0, _lib.ptr(gy), D, _lib.ptr(gl), gth, ld_theta, _lib.ptr(gx), D, B, D, stream)
-    elif type(tr) is QuaternionProductTransformer:          # (log-det 0: gl takes no part)
-        _lib.call('tfep_quaternion_product_backward', _lib.ptr(x), D, th, ld_theta, 0, _lib.ptr(gy), D, gth, ld_theta,
-                  _lib.ptr(gx), D, B, D, stream)
-    else:   # volume-preserving shift: y = x + b (wrap is piecewise identity), log-det = 0
-        _lib.call('tfep_copy_2d', _lib.ptr(gy), D, gth, ld_theta, B, D, stream)
-        _lib.call('tfep_copy_2d', _lib.ptr(gy), D, _lib.ptr(gx), D, B, D, stream)
+            stream = _lib.stream_of(x)
+            _lib.call('tfep_copy_2d', _lib.ptr(gy), D, _lib.ptr(gth), gth.stride(0), B, D, stream)
+            _lib.call('tfep_copy_2d', _lib.ptr(gy), D, _lib.ptr(gx), D, B, D, stream)
 
 
 def _slot_config(tr, dev, order):
@@ -156,29 +139,9 @@ def _slot_config(tr, dev, order):
         return cfg
     key = ('slot_cfg', str(dev))
     if tr.__dict__.get('_slot_cfg_key') != (key, id(order)):
-        h = tr.host()
-        o = order.long()
-        tr.__dict__['_slot_cfg'] = ops.SplineConfig(cfg.x0[o], cfg.xf[o], cfg.y0[o], cfg.yf[o], h['n_bins'],
-                                                    h['circular'], h['identity'], h['learn_lower'],
-                                                    h['learn_upper'], h['min_bin'], h['min_slope'])
+        tr.__dict__['_slot_cfg'] = cfg.take(order.long())
         tr.__dict__['_slot_cfg_key'] = (key, id(order))
     return tr.__dict__['_slot_cfg']
-
-
-def transformer_forward(tr, x, theta, layout, order, stream):
-    """``(y, log_det_J)`` of an affine / spline transformer on parameters stored as ``layout`` says, features of ``x``
-    in the permutation ``order`` (the counterpart of ``transformer_vjp`` for the activation-saving forward)."""
-    B, D = x.shape
-    y = torch.empty(B, D, dtype=torch.float32, device=x.device)
-    ldj = torch.empty(B, dtype=torch.float32, device=x.device)
-    lay = _lib.ParamLayout(*layout)
-    if type(tr) is NeuralSplineTransformer:
-        cfg = _slot_config(tr, x.device, order)
-        _lib.call('tfep_spline_forward', _lib.ptr(x), D, _lib.ptr(theta), lay, ctypes.byref(cfg.desc), _lib.ptr(y), D,
-                  _lib.ptr(ldj), 0, B, D, stream)
-    else:
-        _lib.call('tfep_affine_forward', _lib.ptr(x), D, _lib.ptr(theta), lay, _lib.ptr(y), D, _lib.ptr(ldj), 0, B, D, stream)
-    return y, ldj
 
 
 def trainable_tensors(layer):
@@ -247,13 +210,13 @@ class TransformerFunction(torch.autograd.Function):
     def backward(ctx, gy, gldj):
         x, theta = ctx.saved_tensors
         B, D = x.shape
-        f32 = dict(dtype=torch.float64 if x.dtype == torch.float64 else torch.float32, device=x.device)   # (or float64)
-        gy = ops.zeros(B, D, **f32) if gy is None else gy.contiguous()
-        gl = ops.zeros(B, **f32) if gldj is None else gldj.contiguous()
-        gtheta = ops.zeros(*theta.shape, **f32)
-        gx = torch.empty(B, D, **f32)
+        like = dict(dtype=ops._dtype(x), device=x.device)
+        gy = ops.zeros(B, D, **like) if gy is None else gy.contiguous()
+        gl = ops.zeros(B, **like) if gldj is None else gldj.contiguous()
+        gtheta = ops.zeros(*theta.shape, **like)
+        gx = torch.empty(B, D, **like)
         with torch.no_grad():
-            transformer_vjp(ctx.tr, x, theta, 0, theta.shape[1], gy, gl, gtheta, gx, _lib.stream_of(x))
+            transformer_vjp(ctx.tr, x, theta, 0, gy, gl, gtheta, gx)
         return None, gx, gtheta
 
 
@@ -328,20 +291,19 @@ class TransformerInverseFunction(torch.autograd.Function):
     def backward(ctx, gx, gldj):
         x, theta = ctx.saved_tensors
         B, D = x.shape
-        f32 = dict(dtype=torch.float64 if x.dtype == torch.float64 else torch.float32, device=x.device)   # (or float64)
-        stream = _lib.stream_of(x)
-        gx = ops.zeros(B, D, **f32) if gx is None else gx.contiguous()
-        gl = ops.zeros(B, **f32) if gldj is None else gldj.contiguous()
+        like = dict(dtype=ops._dtype(x), device=x.device)
+        gx = ops.zeros(B, D, **like) if gx is None else gx.contiguous()
+        gl = ops.zeros(B, **like) if gldj is None else gldj.contiguous()
         with torch.no_grad():
-            scratch = ops.zeros(*theta.shape, **f32)
-            tau_x = torch.empty(B, D, **f32)
-            transformer_vjp(ctx.tr, x, theta, 0, theta.shape[1], torch.ones(B, D, **f32), ops.zeros(B, **f32), scratch, tau_x, stream)
-            lx = torch.empty(B, D, **f32)
-            transformer_vjp(ctx.tr, x, theta, 0, theta.shape[1], ops.zeros(B, D, **f32), gl, scratch, lx, stream)
+            scratch = ops.zeros(*theta.shape, **like)
+            tau_x = torch.empty(B, D, **like)
+            transformer_vjp(ctx.tr, x, theta, 0, torch.ones(B, D, **like), ops.zeros(B, **like), scratch, tau_x)
+            lx = torch.empty(B, D, **like)
+            transformer_vjp(ctx.tr, x, theta, 0, ops.zeros(B, D, **like), gl, scratch, lx)
             u = ((gx - lx) / tau_x).contiguous()
-            gtheta = ops.zeros(*theta.shape, **f32)
-            dump = torch.empty(B, D, **f32)
-            transformer_vjp(ctx.tr, x, theta, 0, theta.shape[1], u, gl, gtheta, dump, stream)
+            gtheta = ops.zeros(*theta.shape, **like)
+            dump = torch.empty(B, D, **like)
+            transformer_vjp(ctx.tr, x, theta, 0, u, gl, gtheta, dump)
         return None, u, -gtheta
 
 
@@ -733,7 +695,9 @@ def forward_saving(layer, x):
     h, theta = _conditioner_forward(layer, wts, cin, B)
     x_tr = ops.gather_columns(x, tables['tr']) if layer.has_fixed_indices else x
     xs = ops.gather_columns(x_tr, bplan['order'])
-    ys, ldj = transformer_forward(layer._transformer, xs, theta, (n_out_pad, 1, P), bplan['order'], _lib.stream_of(x))
+    tr, lay = layer._transformer, (n_out_pad, 1, P)          # (affine or spline: ``saves_activations_at``)
+    ys, ldj = (ops.spline(xs, theta, _slot_config(tr, dev, bplan['order']), layout=lay) if type(tr) is NeuralSplineTransformer
+               else ops.affine(xs, theta, layout=lay))
     if layer.has_fixed_indices:
         y_tr = torch.empty(B, n_tr, dtype=torch.float32, device=dev)
         ops.scatter_columns(ys, bplan['order'], y_tr)
@@ -826,11 +790,10 @@ def layer_backward(layer, x, gy, gldj, saved=None, need_gx=True):
             # theta / gtheta are feature-major in slot order: work on slot-ordered copies of x and gy
             xs, gys = ops.gather_columns(x_tr, bplan['order']), ops.gather_columns(gy_tr, bplan['order'])
             gxs = torch.empty(Bc, n_tr, **f32)
-            transformer_vjp(tr, xs, theta, 0, n_out_pad, gys, glc, gtheta, gxs, stream, layout=(n_out_pad, 1, P),
-                            order=bplan['order'])
+            transformer_vjp(tr, xs, theta, 0, gys, glc, gtheta, gxs, layout=(n_out_pad, 1, P), order=bplan['order'])
             ops.scatter_columns(gxs, bplan['order'], gx_dir)
         else:
-            transformer_vjp(tr, x_tr, theta, 0, n_out_pad, gy_tr, glc, gtheta, gx_dir, stream)
+            transformer_vjp(tr, x_tr, theta, 0, gy_tr, glc, gtheta, gx_dir)
         del theta
 
         # ---- masked linears, last to first.  g = gradient w.r.t. the layer's pre-activation output.

@@ -684,10 +684,7 @@ class AutoregressiveFlow(torch.nn.Module):
         """The transformer (``tr``: a member of a mixed transformer) restricted to its features ``sel`` (a degree group)."""
         tr = self._transformer if tr is None else tr
         if type(tr) is NeuralSplineTransformer:
-            cfg, h = tr.config(device), tr.host()
-            return ('spline', ops.SplineConfig(
-                cfg.x0[sel], cfg.xf[sel], cfg.y0[sel], cfg.yf[sel], h['n_bins'], h['circular'], h['identity'],
-                h['learn_lower'], h['learn_upper'], h['min_bin'], h['min_slope']))
+            return ('spline', tr.config(device).take(sel))
         if type(tr) is MoebiusTransformer:
             return ('moebius', tr)
         if type(tr) is SymmetrizedMoebiusTransformer:

@@ -3,7 +3,8 @@
 Every function takes float32 HIP tensors or, where the entry point has a ``_f64`` twin, float64 ones (the dtype of its first
 tensor picks the kernels, ``_dtype`` / ``_sfx``; mixed dtypes are a TypeError), launches on the current HIP stream of the
 tensor's device and returns fresh output tensors (inputs are never modified, like the reference:
-flows/autoregressive.py:165-166).  No autograd, no CPU path.
+flows/autoregressive.py:165-166), unless the caller hands outputs in (``out=`` of the transformer VJPs).  No autograd, no
+CPU path.
 """
 import ctypes
 import os
@@ -55,32 +56,84 @@ def _ldj_out(log_det_J, B, like, dtype=torch.float32):
     return log_det_J, 1
 
 
-def _check_params(parameters, B, n, name='parameters', dtype=torch.float32):
-    parameters, ld = rows(parameters, name, dtype)
+def _check_params(parameters, B, n, name='parameters', dtype=torch.float32, copy=True):
+    parameters, ld = rows(parameters, name, dtype, copy)
     if parameters.shape[0] != B or parameters.shape[1] != n:
         raise ValueError(f'{name} must have shape ({B}, {n}), got {tuple(parameters.shape)}')
     return parameters, ld
 
 
-def _layout(ld, D, layout=None):
-    if layout is not None:
-        return ParamLayout(*layout)
-    return ParamLayout(ld, D, 1)                          # reference layout: column p*D + f
+def _param_block(parameters, B, P, D, dtype, layout=None, name='parameters', copy=True):
+    """``(tensor, ParamLayout)`` of P parameters for each of D features: a (B, P D) tensor in the reference layout (column
+    p*D + f), which may be a column slice of a wider one (``rows``), or, with ``layout = (ld, stride_p, stride_f)``, the buffer
+    that the layout indexes: B rows of stride ``ld``, unit column stride, wide enough for the last feature's last parameter."""
+    if layout is None:
+        parameters, ld = _check_params(parameters, B, P * D, name, dtype, copy)
+        return parameters, ParamLayout(ld, D, 1)
+    ld, stride_p, stride_f = (int(v) for v in layout)
+    reach = (P - 1) * stride_p + (D - 1) * stride_f
+    width = parameters.shape[1] if check_device_tensor(parameters, name, dtype).dim() == 2 else -1
+    if (width < 0 or parameters.shape[0] != B or min(stride_p, stride_f) < 0 or not (D == 0 or reach < width <= ld)
+            or (width > 1 and parameters.stride(1) != 1) or (B > 1 and parameters.stride(0) != ld)):
+        raise ValueError(f'{name} must be the ({B}, > {reach}) buffer that layout {(ld, stride_p, stride_f)} indexes (unit '
+                         f'column stride), got shape {tuple(parameters.shape)}, strides {tuple(parameters.stride())}')
+    return parameters, ParamLayout(ld, stride_p, stride_f)
+
+
+def _vjp_args(dt, x, parameters, P, grad_y, grad_log_det_J, layout, out, alloc, ld_only=False):
+    """The arguments that the six transformer VJP entry points share, checked against the kernel family ``dt`` (TypeError)
+    and for their shapes (ValueError) before anything is launched: ``call(name, *head, <the transformer's own>, *cot, gl,
+    *tail)`` with ``head`` = x and the parameters (``_param_block``; ``ld_only``: their row stride, not a layout), ``cot`` =
+    grad_y, ``gl`` = grad_log_det_J ((B,), or None: NULL), ``tail`` = the outputs, the sizes and the stream.  ``out = (grad_x,
+    grad_parameters)`` is held to the rules of ``x`` and ``parameters`` but never copied (ValueError instead); without it
+    grad_x is uninitialised and grad_parameters comes from ``alloc`` (``zeros`` or ``torch.empty``) in the shape of
+    ``parameters``.  Also returns ``grads = (grad_x, grad_parameters)`` and ``keep``."""
+    x, ldx = rows(x, 'x', dt)
+    B, D = x.shape
+    gy, ldgy = rows(grad_y, 'grad_y', dt)
+    if gy.shape != x.shape:
+        raise ValueError(f'grad_y must have the shape of x, {tuple(x.shape)}, got {tuple(gy.shape)}')
+    if grad_log_det_J is not None and check_device_tensor(grad_log_det_J, 'grad_log_det_J', dt).shape != (B,):
+        raise ValueError(f'grad_log_det_J must have shape ({B},), got {tuple(grad_log_det_J.shape)}')
+    gl = None if grad_log_det_J is None else grad_log_det_J.contiguous()
+    p, lay = _param_block(parameters, B, P, D, dt, layout)
+    if out is None:
+        gx, ldgx = torch.empty(B, D, dtype=dt, device=x.device), max(D, 1)
+        gp = alloc(*p.shape, dtype=dt, device=x.device)
+        glay = ParamLayout(max(gp.shape[1], 1), lay.stride_p, lay.stride_f)
+    else:
+        gx, ldgx = _check_params(out[0], B, D, 'grad_x', dt, copy=False)
+        gp, glay = _param_block(out[1], B, P, D, dt, layout, 'grad_parameters', copy=False)
+    if ld_only:
+        lay, glay = lay.ld, glay.ld
+    # (``keep``: contiguous copies are held in the caller's locals until the launch is queued: a temporary freed inside the
+    # argument list hands its block back to the caching allocator, and the NEXT temporary may be written over it)
+    return ((ptr(x), ldx, ptr(p), lay), (ptr(gy), ldgy), ptr(gl), (ptr(gp), glay, ptr(gx), ldgx, B, D, stream_of(x)), (gx, gp),
+            (x, p, gy, gl))
 
 
 # ----------------------------------------------------------------------------- affine
 
-def affine(x, parameters, inverse=False, log_det_J=None):
-    """AffineTransformer.forward / .inverse (reference affine.py:51-106).  float64 tensors run on the float64 kernels."""
+def affine(x, parameters, inverse=False, log_det_J=None, layout=None):
+    """AffineTransformer.forward / .inverse (reference affine.py:51-106).  float64 tensors run on the float64 kernels.
+    ``layout``: see ``_param_block``."""
     dt = _dtype(x)
     x, ldx = rows(x, 'x', dt)
     B, D = x.shape
-    parameters, ldp = _check_params(parameters, B, 2 * D, dtype=dt)
+    parameters, lay = _param_block(parameters, B, 2, D, dt, layout)
     y = torch.empty(B, D, dtype=x.dtype, device=x.device)
     ldj, acc = _ldj_out(log_det_J, B, x, dt)
     fn = ('tfep_affine_inverse' if inverse else 'tfep_affine_forward') + _sfx(dt)
-    call(fn, ptr(x), ldx, ptr(parameters), _layout(ldp, D), ptr(y), max(D, 1), ptr(ldj), acc, B, D, stream_of(x))
+    call(fn, ptr(x), ldx, ptr(parameters), lay, ptr(y), max(D, 1), ptr(ldj), acc, B, D, stream_of(x))
     return y, ldj
+
+
+def affine_backward(x, parameters, grad_y, grad_log_det_J, *, layout=None, out=None):
+    """VJP of ``affine`` (forward) at ``x``: ``(grad_x, grad_parameters)`` (reference affine.py:321-323); ``_vjp_args``."""
+    dt = _dtype(x)
+    head, cot, gl, tail, grads, keep = _vjp_args(dt, x, parameters, 2, grad_y, grad_log_det_J, layout, out, zeros)
+    call('tfep_affine_backward' + _sfx(dt), *head, *cot, gl, *tail)
+    return grads
 
 
 def sos(x, parameters, n_polynomials, log_det_J=None):
@@ -92,12 +145,21 @@ def sos(x, parameters, n_polynomials, log_det_J=None):
     K = int(n_polynomials)
     if K < 1:
         raise ValueError(f'n_polynomials must be positive, got {K}')
-    parameters, ldp = _check_params(parameters, B, (2 * K + 1) * D, dtype=dt)
+    parameters, lay = _param_block(parameters, B, 2 * K + 1, D, dt)
     y = torch.empty(B, D, dtype=x.dtype, device=x.device)
     ldj, acc = _ldj_out(log_det_J, B, x, dt)
-    call('tfep_sos_forward' + _sfx(dt), ptr(x), ldx, ptr(parameters), _layout(ldp, D), K, ptr(y), max(D, 1), ptr(ldj), acc,
-         B, D, stream_of(x))
+    call('tfep_sos_forward' + _sfx(dt), ptr(x), ldx, ptr(parameters), lay, K, ptr(y), max(D, 1), ptr(ldj), acc, B, D,
+         stream_of(x))
     return y, ldj
+
+
+def sos_backward(x, parameters, n_polynomials, grad_y, *, layout=None, out=None):
+    """VJP of ``sos`` at ``x`` for the cotangent of y: ``(grad_x, grad_parameters)``.  The log-det has no cotangent
+    (non-differentiable, reference sos.py:222); ``_vjp_args``."""
+    dt, K = _dtype(x), int(n_polynomials)
+    head, cot, _, tail, grads, keep = _vjp_args(dt, x, parameters, 2 * K + 1, grad_y, None, layout, out, torch.empty)
+    call('tfep_sos_backward' + _sfx(dt), *head, K, *cot, *tail)
+    return grads
 
 
 def sos_fused_desc(n_polynomials):
@@ -134,39 +196,48 @@ class SplineConfig:
         self.x0, self.xf, self.y0, self.yf = (check_device_tensor(t.contiguous(), n, dtype)
                                               for t, n in ((x0, 'x0'), (xf, 'xf'), (y0, 'y0'), (yf, 'yf')))
         lib = _lib.load()
-        if dtype == torch.float64:
-            self.desc = SplineDescF64(self.x0.data_ptr(), self.xf.data_ptr(), self.y0.data_ptr(), self.yf.data_ptr(),
-                                      int(n_bins), int(bool(circular)), int(bool(identity_boundary_slopes)),
-                                      int(bool(learn_lower_bound)), int(bool(learn_upper_bound)),
-                                      float(min_bin_size), float(min_slope))
-            n = lib.tfep_spline_n_parameters_per_feature_f64(ctypes.byref(self.desc))
-            if n < 0:
-                raise ValueError(lib.tfep_last_error().decode())
-            self.n_parameters_per_feature = n
-            return
-        self.desc = SplineDesc(self.x0.data_ptr(), self.xf.data_ptr(), self.y0.data_ptr(), self.yf.data_ptr(),
-                               int(n_bins), int(bool(circular)), int(bool(identity_boundary_slopes)),
-                               int(bool(learn_lower_bound)), int(bool(learn_upper_bound)),
-                               float(min_bin_size), float(min_slope))
-        self.n_parameters_per_feature = lib.tfep_spline_n_parameters_per_feature(ctypes.byref(self.desc))
+        self.desc = (SplineDescF64 if dtype == _F64 else SplineDesc)(
+            self.x0.data_ptr(), self.xf.data_ptr(), self.y0.data_ptr(), self.yf.data_ptr(), int(n_bins), int(bool(circular)),
+            int(bool(identity_boundary_slopes)), int(bool(learn_lower_bound)), int(bool(learn_upper_bound)),
+            float(min_bin_size), float(min_slope))
+        n = getattr(lib, 'tfep_spline_n_parameters_per_feature' + _sfx(dtype))(ctypes.byref(self.desc))
+        if n < 0:       # (float64: the descriptor was refused, with a message; float32: the count of a negative n_bins)
+            raise ValueError(lib.tfep_last_error().decode() if dtype == _F64 else f'spline: n_bins={int(n_bins)} is negative')
+        self.n_parameters_per_feature = n
+
+    def take(self, index):
+        """This configuration for the features ``index`` (a device index tensor: a subset or a permutation), in that
+        order: the four domain arrays indexed, bins, flags and dtype as they are."""
+        d = self.desc
+        return SplineConfig(self.x0[index], self.xf[index], self.y0[index], self.yf[index], d.n_bins, d.circular,
+                            d.identity_boundary_slopes, d.learn_lower_bound, d.learn_upper_bound, d.min_bin_size,
+                            d.min_slope, dtype=self.dtype)
 
 
 def spline(x, parameters, cfg, inverse=False, log_det_J=None, layout=None):
     """NeuralSplineTransformer.forward / .inverse (reference spline.py:184-261).  The kernels are those of ``cfg.dtype``:
-    ``x`` and ``parameters`` must be of that dtype."""
+    ``x`` and ``parameters`` must be of that dtype.  ``layout``: see ``_param_block``."""
     dt = cfg.dtype
     x, ldx = rows(x, 'x', dt)
     B, D = x.shape
-    P = cfg.n_parameters_per_feature
     if cfg.x0.numel() != D:
         raise ValueError(f'spline domain has {cfg.x0.numel()} features, input has {D}')
-    parameters, ldp = _check_params(parameters, B, P * D, dtype=dt)
+    parameters, lay = _param_block(parameters, B, cfg.n_parameters_per_feature, D, dt, layout)
     y = torch.empty(B, D, dtype=x.dtype, device=x.device)
     ldj, acc = _ldj_out(log_det_J, B, x, dt)
     fn = ('tfep_spline_inverse' if inverse else 'tfep_spline_forward') + _sfx(dt)
-    call(fn, ptr(x), ldx, ptr(parameters), _layout(ldp, D, layout), ctypes.byref(cfg.desc),
-         ptr(y), max(D, 1), ptr(ldj), acc, B, D, stream_of(x))
+    call(fn, ptr(x), ldx, ptr(parameters), lay, ctypes.byref(cfg.desc), ptr(y), max(D, 1), ptr(ldj), acc, B, D, stream_of(x))
     return y, ldj
+
+
+def spline_backward(x, parameters, cfg, grad_y, grad_log_det_J, *, layout=None, out=None):
+    """VJP of ``spline`` (forward) at ``x``: ``(grad_x, grad_parameters)``, on the kernels of ``cfg.dtype``; ``_vjp_args``."""
+    head, cot, gl, tail, grads, keep = _vjp_args(cfg.dtype, x, parameters, cfg.n_parameters_per_feature, grad_y,
+                                                 grad_log_det_J, layout, out, zeros)
+    if cfg.x0.numel() != grads[0].shape[1]:
+        raise ValueError(f'spline domain has {cfg.x0.numel()} features, input has {grads[0].shape[1]}')
+    call('tfep_spline_backward' + _sfx(cfg.dtype), *head, ctypes.byref(cfg.desc), *cot, gl, *tail)
+    return grads
 
 
 # ----------------------------------------------------------------------------- moebius
@@ -184,6 +255,14 @@ def moebius(x, parameters, dimension, max_radius=0.99, unit_sphere=False, invers
     return y, ldj
 
 
+def moebius_backward(x, parameters, dimension, max_radius, unit_sphere, grad_y, grad_log_det_J, *, out=None):
+    """VJP of ``moebius`` (forward) at ``x``: ``(grad_x, grad_parameters)``; float32 only; ``_vjp_args``."""
+    head, cot, gl, tail, grads, keep = _vjp_args(torch.float32, x, parameters, 1, grad_y, grad_log_det_J, None, out, zeros,
+                                                 ld_only=True)
+    call('tfep_moebius_backward', *head, int(dimension), float(max_radius), int(bool(unit_sphere)), 1, *cot, gl, *tail)
+    return grads
+
+
 def symmetrized_moebius(x, parameters, dimension, max_radius=0.99, inverse=False, log_det_J=None):
     """SymmetrizedMoebiusTransformer.forward / .inverse (reference moebius.py:481-629).  float64 tensors run on the float64
     kernels; mixed float32 / float64 arguments are a TypeError."""
@@ -196,6 +275,17 @@ def symmetrized_moebius(x, parameters, dimension, max_radius=0.99, inverse=False
     call('tfep_symmetrized_moebius' + _sfx(dt), ptr(x), ldx, ptr(parameters), ldp, int(dimension), float(max_radius),
          int(bool(inverse)), ptr(y), max(D, 1), ptr(ldj), acc, B, D, stream_of(x))
     return y, ldj
+
+
+def symmetrized_moebius_backward(x, parameters, dimension, max_radius, inverse, grad_y, grad_log_det_J, *, out=None):
+    """VJP of ``symmetrized_moebius`` in the direction ``inverse`` at its input ``x``: ``(grad_x, grad_parameters)``; the
+    log-det carries gradient in both directions; ``_vjp_args``."""
+    dt = _dtype(x)
+    head, cot, gl, tail, grads, keep = _vjp_args(dt, x, parameters, 1, grad_y, grad_log_det_J, None, out, torch.empty,
+                                                 ld_only=True)
+    call('tfep_symmetrized_moebius_backward' + _sfx(dt), *head, int(dimension), float(max_radius), int(bool(inverse)), *cot,
+         gl, *tail)
+    return grads
 
 
 def quaternion_product(x, parameters, inverse=False, log_det_J=None):
@@ -214,6 +304,15 @@ def quaternion_product(x, parameters, inverse=False, log_det_J=None):
     call('tfep_quaternion_product' + _sfx(dt), ptr(x), ldx, ptr(parameters), ldp, int(bool(inverse)), ptr(y), max(D, 1),
          ptr(ldj), acc, B, D, stream_of(x))
     return y, ldj
+
+
+def quaternion_product_backward(x, parameters, inverse, grad_y, *, out=None):
+    """VJP of ``quaternion_product`` in the direction ``inverse`` at its input ``x``: ``(grad_x, grad_parameters)``.  The
+    log-det is the constant zero: its cotangent is no argument; ``_vjp_args``."""
+    dt = _dtype(x)
+    head, cot, _, tail, grads, keep = _vjp_args(dt, x, parameters, 1, grad_y, None, None, out, torch.empty, ld_only=True)
+    call('tfep_quaternion_product_backward' + _sfx(dt), *head, int(bool(inverse)), *cot, *tail)
+    return grads
 
 
 def moebius_split_out(x, parameters, max_radius, cols_padded):

@@ -1,10 +1,11 @@
 """The kernels as custom torch ops: ``torch.ops.tfep.*`` (north star: "exposed as custom torch ops").
 
-Each op is a thin dispatcher entry over one C-ABI entry point of ``include/tfep_hip.h`` (through ``tfep_amd.ops``):
-a schema, a HIP ("cuda" device type) implementation, a fake / meta implementation (shapes and dtypes only, so that
-``torch.compile``, ``make_fx`` and fake-tensor tracing see through them) and, where a VJP kernel exists, an autograd
-formula whose backward is itself a registered op.  There is no CPU implementation: calling an op with CPU tensors fails
-in the dispatcher ("no kernel for CPU") -- the same no-fallback policy as the rest of the package.
+Each op is a thin dispatcher entry over one C-ABI entry point of ``include/tfep_hip.h``, through its wrapper in
+``tfep_amd.ops`` (only ``fused_output_transformer`` launches from here, ``_fused_launch``): a schema, a HIP ("cuda" device
+type) implementation, a fake / meta implementation (shapes and dtypes only, so that ``torch.compile``, ``make_fx`` and
+fake-tensor tracing see through them) and, where a VJP kernel exists, an autograd formula whose backward is itself a
+registered op.  There is no CPU implementation: calling an op with CPU tensors fails in the dispatcher ("no kernel for
+CPU") -- the same no-fallback policy as the rest of the package.
 
   tfep::affine_forward / affine_inverse / affine_backward            reference transformers/affine.py:281-363
   tfep::sos_forward / sos_backward                                    reference transformers/sos.py:81-265 (SOS_OPS)
@@ -52,14 +53,6 @@ def _pair_like(x):
     return x.new_empty(x.shape), x.new_empty((x.shape[0],))
 
 
-def _vjp_dtype(x, *others):
-    """The dtype of a VJP launch: every tensor float32, or every tensor float64 (the float64 kernels); else TypeError."""
-    dt = ops._dtype(x)
-    for t, n in others:
-        _lib.check_device_tensor(t, n, dt)
-    return dt
-
-
 # ============================================================================= affine
 
 @custom_op('tfep::affine_forward', mutates_args=(), device_types=_DEV)
@@ -74,17 +67,7 @@ def affine_inverse(y: Tensor, parameters: Tensor) -> Tuple[Tensor, Tensor]:
 
 @custom_op('tfep::affine_backward', mutates_args=(), device_types=_DEV)
 def affine_backward(x: Tensor, parameters: Tensor, grad_y: Tensor, grad_log_det_J: Tensor) -> Tuple[Tensor, Tensor]:
-    # (contiguous copies are held in locals until the launch is queued: a temporary freed inside the argument list
-    # hands its block back to the caching allocator, and the NEXT temporary may be written over it)
-    x, parameters, gy, gl = x.contiguous(), parameters.contiguous(), grad_y.contiguous(), grad_log_det_J.contiguous()
-    dt = _vjp_dtype(x, (x, 'x'), (parameters, 'parameters'), (gy, 'grad_y'), (gl, 'grad_log_det_J'))
-    B, D = x.shape
-    gx = torch.empty_like(x)
-    gp = ops.zeros(*parameters.shape, dtype=dt, device=x.device)
-    lay = _lib.ParamLayout(parameters.shape[1], D, 1)
-    _lib.call('tfep_affine_backward' + ops._sfx(dt), _lib.ptr(x), D, _lib.ptr(parameters), lay, _lib.ptr(gy), D,
-              _lib.ptr(gl), _lib.ptr(gp), lay, _lib.ptr(gx), D, B, D, _lib.stream_of(x))
-    return gx, gp
+    return ops.affine_backward(x, parameters, grad_y, grad_log_det_J)
 
 
 affine_forward.register_fake(lambda x, parameters: _pair_like(x))
@@ -125,17 +108,7 @@ def sos_forward(x: Tensor, parameters: Tensor, n_polynomials: int) -> Tuple[Tens
 @custom_op('tfep::sos_backward', mutates_args=(), device_types=_DEV)
 def sos_backward(x: Tensor, parameters: Tensor, n_polynomials: int, grad_y: Tensor) -> Tuple[Tensor, Tensor]:
     """VJP of ``sos_forward`` for the cotangent of y; the log-det has none (non-differentiable, reference sos.py:222)."""
-    x, parameters, gy = x.contiguous(), parameters.contiguous(), grad_y.contiguous()
-    dt = _vjp_dtype(x, (x, 'x'), (parameters, 'parameters'), (gy, 'grad_y'))
-    B, D = x.shape
-    if parameters.shape != (B, (2 * n_polynomials + 1) * D) or gy.shape != x.shape:
-        raise ValueError('sos_backward: parameters must be (B, (2 K + 1) D) and grad_y of the shape of x')
-    gx = torch.empty_like(x)
-    gp = torch.empty_like(parameters)
-    lay = _lib.ParamLayout(parameters.shape[1], D, 1)
-    _lib.call('tfep_sos_backward' + ops._sfx(dt), _lib.ptr(x), D, _lib.ptr(parameters), lay, int(n_polynomials), _lib.ptr(gy),
-              D, _lib.ptr(gp), lay, _lib.ptr(gx), D, B, D, _lib.stream_of(x))
-    return gx, gp
+    return ops.sos_backward(x, parameters, n_polynomials, grad_y)
 
 
 sos_forward.register_fake(lambda x, parameters, n_polynomials: _pair_like(x))
@@ -191,16 +164,7 @@ def spline_backward(x: Tensor, parameters: Tensor, grad_y: Tensor, grad_log_det_
                     min_slope: float) -> Tuple[Tensor, Tensor]:
     cfg = _spline_cfg(x0, xf, y0, yf, n_bins, circular, identity_boundary_slopes, learn_lower_bound, learn_upper_bound,
                       min_bin_size, min_slope)
-    x, parameters, gy, gl = x.contiguous(), parameters.contiguous(), grad_y.contiguous(), grad_log_det_J.contiguous()
-    dt = cfg.dtype
-    _vjp_dtype(x0, (x, 'x'), (parameters, 'parameters'), (gy, 'grad_y'), (gl, 'grad_log_det_J'))
-    B, D = x.shape
-    gx = torch.empty_like(x)
-    gp = ops.zeros(*parameters.shape, dtype=dt, device=x.device)
-    lay = _lib.ParamLayout(parameters.shape[1], D, 1)
-    _lib.call('tfep_spline_backward' + ops._sfx(dt), _lib.ptr(x), D, _lib.ptr(parameters), lay, ctypes.byref(cfg.desc),
-              _lib.ptr(gy), D, _lib.ptr(gl), _lib.ptr(gp), lay, _lib.ptr(gx), D, B, D, _lib.stream_of(x))
-    return gx, gp
+    return ops.spline_backward(x, parameters, cfg, grad_y, grad_log_det_J)
 
 
 spline_forward.register_fake(lambda x, parameters, *cfg: _pair_like(x))
@@ -241,14 +205,7 @@ def moebius_inverse(y: Tensor, parameters: Tensor, dimension: int, max_radius: f
 @custom_op('tfep::moebius_backward', mutates_args=(), device_types=_DEV)
 def moebius_backward(x: Tensor, parameters: Tensor, grad_y: Tensor, grad_log_det_J: Tensor, dimension: int,
                      max_radius: float, unit_sphere: bool) -> Tuple[Tensor, Tensor]:
-    x, parameters, gy, gl = x.contiguous(), parameters.contiguous(), grad_y.contiguous(), grad_log_det_J.contiguous()
-    B, D = x.shape
-    gx = torch.empty_like(x)
-    gp = ops.zeros(*parameters.shape, dtype=torch.float32, device=x.device)
-    _lib.call('tfep_moebius_backward', _lib.ptr(x), D, _lib.ptr(parameters), parameters.shape[1], int(dimension),
-              float(max_radius), int(bool(unit_sphere)), 1, _lib.ptr(gy), D, _lib.ptr(gl), _lib.ptr(gp),
-              parameters.shape[1], _lib.ptr(gx), D, B, D, _lib.stream_of(x))
-    return gx, gp
+    return ops.moebius_backward(x, parameters, dimension, max_radius, unit_sphere, grad_y, grad_log_det_J)
 
 
 moebius_forward.register_fake(lambda x, parameters, *a: _pair_like(x))
@@ -289,17 +246,7 @@ def symmetrized_moebius_backward(x: Tensor, parameters: Tensor, grad_y: Tensor, 
                                  max_radius: float, inverse: bool) -> Tuple[Tensor, Tensor]:
     """VJP of ``symmetrized_moebius_forward`` (``inverse`` False) or ``_inverse`` (True) at its input ``x``; the log-det
     carries gradient in both directions."""
-    x, parameters, gy, gl = x.contiguous(), parameters.contiguous(), grad_y.contiguous(), grad_log_det_J.contiguous()
-    dt = _vjp_dtype(x, (x, 'x'), (parameters, 'parameters'), (gy, 'grad_y'), (gl, 'grad_log_det_J'))
-    B, D = x.shape
-    if parameters.shape != x.shape or gy.shape != x.shape or gl.shape != (B,):
-        raise ValueError('symmetrized_moebius_backward: parameters and grad_y must have the shape of x, grad_log_det_J (B,)')
-    gx = torch.empty_like(x)
-    gp = torch.empty_like(parameters)
-    _lib.call('tfep_symmetrized_moebius_backward' + ops._sfx(dt), _lib.ptr(x), D, _lib.ptr(parameters), D, int(dimension),
-              float(max_radius), int(bool(inverse)), _lib.ptr(gy), D, _lib.ptr(gl), _lib.ptr(gp), D, _lib.ptr(gx), D, B, D,
-              _lib.stream_of(x))
-    return gx, gp
+    return ops.symmetrized_moebius_backward(x, parameters, dimension, max_radius, inverse, grad_y, grad_log_det_J)
 
 
 symmetrized_moebius_forward.register_fake(lambda x, parameters, *a: _pair_like(x))
@@ -337,17 +284,7 @@ def quaternion_product_inverse(y: Tensor, parameters: Tensor) -> Tuple[Tensor, T
 def quaternion_product_backward(x: Tensor, parameters: Tensor, grad_y: Tensor, inverse: bool) -> Tuple[Tensor, Tensor]:
     """VJP of ``quaternion_product_forward`` (``inverse`` False) or ``_inverse`` (True) at its input ``x``.  The log-det is
     the constant zero: its cotangent is no argument."""
-    x, parameters, gy = x.contiguous(), parameters.contiguous(), grad_y.contiguous()
-    dt = _vjp_dtype(x, (x, 'x'), (parameters, 'parameters'), (gy, 'grad_y'))
-    B, D = x.shape
-    if parameters.shape != x.shape or gy.shape != x.shape:
-        raise ValueError('quaternion_product_backward: parameters and grad_y must have the shape of x')
-    gx = torch.empty_like(x)
-    gp = torch.empty_like(parameters)
-    _lib.call('tfep_quaternion_product_backward' + ops._sfx(dt), _lib.ptr(x), max(D, 1), _lib.ptr(parameters), max(D, 1),
-              int(bool(inverse)), _lib.ptr(gy), max(D, 1), _lib.ptr(gp), max(D, 1), _lib.ptr(gx), max(D, 1), B, D,
-              _lib.stream_of(x))
-    return gx, gp
+    return ops.quaternion_product_backward(x, parameters, inverse, grad_y)
 
 
 quaternion_product_forward.register_fake(lambda x, parameters: _pair_like(x))
