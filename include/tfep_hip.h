@@ -837,6 +837,34 @@ typedef struct tfep_inverse_chain_f64_desc {
 int64_t tfep_inverse_chain_f64_lds_bytes(int n_cols_total, int par_cols, int max_feats);
 int tfep_inverse_chain_f64(const tfep_inverse_chain_f64_desc* desc, void* stream);
 
+/*
+ * The same chain with vector-valued members: a symmetrized Moebius transformer or a quaternion product, alone or as
+ * members of a mixed transformer beside affine / RQ-spline members.  `chain` is read exactly as tfep_inverse_chain_f64
+ * reads its descriptor (every check of that entry point applies; kinds 0 and 1 run on the same device functions, with the
+ * same summation order), plus:
+ *   member_kind 2  symmetrized Moebius on member_dim[m]-vectors (2 .. 8), 0 < member_max_radius[m] < 1.  One parameter per
+ *                  feature (the raw vector w).  log_det_J[b] += log|det J| of the inverse map, once per vector.
+ *   member_kind 3  quaternion product: member_dim[m] = 4, scalar last, one parameter per feature (the raw quaternion p);
+ *                  x = conj(p / |p|) (x) y.  Adds exactly 0 to log_det_J.
+ * The components of a vector are features of ONE degree; they need not sit in adjacent slots.  The two last ints of a
+ * feature record link them:
+ *   feats[s][6]    0 for a feature of a scalar member, 1 + i for component i of a vector,
+ *   feats[s][7]    the slot of component i + 1 of the same vector, -1 at the last component.
+ * A vector is evaluated once, by the wave that owns the slot of its component 0: the parameters of its member_dim slots,
+ * the member_dim values of y, then x, the conditioner inputs a[0][b, pos] and the log-det (in the slot of component 0; the
+ * other slots add 0.0), so log_det_J is still summed in slot order and a row's bits do not depend on its batch.
+ * The caller guarantees what only the device tables could show: a vector member's features have P = 1 and periodic = 0,
+ * and every chain of links has exactly member_dim slots, all inside its step's [slot0, slot1)
+ * (tfep_amd/nn/flows/_blocked_f64.py:vector_links builds them so; a link that leaves the range ends the chain).  LDS and
+ * launch shape as tfep_inverse_chain_f64.
+ */
+typedef struct tfep_inverse_chain_vec_f64_desc {
+    tfep_inverse_chain_f64_desc chain;
+    int32_t member_dim[TFEP_INVERSE_F64_MAX_MEMBERS];
+    double member_max_radius[TFEP_INVERSE_F64_MAX_MEMBERS];
+} tfep_inverse_chain_vec_f64_desc;
+int tfep_inverse_chain_vec_f64(const tfep_inverse_chain_vec_f64_desc* desc, void* stream);
+
 int tfep_periodic_embedding_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
                                 const int32_t* nonperiodic_indices, int n_nonperiodic,
                                 double lower, double upper, double* out, int64_t ldo, int B, void* stream);

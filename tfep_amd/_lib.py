@@ -91,6 +91,10 @@ class InverseChainF64Desc(Structure):
                 ('spline', SplineDescF64 * 4), ('emb_lower', c_double), ('emb_scale', c_double)]
 
 
+class InverseChainVecF64Desc(Structure):
+    _fields_ = [('chain', InverseChainF64Desc), ('member_dim', c_int32 * 4), ('member_max_radius', c_double * 4)]
+
+
 class EgnnLayerParams(Structure):
     _fields_ = [('F', c_int32), ('G', c_int32)] + [(k, c_void_p) for k in (
         'dist_means', 'dist_log_gammas', 'msg0_w', 'msg0_b', 'msg2_w', 'msg2_b', 'att_w', 'att_b', 'ux0_w', 'ux0_b',
@@ -235,6 +239,7 @@ _SIGNATURES = {
                                          ParamLayout, _P, c_int64, c_int, c_int, _P]),
     'tfep_inverse_chain_f64_lds_bytes': (c_int64, [c_int, c_int, c_int]),
     'tfep_inverse_chain_f64': (c_int, [POINTER(InverseChainF64Desc), _P]),
+    'tfep_inverse_chain_vec_f64': (c_int, [POINTER(InverseChainVecF64Desc), _P]),
     'tfep_periodic_embedding_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double,
                                             _P, c_int64, c_int, _P]),
     'tfep_periodic_embedding_backward_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double, _P, c_int64,

@@ -18,8 +18,19 @@
 // Summation order of a row's pre-activation: panel + bias, then the chain's columns in ascending order on two
 // interleaved accumulators -- fixed per sample row and independent of the batch (no atomics, no split by batch size), so
 // a row has the same bits alone and inside any batch.  Everything is fp64: IEEE fma, library expm1 / exp / log / sincos.
+//
+// Vector members (tfep_inverse_chain_vec_f64, chain_kernel<KMAX, true>): a symmetrized Moebius d-vector or a quaternion
+// is one unit of work of a degree.  The wave that owns it follows the links of its feature records (feats[s][6]: 1 +
+// component index, feats[s][7]: the slot of the next component), reads the d parameters from `par` (P = 1 per feature)
+// and the d values of y, evaluates the map of symmoebius.h / quatprod.h once and writes every component; the log-det
+// goes to the slot of component 0, 0.0 to the others, so the row's sum stays "in slot order, wave 0".  The scalar
+// instantiation chain_kernel<KMAX, false> compiles none of this.
+#include <type_traits>
+
 #include "common.h"
+#include "quatprod.h"
 #include "spline_f64.h"
+#include "symmoebius.h"
 
 namespace tfep {
 namespace inv64 {
@@ -34,6 +45,11 @@ struct ChainArgs {
     Spline64 spl[MAXM];
 };
 
+struct ChainVecArgs : ChainArgs {
+    int32_t dim[MAXM];
+    double max_radius[MAXM];
+};
+
 // acc + sum_j w[j] * s[j][lane], j ascending, even / odd j on two accumulators
 __device__ inline double chain_dot(double acc, const double* __restrict__ w, const double* s, int n, int lane) {
     double acc1 = 0.0;
@@ -46,8 +62,8 @@ __device__ inline double chain_dot(double acc, const double* __restrict__ w, con
     return acc + acc1;
 }
 
-template <int KMAX>
-__global__ void __launch_bounds__(THREADS) chain_kernel(ChainArgs g) {
+template <int KMAX, bool VEC>
+__global__ void __launch_bounds__(THREADS) chain_kernel(std::conditional_t<VEC, ChainVecArgs, ChainArgs> g) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const tfep_inverse_chain_f64_desc& d = g.d;
     const int lane = threadIdx.x & 63;
@@ -90,9 +106,56 @@ __global__ void __launch_bounds__(THREADS) chain_kernel(ChainArgs g) {
             }
             __syncthreads();
             // 2. the inverse transformer element, x, the conditioner inputs it feeds
-            for (int f = f0 + wave; f < f1; f += WAVES) {
+            [[maybe_unused]] int unit = 0;                              // VEC: scalar features and heads of vectors
+            for (int f = VEC ? f0 : f0 + wave; f < f1; f += VEC ? 1 : WAVES) {
                 const int32_t* ft = d.feats + (int64_t)f * FEAT_INTS;
                 const int col_x = ft[0], member = ft[1], pos = ft[4], periodic = ft[5];
+                if constexpr (VEC) {
+                    const int comp = ft[6];
+                    if (comp > 1) continue;                                 // written with the head of its vector
+                    if ((unit++ & (WAVES - 1)) != wave) continue;
+                    if (comp == 1) {
+                        const int kind = d.member_kind[member], dim = kind == 3 ? 4 : g.dim[member];
+                        double yv[MOEBIUS_MAX_DIM], wv[MOEBIUS_MAX_DIM], xv[MOEBIUS_MAX_DIM];
+                        int slot[MOEBIUS_MAX_DIM];
+                        int s_ = f;
+#pragma unroll
+                        for (int i = 0; i < MOEBIUS_MAX_DIM; ++i) {
+                            slot[i] = -1;
+                            yv[i] = wv[i] = xv[i] = 0.0;
+                            if (i < dim && s_ >= f0 && s_ < f1) {                // (a link never leaves the degree: host plan)
+                                const int32_t* fc = d.feats + (int64_t)s_ * FEAT_INTS;
+                                slot[i] = s_;
+                                wv[i] = par[(int64_t)(s_ - f0) * d.par_cols * ROWS + lane];
+                                yv[i] = d.y[bc * d.ldy + fc[0]];
+                                s_ = fc[7];
+                            }
+                        }
+                        double ld = 0.0;
+                        if (kind == 3) {                                    // quaternion product: volume preserving
+                            const double y4[4] = {yv[0], yv[1], yv[2], yv[3]}, w4[4] = {wv[0], wv[1], wv[2], wv[3]};
+                            double x4[4];
+                            quatprod_element<double, true>(y4, w4, x4);
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) xv[i] = x4[i];
+                        } else {                                            // log|det J| of the inverse itself (symmoebius.h)
+                            ld = symmoebius_vector<double, true>(yv, wv, dim, g.max_radius[member], xv);
+                        }
+#pragma unroll
+                        for (int i = 0; i < MOEBIUS_MAX_DIM; ++i) {
+                            if (slot[i] < 0) continue;
+                            const int32_t* fc = d.feats + (int64_t)slot[i] * FEAT_INTS;
+                            const int cx = fc[0], ps = fc[4];
+                            ldjc[(slot[i] - f0) * ROWS + lane] = i == 0 ? ld : 0.0;
+                            S0[(ps - d.k0[0]) * ROWS + lane] = xv[i];
+                            if (live) {
+                                d.x[(int64_t)b * d.ldx + cx] = xv[i];
+                                d.a[0][(int64_t)b * d.lda[0] + ps] = xv[i];
+                            }
+                        }
+                        continue;
+                    }
+                }
                 const double* pf = par + (int64_t)(f - f0) * d.par_cols * ROWS + lane;
                 const double yv = d.y[bc * d.ldy + col_x];
                 double xv, contrib;
@@ -147,18 +210,89 @@ inline int64_t lds_bytes(int64_t n_cols_total, int64_t par_cols, int64_t max_fea
     return (n_cols_total + par_cols * max_feats + max_feats) * ROWS * (int64_t)sizeof(double);
 }
 
-template <int KMAX>
-int launch(const ChainArgs& g, size_t lds, hipStream_t stream) {
+template <int KMAX, bool VEC>
+int launch(const std::conditional_t<VEC, ChainVecArgs, ChainArgs>& g, size_t lds, hipStream_t stream) {
     static bool attr_done[TFEP_MAX_DEVICES] = {};
     const int slot = current_device_slot();
     if (!attr_done[slot]) {
-        hipError_t e = hipFuncSetAttribute((const void*)chain_kernel<KMAX>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute((const void*)chain_kernel<KMAX, VEC>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)LDS_LIMIT);
         if (e != hipSuccess) return fail(TFEP_ERR_LAUNCH, "hipFuncSetAttribute(LDS=%d): %s", (int)LDS_LIMIT, hipGetErrorString(e));
         attr_done[slot] = true;
     }
-    chain_kernel<KMAX><<<(unsigned)((g.d.B + ROWS - 1) / ROWS), THREADS, lds, stream>>>(g);
-    return check_launch("inverse_chain_f64_kernel");
+    chain_kernel<KMAX, VEC><<<(unsigned)((g.d.B + ROWS - 1) / ROWS), THREADS, lds, stream>>>(g);
+    return check_launch(VEC ? "inverse_chain_vec_f64_kernel" : "inverse_chain_f64_kernel");
+}
+
+// The argument checks and the launch of both entry points; `who` prefixes the error messages.  VEC: member kinds 2 and 3
+// with member_dim / member_max_radius.
+template <bool VEC>
+int run(const char* who, const tfep_inverse_chain_f64_desc* d, const int32_t* member_dim, const double* member_max_radius,
+        void* stream) {
+    TFEP_REQUIRE(d->B >= 0, "%s: negative batch", who);
+    TFEP_REQUIRE(d->n_linears >= 2 && d->n_linears <= MAXL, "%s: n_linears=%d unsupported (2..%d)", who, d->n_linears, MAXL);
+    TFEP_REQUIRE(d->n_members >= 1 && d->n_members <= MAXM, "%s: n_members=%d unsupported (1..%d)", who, d->n_members, MAXM);
+    TFEP_REQUIRE(d->n_steps >= 0 && d->par_cols >= 1 && d->max_feats >= 1, "%s: bad step / parameter counts", who);
+    if (d->B == 0 || d->n_steps == 0) return TFEP_OK;         // (an empty batch has no storage: its pointers are NULL)
+    TFEP_REQUIRE(d->y && d->x && d->log_det_J && d->steps && d->feats, "%s: NULL pointer (y / x / log_det_J / tables)", who);
+    TFEP_REQUIRE(d->ldy >= 1 && d->ldx >= 1, "%s: row strides of x / y must be positive", who);
+    const int L = d->n_linears - 1;
+    int64_t n_cols_total = 0;
+    for (int l = 0; l <= L; ++l) {
+        TFEP_REQUIRE(d->a[l] && d->w[l] && d->bias[l], "%s: NULL operand of linear %d", who, l);
+        TFEP_REQUIRE((uintptr_t)d->a[l] % 8 == 0 && (uintptr_t)d->w[l] % 8 == 0 && (uintptr_t)d->bias[l] % 8 == 0,
+                     "%s: operands of linear %d are not 8-byte aligned", who, l);
+        TFEP_REQUIRE(d->k0[l] >= 0 && d->k0[l] % 16 == 0, "%s: k0[%d]=%d must be a non-negative multiple of 16 "
+                     "(where the panel product stops)", who, l, d->k0[l]);
+        TFEP_REQUIRE(d->n_old[l] >= 0 && d->n_old[l] < 16 && d->n_cols[l] >= d->n_old[l],
+                     "%s: linear %d: n_old=%d must be in [0, 16) and at most n_cols=%d", who, l, d->n_old[l], d->n_cols[l]);
+        TFEP_REQUIRE(d->lda[l] >= (int64_t)d->k0[l] + d->n_cols[l] && d->ldw[l] >= (int64_t)d->k0[l] + d->n_cols[l],
+                     "%s: row strides of linear %d too small for columns [%d, %d)", who, l, d->k0[l], d->k0[l] + d->n_cols[l]);
+        TFEP_REQUIRE(d->lds_col0[l] == n_cols_total, "%s: lds_col0[%d]=%d, expected the running sum of n_cols (%lld)", who, l,
+                     d->lds_col0[l], (long long)n_cols_total);
+        n_cols_total += d->n_cols[l];
+    }
+    TFEP_REQUIRE(!d->has_panel[L] || (d->zout && d->ldzout >= 1 && (uintptr_t)d->zout % 8 == 0),
+                 "%s: the output panel needs zout and a positive row stride", who);
+    const int64_t lds = lds_bytes(n_cols_total, d->par_cols, d->max_feats);
+    TFEP_REQUIRE(lds <= LDS_LIMIT, "%s: the block's state needs %lld bytes of LDS (limit %lld): fewer degrees per block", who,
+                 (long long)lds, (long long)LDS_LIMIT);
+    std::conditional_t<VEC, ChainVecArgs, ChainArgs> g = {};
+    g.d = *d;
+    int kmax = 0;
+    for (int m = 0; m < d->n_members; ++m) {
+        const int kind = d->member_kind[m];
+        if constexpr (VEC) {
+            TFEP_REQUIRE(kind >= 0 && kind <= 3, "%s: member %d: kind must be 0 (affine), 1 (RQ spline), 2 (symmetrized Moebius) "
+                         "or 3 (quaternion product)", who, m);
+            if (kind == 2) {
+                TFEP_REQUIRE(member_dim[m] >= 2 && member_dim[m] <= MOEBIUS_MAX_DIM, "%s: member %d: member_dim=%d of a "
+                             "symmetrized Moebius member must be in 2..%d", who, m, member_dim[m], MOEBIUS_MAX_DIM);
+                TFEP_REQUIRE(member_max_radius[m] > 0.0 && member_max_radius[m] < 1.0, "%s: member %d: max_radius=%g must be "
+                             "in (0, 1)", who, m, member_max_radius[m]);
+            } else if (kind == 3) {
+                TFEP_REQUIRE(member_dim[m] == 4, "%s: member %d: member_dim=%d of a quaternion member must be 4", who, m,
+                             member_dim[m]);
+            }
+            g.dim[m] = kind >= 2 ? member_dim[m] : 0;
+            g.max_radius[m] = kind == 2 ? member_max_radius[m] : 0.0;
+        } else {
+            TFEP_REQUIRE(kind == 0 || kind == 1, "%s: member %d: kind must be 0 (affine) or 1 (RQ spline)", who, m);
+        }
+        if (kind == 1) {
+            int rc = make_spline64(&d->spline[m], &g.spl[m]);
+            if (rc) return rc;
+            TFEP_REQUIRE(g.spl[m].P <= d->par_cols, "%s: member %d has %d parameters per feature, par_cols=%d", who, m,
+                         g.spl[m].P, d->par_cols);
+            kmax = g.spl[m].K > kmax ? g.spl[m].K : kmax;
+        } else if (kind == 0) {
+            TFEP_REQUIRE(d->par_cols >= 2, "%s: an affine member needs par_cols >= 2", who);
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (kmax <= 8) return launch<8, VEC>(g, (size_t)lds, s);
+    if (kmax <= 16) return launch<16, VEC>(g, (size_t)lds, s);
+    return launch<32, VEC>(g, (size_t)lds, s);
 }
 
 }  // namespace inv64
@@ -175,57 +309,12 @@ int64_t tfep_inverse_chain_f64_lds_bytes(int n_cols_total, int par_cols, int max
 
 int tfep_inverse_chain_f64(const tfep_inverse_chain_f64_desc* d, void* stream) {
     TFEP_REQUIRE(d != nullptr, "inverse_chain_f64: descriptor is NULL");
-    TFEP_REQUIRE(d->B >= 0, "inverse_chain_f64: negative batch");
-    TFEP_REQUIRE(d->n_linears >= 2 && d->n_linears <= inv64::MAXL, "inverse_chain_f64: n_linears=%d unsupported (2..%d)",
-                 d->n_linears, inv64::MAXL);
-    TFEP_REQUIRE(d->n_members >= 1 && d->n_members <= inv64::MAXM, "inverse_chain_f64: n_members=%d unsupported (1..%d)",
-                 d->n_members, inv64::MAXM);
-    TFEP_REQUIRE(d->n_steps >= 0 && d->par_cols >= 1 && d->max_feats >= 1, "inverse_chain_f64: bad step / parameter counts");
-    if (d->B == 0 || d->n_steps == 0) return TFEP_OK;         // (an empty batch has no storage: its pointers are NULL)
-    TFEP_REQUIRE(d->y && d->x && d->log_det_J && d->steps && d->feats, "inverse_chain_f64: NULL pointer (y / x / log_det_J / tables)");
-    TFEP_REQUIRE(d->ldy >= 1 && d->ldx >= 1, "inverse_chain_f64: row strides of x / y must be positive");
-    const int L = d->n_linears - 1;
-    int64_t n_cols_total = 0;
-    for (int l = 0; l <= L; ++l) {
-        TFEP_REQUIRE(d->a[l] && d->w[l] && d->bias[l], "inverse_chain_f64: NULL operand of linear %d", l);
-        TFEP_REQUIRE((uintptr_t)d->a[l] % 8 == 0 && (uintptr_t)d->w[l] % 8 == 0 && (uintptr_t)d->bias[l] % 8 == 0,
-                     "inverse_chain_f64: operands of linear %d are not 8-byte aligned", l);
-        TFEP_REQUIRE(d->k0[l] >= 0 && d->k0[l] % 16 == 0, "inverse_chain_f64: k0[%d]=%d must be a non-negative multiple of 16 "
-                     "(where the panel product stops)", l, d->k0[l]);
-        TFEP_REQUIRE(d->n_old[l] >= 0 && d->n_old[l] < 16 && d->n_cols[l] >= d->n_old[l],
-                     "inverse_chain_f64: linear %d: n_old=%d must be in [0, 16) and at most n_cols=%d", l, d->n_old[l], d->n_cols[l]);
-        TFEP_REQUIRE(d->lda[l] >= (int64_t)d->k0[l] + d->n_cols[l] && d->ldw[l] >= (int64_t)d->k0[l] + d->n_cols[l],
-                     "inverse_chain_f64: row strides of linear %d too small for columns [%d, %d)", l, d->k0[l],
-                     d->k0[l] + d->n_cols[l]);
-        TFEP_REQUIRE(d->lds_col0[l] == n_cols_total, "inverse_chain_f64: lds_col0[%d]=%d, expected the running sum of n_cols (%lld)",
-                     l, d->lds_col0[l], (long long)n_cols_total);
-        n_cols_total += d->n_cols[l];
-    }
-    TFEP_REQUIRE(!d->has_panel[L] || (d->zout && d->ldzout >= 1 && (uintptr_t)d->zout % 8 == 0),
-                 "inverse_chain_f64: the output panel needs zout and a positive row stride");
-    const int64_t lds = inv64::lds_bytes(n_cols_total, d->par_cols, d->max_feats);
-    TFEP_REQUIRE(lds <= inv64::LDS_LIMIT, "inverse_chain_f64: the block's state needs %lld bytes of LDS (limit %lld): fewer "
-                 "degrees per block", (long long)lds, (long long)inv64::LDS_LIMIT);
-    inv64::ChainArgs g = {};
-    g.d = *d;
-    int kmax = 0;
-    for (int m = 0; m < d->n_members; ++m) {
-        TFEP_REQUIRE(d->member_kind[m] == 0 || d->member_kind[m] == 1, "inverse_chain_f64: member %d: kind must be 0 (affine) or "
-                     "1 (RQ spline)", m);
-        if (d->member_kind[m] == 1) {
-            int rc = make_spline64(&d->spline[m], &g.spl[m]);
-            if (rc) return rc;
-            TFEP_REQUIRE(g.spl[m].P <= d->par_cols, "inverse_chain_f64: member %d has %d parameters per feature, par_cols=%d",
-                         m, g.spl[m].P, d->par_cols);
-            kmax = g.spl[m].K > kmax ? g.spl[m].K : kmax;
-        } else {
-            TFEP_REQUIRE(d->par_cols >= 2, "inverse_chain_f64: an affine member needs par_cols >= 2");
-        }
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (kmax <= 8) return inv64::launch<8>(g, (size_t)lds, s);
-    if (kmax <= 16) return inv64::launch<16>(g, (size_t)lds, s);
-    return inv64::launch<32>(g, (size_t)lds, s);
+    return inv64::run<false>("inverse_chain_f64", d, nullptr, nullptr, stream);
+}
+
+int tfep_inverse_chain_vec_f64(const tfep_inverse_chain_vec_f64_desc* d, void* stream) {
+    TFEP_REQUIRE(d != nullptr, "inverse_chain_vec_f64: descriptor is NULL");
+    return inv64::run<true>("inverse_chain_vec_f64", &d->chain, d->member_dim, d->member_max_radius, stream);
 }
 
 }  // extern "C"

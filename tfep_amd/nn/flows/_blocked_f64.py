@@ -12,6 +12,9 @@ starts (and so are, from the very start, the inputs of degree -1, which no step 
 multiplies the block's rows with columns ``[0, k0)``, ``k0`` = that count rounded DOWN to the GEMM's k granularity (16),
 and the chain kernel (``csrc/inverse_block_f64.hip``) adds columns ``[k0, cut)`` of every row: each product is counted
 exactly once.
+
+Vector-valued members (symmetrized Moebius, quaternion product; ``blocked_inverse_f64_vectors``): ``vector_links`` says
+which slots are the components of one vector, for ``tfep_inverse_chain_vec_f64``.
 """
 import numpy as np
 
@@ -145,3 +148,46 @@ def feature_slots(deg_tr, params_of, member_of=None, local_of=None, member_offse
     if np.any(row_of_out < 0):
         raise ValueError('feature_slots: the conditioner outputs do not match the transformer parameters')
     return order, base, row_of_out
+
+
+def vector_links(slot_order, deg_tr, member_of, local_of, member_dim, periodic_of=None):
+    """The links of the vector members (``tfep_inverse_chain_vec_f64``: ints 6 and 7 of a feature record).
+
+    ``slot_order[s]``: the transformed feature in slot ``s`` (``feature_slots``); ``deg_tr[t]`` / ``member_of[t]`` /
+    ``local_of[t]``: degree, member and index inside its member of feature ``t`` (``member_of`` None: one member);
+    ``member_dim[g]``: the vector dimension of member ``g``, 0 for an element-wise member; ``periodic_of[t]``: is the feature
+    periodic in the conditioner's embedding (None: none is).
+
+    Vector ``v`` of a member is its local features ``[v * dim, (v + 1) * dim)`` -- the reference's ``reshape(B, -1, dim)``
+    on the member's own feature order.  Returns the ``(n_slots, 2)`` int32 table ``[1 + component, next slot]`` (component
+    0 for an element-wise member, next -1 at the last component and for element-wise members), or None when a member's
+    feature count is no multiple of its dimension, a vector spans two degrees, or a component is periodic.  Slots are
+    sorted by degree, so all the links of a vector stay inside the slot range of its degree.
+    """
+    slot_order = np.asarray(slot_order, dtype=np.int64)
+    deg_tr = np.asarray(deg_tr, dtype=np.int64)
+    local_of = np.asarray(local_of, dtype=np.int64)
+    n = len(slot_order)
+    member_of = np.zeros(n, dtype=np.int64) if member_of is None else np.asarray(member_of, dtype=np.int64)
+    periodic_of = np.zeros(n, dtype=bool) if periodic_of is None else np.asarray(periodic_of, dtype=bool)
+    slot_of = np.empty(n, dtype=np.int64)
+    slot_of[slot_order] = np.arange(n)
+    links = np.zeros((n, 2), dtype=np.int32)
+    links[:, 1] = -1
+    for g, dim in enumerate(member_dim):
+        dim = int(dim)
+        if dim == 0:
+            continue
+        feats = np.nonzero(member_of == g)[0]
+        if len(feats) % dim != 0:
+            return None
+        feats = feats[np.argsort(local_of[feats], kind='stable')]
+        if not np.array_equal(local_of[feats], np.arange(len(feats))):
+            return None
+        for vec in feats.reshape(-1, dim):
+            if np.any(deg_tr[vec] != deg_tr[vec[0]]) or np.any(periodic_of[vec]):
+                return None
+            slots = slot_of[vec]
+            links[slots, 0] = 1 + np.arange(dim)
+            links[slots[:-1], 1] = slots[1:]
+    return links

@@ -31,6 +31,9 @@ from .sequential import _side_stream
 # (0 / 1 / 3: tfep_fused_kind; 2: one launch per group)
 _FUSED_AFFINE, _FUSED_SPLINE, _FUSED_MIXED, _FUSED_SOS = 0, 1, 2, 3
 
+# member_kind of the float64 chain kernels, by position (2 and 3: tfep_inverse_chain_vec_f64 only)
+_F64_CHAIN_KINDS = (AffineTransformer, NeuralSplineTransformer, SymmetrizedMoebiusTransformer, QuaternionProductTransformer)
+
 
 class AutoregressiveFlow(torch.nn.Module):
     """Transform features with a transformer parametrised by a conditioner (Papamakarios et al. 2017)."""
@@ -1758,11 +1761,17 @@ class AutoregressiveFlow(torch.nn.Module):
     #: (``_blocked_f64.fit_block``).  Larger blocks mean fewer, fuller panel GEMMs; 16 is what fits a cfg2-sized layer.
     inverse_block_f64 = 16
 
+    #: Opt-in: let the float64 blocked inverse also take a ``SymmetrizedMoebiusTransformer`` or a
+    #: ``QuaternionProductTransformer``, alone or as a member of a mixed transformer, when every vector lies inside one
+    #: degree (chain kernel ``tfep_inverse_chain_vec_f64``).  Off by default: such layers keep the pass per degree.
+    blocked_inverse_f64_vectors = False
+
     def _blocked_f64_ok(self):
         """Does this float64 layer take the float64 blocked inverse?  A MADE conditioner (2 .. 5 masked linears, masks that
         a degree assignment reproduces, no embedding or a PeriodicEmbedding, no ``_conditioner_indices``) and an affine or
         RQ-spline transformer, or a mixed transformer of up to four such members; features that no step transforms pass
-        through.  Everything else keeps the pass per degree."""
+        through.  With ``blocked_inverse_f64_vectors`` a symmetrized Moebius or quaternion-product transformer (or member)
+        whose vectors each lie inside one degree qualifies too.  Everything else keeps the pass per degree."""
         made = self._conditioner
         if not self.blocked_inverse or not self.is_float64 or not isinstance(made, MADE) or len(self._conditioner_indices) > 0:
             return False
@@ -1773,7 +1782,8 @@ class AutoregressiveFlow(torch.nn.Module):
             return False
         tr = self._transformer
         members = tr._transformers if type(tr) is MixedTransformer else [tr]
-        if not all(type(t) in (AffineTransformer, NeuralSplineTransformer) for t in members):
+        kinds = _F64_CHAIN_KINDS if self.blocked_inverse_f64_vectors else _F64_CHAIN_KINDS[:2]
+        if not all(type(t) in kinds for t in members):
             return False
         return self._blocked_f64_host_plan() is not None
 
@@ -1781,7 +1791,7 @@ class AutoregressiveFlow(torch.nn.Module):
         """The host plan of the float64 blocked inverse (``flows/_blocked_f64.py``), or None when the layer's degrees do not
         fit it; cached per block size and mask version."""
         made = self._conditioner
-        key = ('blocked_f64_host', int(self.inverse_block_f64), made._mask_versions())
+        key = ('blocked_f64_host', int(self.inverse_block_f64), bool(self.blocked_inverse_f64_vectors), made._mask_versions())
         if key not in self._dev:
             self._dev[key] = self._make_blocked_f64_host_plan(max(1, int(self.inverse_block_f64)))
         return self._dev[key]
@@ -1825,8 +1835,8 @@ class AutoregressiveFlow(torch.nn.Module):
             offsets, counts = tr.host_splits(), [len(i) for i in inds]
         else:
             members, member_of, local_of, offsets, counts = [tr], None, np.arange(n_tr), None, None
-        kinds = [0 if type(t) is AffineTransformer else 1 for t in members]
-        P_of = [2 if k == 0 else t.n_parameters_per_feature for k, t in zip(kinds, members)]
+        kinds = [_F64_CHAIN_KINDS.index(type(t)) for t in members]       # (member_kind of the chain kernel)
+        P_of = [t.n_parameters_per_feature if k == 1 else 2 if k == 0 else 1 for k, t in zip(kinds, members)]
         mem = np.zeros(n_tr, dtype=np.int64) if member_of is None else member_of
         params_of = np.asarray(P_of, dtype=np.int64)[mem]
         if int(params_of.sum()) != lins[-1].out_features:
@@ -1849,6 +1859,13 @@ class AutoregressiveFlow(torch.nn.Module):
         for s, t in enumerate(slot_order):
             c = int(tr_idx[t])
             feats[s, :6] = (c, mem[t], params_of[t], base[s], input_pos(c), int(periodic[c]))
+        if any(k >= 2 for k in kinds):              # vector members: every vector inside one degree, its components linked
+            links = bf.vector_links(slot_order, deg_tr.numpy(), member_of, local_of,
+                                    [int(t.dimension) if k >= 2 else 0 for k, t in zip(kinds, members)],
+                                    [bool(periodic[int(c)]) for c in tr_idx])
+            if links is None:
+                return None
+            feats[:, 6:8] = links
         fixed = [int(c) for c in self._fixed_indices.cpu().tolist()]
         plan.update(feats=feats, slot_member=mem[slot_order], slot_local=np.asarray(local_of)[slot_order], members=members,
                     kinds=kinds, row_of_out=row_of_out, pos0=pos0, hidden_pos=[p for _, p in hidden], limits=limits,
@@ -1889,8 +1906,21 @@ class AutoregressiveFlow(torch.nn.Module):
         feats = torch.from_numpy(hp['feats']).to(device)
         lo, hi = hp['limits']
         descs, step0 = [], 0
+        vectors = any(k >= 2 for k in hp['kinds'])
+        entry = 'tfep_inverse_chain_vec_f64' if vectors else 'tfep_inverse_chain_f64'
+        outer = []                                  # what the entry point takes: the descriptor, or the one that holds it
         for b in hp['blocks']:
-            d = _lib.InverseChainF64Desc()
+            if vectors:
+                vd = _lib.InverseChainVecF64Desc()
+                d = vd.chain                        # (a view: filled below like the scalar descriptor)
+                for g, (t, kind) in enumerate(zip(hp['members'], hp['kinds'])):
+                    if kind >= 2:
+                        vd.member_dim[g] = int(t.dimension)
+                        vd.member_max_radius[g] = float(t.max_radius) if kind == 2 else 0.0
+                outer.append(vd)
+            else:
+                d = _lib.InverseChainF64Desc()
+                outer.append(d)
             d.n_linears, d.n_steps, d.n_members = L + 1, len(b['steps']), len(hp['members'])
             d.par_cols, d.max_feats, d.zout_row0 = hp['par_cols'], hp['max_feats'], b['out_rows'][0]
             for l in range(L + 1):
@@ -1913,6 +1943,7 @@ class AutoregressiveFlow(torch.nn.Module):
         def idx(pairs, j):
             return torch.tensor([p[j] for p in pairs], **i32)
         dp = dict(rows=rows, cols=cols, n_rows=n_rows, k_pad=k_pad, w=w, dom=dom, steps=steps, feats=feats, descs=descs,
+                  outer=outer, entry=entry,
                   fixed_plain=(idx(hp['fixed_plain'], 0), idx(hp['fixed_plain'], 1)),
                   fixed_periodic=(idx(hp['fixed_periodic'], 0), idx(hp['fixed_periodic'], 1)))
         hp['device'][key] = dp
@@ -1921,7 +1952,8 @@ class AutoregressiveFlow(torch.nn.Module):
     def _inverse_blocked_f64(self, y):
         """The float64 blocked forward substitution: per block of ``inverse_block_f64`` degrees one fp64-MFMA panel GEMM per
         masked linear (the block's rows times every column that earlier blocks made final, up to the last multiple of 16)
-        and one launch of the chain kernel (``tfep_inverse_chain_f64``: the remaining columns, ELU, transformer parameters,
+        and one launch of the chain kernel (``tfep_inverse_chain_f64``, or ``tfep_inverse_chain_vec_f64`` for a layer with a
+        vector-valued member: the remaining columns, ELU, transformer parameters,
         inverse transformer, log-det, periodic embedding), on weights packed once per call with rows and columns sorted by
         degree.  About one forward in flops; all in fp64; a row's bits do not depend on its batch."""
         hp = self._blocked_f64_host_plan()
@@ -1958,7 +1990,7 @@ class AutoregressiveFlow(torch.nn.Module):
         zout = torch.empty(B, ldz, **f64)
         stream = _lib.stream_of(y)
         vp = ctypes.c_void_p
-        for blk, d in zip(hp['blocks'], dp['descs']):
+        for blk, d, outer in zip(hp['blocks'], dp['descs'], dp['outer']):
             for l in range(L + 1):
                 r0, r1 = blk['rows'][l] if l < L else blk['out_rows']
                 k0 = blk['k0'][l]
@@ -1974,7 +2006,7 @@ class AutoregressiveFlow(torch.nn.Module):
             for l in range(L + 1):
                 d.a[l], d.bias[l] = a[l].data_ptr(), bias[l].data_ptr()
             d.zout, d.ldzout = zout.data_ptr(), ldz
-            _lib.call('tfep_inverse_chain_f64', ctypes.byref(d), stream)
+            _lib.call(dp['entry'], ctypes.byref(outer), stream)
         return x, ldj
 
     def get_transformer_parameters(self, x: torch.Tensor) -> torch.Tensor:

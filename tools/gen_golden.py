@@ -1571,6 +1571,89 @@ def gen_quatprod():
     np.savez_compressed(os.path.join(OUT, 'quatprod.npz'), **out)
 
 
+#: blocked_f64_vectors.npz, flow ``mixed``: member indices and the ascending degrees (the descending layer: 9 - degree).
+#: Degrees 0 .. 3 each hold a 2-vector with a spline feature BETWEEN its components (the slot order interleaves), degrees
+#: 4 and 5 a quaternion each, degrees 6 .. 9 a spline feature each.
+BLOCKED_F64_MIXED_INDICES = [[0, 2, 3, 5, 6, 8, 9, 11], list(range(12, 20)), [1, 4, 7, 10, 20, 21, 22, 23]]
+BLOCKED_F64_MIXED_DEGREES = [0] * 3 + [1] * 3 + [2] * 3 + [3] * 3 + [4] * 4 + [5] * 4 + [6, 7, 8, 9]
+BLOCKED_F64_HIDDEN = [40, 40]
+
+
+def blocked_f64_vector_flows():
+    """The flow configurations of blocked_f64_vectors.npz: name -> constructor(dtype).  D = 24, two layers (ascending,
+    descending), every vector inside one degree, hidden width 40 (later blocks of the float64 blocked inverse have panels)."""
+    from tfep.nn.conditioners.made import generate_degrees as gd
+    from tfep.nn.transformers.moebius import SymmetrizedMoebiusTransformer
+    from tfep.nn.transformers.quatprod import QuaternionProductTransformer
+
+    def two(make_tr, asc, desc):
+        return SequentialFlow(*(MAF(degrees_in=deg, transformer=make_tr(), hidden_layers=list(BLOCKED_F64_HIDDEN),
+                                    initialize_identity=False) for deg in (asc, desc)))
+
+    def mixed(dt):
+        return MixedTransformer(
+            transformers=[SymmetrizedMoebiusTransformer(2), QuaternionProductTransformer(),
+                          NeuralSplineTransformer(x0=torch.full((8,), -4.0).to(dt), xf=torch.full((8,), 4.0).to(dt), n_bins=8)],
+            indices=BLOCKED_F64_MIXED_INDICES)
+    asc = torch.tensor(BLOCKED_F64_MIXED_DEGREES)
+    return {
+        'sym3': lambda dt: two(lambda: SymmetrizedMoebiusTransformer(3), gd(24, 'ascending', repeats=3),
+                               gd(24, 'descending', repeats=3)),
+        'quat': lambda dt: two(QuaternionProductTransformer, gd(24, 'ascending', repeats=4), gd(24, 'descending', repeats=4)),
+        'mixed': lambda dt: two(lambda: mixed(dt), asc, 9 - asc),
+    }
+
+
+def gen_blocked_f64_vectors():
+    """float64 flows with vector-valued transformers for the float64 blocked inverse (tests/test_gpu_blocked_f64_vectors.py),
+    the reference in float64 on float32-rounded inputs and weights: x, ``y`` / ``ldj`` (forward), ``y_inv`` / ``ldj_inv`` (the
+    inverse applied to the same x), the state, and BoltzmannKLDivLoss(u(.), log_det_J) with u(y) = sum_f (c_f y_f^2 + d_f y_f)
+    through the inverse with its gradients.  Refuses to write unless the reference's own inverse(forward(x)) returns x to
+    1e-10 on every flow (else a vector straddles two degrees)."""
+    import roma_standin
+    roma_standin.install()
+    out = {}
+    B, D = 32, 24
+
+    def quad(y, c, d):
+        return (c * y ** 2 + d * y).sum(dim=1)
+
+    for i, (name, make) in enumerate(blocked_f64_vector_flows().items()):
+        seed = 400 + 10 * i
+        torch.manual_seed(seed)
+        f32 = make(torch.float32)
+        perturb_weight_g(f32, seed + 1)
+        g = gen(seed + 2)
+        x = torch.randn(B, D, generator=g).double()
+        c = (torch.rand(D, generator=g) * 0.3).double()
+        d = (torch.randn(D, generator=g) * 0.2).double()
+        sd = {k: v.clone() for k, v in f32.state_dict().items()}
+        with f64():
+            m = make(torch.float64)
+            m.load_state_dict(to_double_sd(sd))
+            with torch.no_grad():
+                y, ldj = m(x)
+                back, ldj_back = m.inverse(y)
+            err = float((back - x).abs().max())
+            print(f'{name}: reference round trip max |inverse(forward(x)) - x| = {err:.3e}, '
+                  f'log-dets cancel to {float((ldj + ldj_back).abs().max()):.3e}')
+            assert err <= 1e-10, (name, err)
+            xx = x.clone().requires_grad_(True)
+            y_inv, ldj_inv = m.inverse(xx)
+            loss = BoltzmannKLDivLoss()(quad(y_inv, c, d), ldj_inv)
+            loss.backward()
+        out[f'{name}/x'], out[f'{name}/c'], out[f'{name}/d'] = npy(x), npy(c), npy(d)
+        out[f'{name}/y'], out[f'{name}/ldj'] = npy(y), npy(ldj)
+        out[f'{name}/y_inv'], out[f'{name}/ldj_inv'] = npy(y_inv), npy(ldj_inv)
+        out[f'{name}/loss_inv'], out[f'{name}/gx_inv'] = npy(loss), npy(xx.grad)
+        for k, prm in m.named_parameters():
+            out[f'{name}/grad_inv/{k}'] = npy(prm.grad)
+        for k, v in sd.items():
+            if not k.endswith('.mask'):
+                out[f'{name}/sd/{k}'] = npy(v)
+    np.savez_compressed(os.path.join(OUT, 'blocked_f64_vectors.npz'), **out)
+
+
 # -----------------------------------------------------------------------------
 # FlipInvariantEmbedding on its kernels: module outputs and gradients at the shapes where a kernel can go wrong
 # -----------------------------------------------------------------------------
