@@ -215,20 +215,49 @@ typedef float f32x4_alias __attribute__((ext_vector_type(4), may_alias));
 template <int P> constexpr int spl_rec() { return P + 1 <= 20 ? 20 : 28; }
 template <int P> constexpr int spl_wave_bytes() { return 16 * 16 * spl_rec<P>() * 4; }     // one 16-row block of one wave
 
-// dynamic LDS of one kernel instantiation: the operand stages, or the epilogue records of a narrow spline tile
+// Accumulator groups (one f32x4: a lane's four rows of one 16-row block and one parameter) that the epilogue of the 8-bin
+// layouts with up to 25 parameters parks in LDS.  While block m is evaluated the accumulators of blocks m + 1 .. 3 are
+// still live (300 registers for P = 25) beside the two interleaved fp64 chains of the evaluation (~125 VGPRs) and the
+// bias, row scales and inputs (~60).  The evaluation needs VGPRs, so the VGPR-held groups (parameters N_ACC_AGPR .. P - 1)
+// are what is in its way: the 12 needed last go to LDS -- the operand stages are dead by then, and 12 groups per lane is
+// what the 160 KB hold beside the records of one block -- and the others move into the AGPRs that block 0 frees.  The
+// AGPR-held groups stay where they are.  (Before, the allocator sent 47 groups to scratch memory and back: 756 B per lane,
+// 9.3 GB per launch of the cfg2 layer.)  Slot q is parameter P - 1 - q % NV of block 3 - q / NV, NV = P - N_ACC_AGPR.
+// The layouts with 26 / 27 parameters have more VGPR-held groups than LDS and block 0's AGPRs take, the narrow ones
+// spill little or nothing: they keep the epilogue they had.
+template <int P> constexpr int spl_park_groups() { return (P >= 23 && P <= 25) ? 12 : 0; }
+template <int P> constexpr int spl_park_wave_bytes() { return spl_park_groups<P>() * 64 * 16; }
+template <int P>
+constexpr int spl_park_slot(int n, int m) {
+    constexpr int NV = P - N_ACC_AGPR;
+    if (NV <= 0 || n < N_ACC_AGPR || m == 0) return -1;
+    const int q = (SMREP - 1 - m) * NV + (P - 1 - n);
+    return q < spl_park_groups<P>() ? q : -1;
+}
+
+// dynamic LDS of one kernel instantiation: the operand stages, or the epilogue records (and parked accumulators) of a
+// spline tile
 template <int NREP, int EPI, int P>
 constexpr int split_lds_bytes() {
     constexpr int stages = STile<NREP>::LDS_BYTES;
-    if constexpr (epi_is_spline(EPI)) return stages > SWAVES * spl_wave_bytes<P>() ? stages : SWAVES * spl_wave_bytes<P>();
+    constexpr int epilogue = SWAVES * (spl_wave_bytes<P>() + spl_park_wave_bytes<P>());
+    if constexpr (epi_is_spline(EPI)) return stages > epilogue ? stages : epilogue;
     return stages;
 }
 
 template <int KSPL, int P, bool IDB, bool SAVE>
 __device__ __forceinline__ void split_spline_epilogue(const GemmArgs& g, f32x4 (&acc)[P][SMREP],
                                                       const f32x4 (&rs)[SMREP], int nt, int n0, int wrow0, int lane,
-                                                      float* rec_base) {
+                                                      float* rec_base, f32x4_alias* park_lane) {
     constexpr int SPL_REC = spl_rec<P>();
     static_assert(P + 1 <= SPL_REC, "record too small");
+    // The parked groups leave the registers first, 16 bytes per lane and slot (lanes side by side: no bank conflicts);
+    // a wave reads back what it wrote itself, block by block, where the records are made.
+    static_for<0, P * SMREP>([&](auto ic) __attribute__((always_inline)) {
+        constexpr int n = ic.value / SMREP, m = ic.value % SMREP;
+        constexpr int q = spl_park_slot<P>(n, m);
+        if constexpr (q >= 0) park_lane[q * 64] = acc[n][m];
+    });
     const FusedArgs& fu = g.fu;
     const SplineFlags sf = spline_flags_of_layout<KSPL, P, IDB>(fu.sf);
     const int cj = lane & 15, gq = lane >> 4;
@@ -260,11 +289,35 @@ __device__ __forceinline__ void split_spline_epilogue(const GemmArgs& g, f32x4 (
     float* rec0 = rec_base + ((gq * 4) * 16 + cj) * SPL_REC;      // record of (row gq*4, feature cj)
     static_for<0, SMREP>([&](auto mc) __attribute__((always_inline)) {
         constexpr int m = mc.value;
-        static_for<0, P * 4>([&](auto ic) __attribute__((always_inline)) {
-            constexpr int n = ic.value / 4, i = ic.value % 4;
-            rec0[i * 16 * SPL_REC + n] = acc[n][m][i] * rs[m][i] + bias_p[n];
+        static_for<0, P>([&](auto nc) __attribute__((always_inline)) {
+            constexpr int n = nc.value;
+            constexpr int q = spl_park_slot<P>(n, m);
+            f32x4 a;
+            if constexpr (q >= 0) {
+                a = park_lane[q * 64];
+            } else {
+                // (re-defined where it lives, right in front of its use: the copy into VGPRs that the arithmetic needs is
+                // made here -- made where the accumulators leave the k-loop, it is a VGPR value that lives to this point)
+                if constexpr (m > 0 && spl_park_groups<P>() > 0) redefine<true>(acc[n][m]);
+                a = acc[n][m];
+            }
+            static_for<0, 4>([&](auto ic) __attribute__((always_inline)) {
+                constexpr int i = ic.value;
+                rec0[i * 16 * SPL_REC + n] = a[i] * rs[m][i] + bias_p[n];
+            });
         });
         static_for<0, 4>([&](auto ic) __attribute__((always_inline)) { rec0[ic.value * 16 * SPL_REC + P] = xin[m][ic.value]; });
+        if constexpr (m == 0 && spl_park_groups<P>() > 0) {
+            // Block 0's accumulators are records now: the 16 * N_ACC_AGPR / SMREP AGPRs they had take the VGPR-held groups
+            // that are not parked, and the VGPRs are the evaluation's.
+            static_assert((P - N_ACC_AGPR) * (SMREP - 1) - spl_park_groups<P>() <= N_ACC_AGPR, "more groups than block 0 frees");
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<N_ACC_AGPR * SMREP, P * SMREP>([&](auto ic) __attribute__((always_inline)) {
+                constexpr int n = ic.value / SMREP, mm = ic.value % SMREP;
+                if constexpr (mm > 0 && spl_park_slot<P>(n, mm) < 0) redefine<true>(acc[n][mm]);
+            });
+            __builtin_amdgcn_sched_barrier(0);
+        }
         // two records per iteration, in one basic block: their fp64 chains are independent and interleave
 #pragma nounroll
         for (int i0 = 0; i0 < 4; i0 += 2) {
@@ -615,9 +668,12 @@ __global__ void __launch_bounds__(STHREADS, OCC) split_gemm_kernel(GemmArgs g, i
         });
     }
     if constexpr (epi_is_spline(EPI)) {
-        static_assert(SWAVES * spl_wave_bytes<P>() <= split_lds_bytes<NREP, EPI, P>(), "epilogue records do not fit in LDS");
+        constexpr int PARK0 = SWAVES * spl_wave_bytes<P>();          // the parked accumulators: behind the records, a region per wave
+        static_assert(PARK0 + SWAVES * spl_park_wave_bytes<P>() <= split_lds_bytes<NREP, EPI, P>() &&
+                      split_lds_bytes<NREP, EPI, P>() <= 160 * 1024, "epilogue records and parked accumulators do not fit in LDS");
         __syncthreads();                        // every wave is done with the operand stages: LDS is reused below
-        split_spline_epilogue<KSPL, P, EPI == EPI_SPLINE_IDB, SAVE>(g, acc, rs, nt, n0, wrow0, lane, (float*)(slds + wave * spl_wave_bytes<P>()));
+        split_spline_epilogue<KSPL, P, EPI == EPI_SPLINE_IDB, SAVE>(g, acc, rs, nt, n0, wrow0, lane, (float*)(slds + wave * spl_wave_bytes<P>()),
+                                                                   (f32x4_alias*)(slds + PARK0 + wave * spl_park_wave_bytes<P>()) + lane);
     } else if constexpr (EPI == EPI_ELU_SPLIT) {
         // y = ELU(x W^T + b) written straight as split rows for the next GEMM.  The row scale cannot wait for the row
         // maximum (other workgroups hold the other columns), so it comes from a bound every workgroup can compute:
