@@ -1380,6 +1380,89 @@ typedef struct tfep_egnn_node_bwd_args {
 } tfep_egnn_node_bwd_args;
 int tfep_egnn_node_backward(const tfep_egnn_node_bwd_args* args, void* stream);
 
+/*
+ * Parameter gradients of <g, velocity> (csrc/egnn_param_grad.hip): separate passes beside the reverse pass above, fed with
+ * the layer inputs the forward pass saved and the cotangents the reverse pass produced.  Every pass runs on a grid of
+ * tfep_egnn_param_grad_workgroups(items, max_workgroups) workgroups; workgroup w walks the contiguous items
+ * [w items / W, (w + 1) items / W), sums in fp32 (the matrix-sized sums on v_mfma_f32_16x16x4_f32; the edge pass per
+ * item, adding every item's sums to its set as doubles) and leaves ONE partial set of
+ * tfep_egnn_param_grad_partial_entries(nt, kind) doubles at partials + w * that.  tfep_egnn_param_grad_reduce adds
+ * the partial sets in workgroup order in fp64, rounds once and un-pads into tensors of the parameters' own shapes.  No
+ * atomics: bit-reproducible.  kind: 0 the edge pass, 1 / 2 the two parts of the node pass.
+ */
+int tfep_egnn_param_grad_workgroups(int64_t items, int max_workgroups);      /* max_workgroups 0: 2 x the CU count */
+int64_t tfep_egnn_param_grad_partial_entries(int nt, int kind);               /* -1 for a bad nt / kind */
+int64_t tfep_egnn_param_grad_struct_bytes(int which);    /* sizeof of the three argument structs below, in order; else -1 */
+
+/*
+ * Edge pass of one layer (items: the (sample, block of 16 destinations) pairs, B ceil(n / 16)): the edge chain is
+ * recomputed as by tfep_egnn_edge_backward with src_owned = 0 (same arguments, same `split` arithmetic for the recompute;
+ * the gradient products are exact fp32) and summed over the live edges into
+ *   g_z3 (x) m -> update_x_mlp.0.weight, sum g_z3 -> its bias, g_s silu(z3) -> update_x_mlp.2.weight,
+ *   g_e a2 -> attention_mlp.0.weight, sum g_e -> its bias, g_z2 (x) silu(z1) -> message_mlp.2.weight, sum g_z2 -> its bias,
+ *   g_z1 (x) rbf -> message_mlp.0.weight[:, 2F:], g_rbf d rbf / d log gamma -> distance_embedding._log_gammas.
+ */
+typedef struct tfep_egnn_edge_param_grad_args {
+    int32_t B, n_nodes, nt, split, max_workgroups;
+    float r_cutoff, speed_factor;
+    const float* packed;
+    const float* pos;
+    const float* P;
+    const float* Q;
+    int64_t pq_bstride;
+    const float* g_pos_out;
+    const float* g_nm;              /* NULL = zero: last layer */
+    double* partials;               /* workgroups x partial_entries(nt, 0) doubles */
+} tfep_egnn_edge_param_grad_args;
+int tfep_egnn_edge_param_grad(const tfep_egnn_edge_param_grad_args* args, void* stream);
+
+/*
+ * Node pass between layer l and l + 1 (items: groups of 16 nodes of the (B n) rows), arguments as
+ * tfep_egnn_node_backward BEFORE it runs (g_h_next still the cotangent of h').  part 0 (kind 1): g_P (x) h', g_Q (x) h',
+ * sum g_Q -> message_mlp.0.{weight[:, :F], weight[:, F:2F], bias} of layer l + 1, h' = h_next, the saved input of layer
+ * l + 1.  part 1 (kind 2): update_h_mlp.{0,2}.{weight,bias} of layer l, its hidden activation recomputed from h, nm.
+ */
+typedef struct tfep_egnn_node_param_grad_args {
+    int32_t B, n_nodes, nt, part, max_workgroups;
+    const float* packed;
+    const float* packed_next;
+    const float* h;
+    int64_t h_bstride;
+    const float* nm;
+    const float* h_next;
+    const float* g_h_next;          /* NULL = zero */
+    const float* g_P;
+    const float* g_Q;
+    double* partials;               /* workgroups x partial_entries(nt, 1 + part) doubles */
+} tfep_egnn_node_param_grad_args;
+int tfep_egnn_node_param_grad(const tfep_egnn_node_param_grad_args* args, void* stream);
+
+/* Gradient tensors of one _EGLayer, shapes of tfep_egnn_layer_params; NULL: not written. */
+typedef struct tfep_egnn_layer_grads {
+    int32_t F, G;
+    float* dist_log_gammas;
+    float* msg0_w;
+    float* msg0_b;
+    float* msg2_w;
+    float* msg2_b;
+    float* att_w;
+    float* att_b;
+    float* ux0_w;
+    float* ux0_b;
+    float* ux2_w;
+    float* uh0_w;
+    float* uh0_b;
+    float* uh2_w;
+    float* uh2_b;
+} tfep_egnn_layer_grads;
+/* kind 0 writes dist_log_gammas, msg0_w[:, 2F:], msg2_*, att_*, ux*; kind 1 msg0_w[:, :2F], msg0_b; kind 2 uh*. */
+typedef struct tfep_egnn_param_grad_reduce_args {
+    int32_t n_partials, nt, kind;
+    const double* partials;
+    tfep_egnn_layer_grads grads;
+} tfep_egnn_param_grad_reduce_args;
+int tfep_egnn_param_grad_reduce(const tfep_egnn_param_grad_reduce_args* args, void* stream);
+
 /* out = sign (in - mean over the nodes), per sample and component, (B, 3 n_nodes): the centring of the velocity
  * (egnn.py:187-191) and, being a symmetric projector, its own reverse pass. */
 int tfep_egnn_center(const float* in, int B, int n_nodes, float sign, float* out, void* stream);

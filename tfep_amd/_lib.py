@@ -129,6 +129,30 @@ class EgnnNodeBwdArgs(Structure):
                 ('g_Q', c_void_p), ('g_h', c_void_p), ('g_nm', c_void_p)]
 
 
+class EgnnEdgeParamGradArgs(Structure):
+    _fields_ = [('B', c_int32), ('n_nodes', c_int32), ('nt', c_int32), ('split', c_int32), ('max_workgroups', c_int32),
+                ('r_cutoff', c_float), ('speed_factor', c_float), ('packed', c_void_p), ('pos', c_void_p),
+                ('P', c_void_p), ('Q', c_void_p), ('pq_bstride', c_int64), ('g_pos_out', c_void_p), ('g_nm', c_void_p),
+                ('partials', c_void_p)]
+
+
+class EgnnNodeParamGradArgs(Structure):
+    _fields_ = [('B', c_int32), ('n_nodes', c_int32), ('nt', c_int32), ('part', c_int32), ('max_workgroups', c_int32),
+                ('packed', c_void_p), ('packed_next', c_void_p), ('h', c_void_p), ('h_bstride', c_int64), ('nm', c_void_p),
+                ('h_next', c_void_p), ('g_h_next', c_void_p), ('g_P', c_void_p), ('g_Q', c_void_p), ('partials', c_void_p)]
+
+
+class EgnnLayerGrads(Structure):
+    _fields_ = [('F', c_int32), ('G', c_int32)] + [(k, c_void_p) for k in (
+        'dist_log_gammas', 'msg0_w', 'msg0_b', 'msg2_w', 'msg2_b', 'att_w', 'att_b', 'ux0_w', 'ux0_b', 'ux2_w', 'uh0_w',
+        'uh0_b', 'uh2_w', 'uh2_b')]
+
+
+class EgnnParamGradReduceArgs(Structure):
+    _fields_ = [('n_partials', c_int32), ('nt', c_int32), ('kind', c_int32), ('partials', c_void_p),
+                ('grads', EgnnLayerGrads)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     'tfep_hip_abi_version': (c_int, []),
@@ -219,6 +243,12 @@ _SIGNATURES = {
     'tfep_egnn_finish': (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, c_float, _P, _P, _P, _P]),
     'tfep_egnn_edge_backward': (c_int, [POINTER(EgnnEdgeBwdArgs), _P]),
     'tfep_egnn_node_backward': (c_int, [POINTER(EgnnNodeBwdArgs), _P]),
+    'tfep_egnn_param_grad_workgroups': (c_int, [c_int64, c_int]),
+    'tfep_egnn_param_grad_partial_entries': (c_int64, [c_int, c_int]),
+    'tfep_egnn_param_grad_struct_bytes': (c_int64, [c_int]),
+    'tfep_egnn_edge_param_grad': (c_int, [POINTER(EgnnEdgeParamGradArgs), _P]),
+    'tfep_egnn_node_param_grad': (c_int, [POINTER(EgnnNodeParamGradArgs), _P]),
+    'tfep_egnn_param_grad_reduce': (c_int, [POINTER(EgnnParamGradReduceArgs), _P]),
     'tfep_egnn_center': (c_int, [_P, c_int, c_int, c_float, _P, _P]),
     'tfep_row_dots': (c_int, [_P, _P, c_int, c_int, c_float, _P, _P, _P]),
     'tfep_radial_expansion': (c_int, [_P, c_int64, _P, _P, c_int, c_float, c_int, c_int, _P, _P]),

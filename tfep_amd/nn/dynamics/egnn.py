@@ -51,6 +51,14 @@ class EGNNDynamics(FixedGraph):
     """Velocity field of a continuous normalizing flow (Satorras et al. 2021, as varied by tfep).  Arguments as
     reference egnn.py:73-128."""
 
+    #: Opt-in first-order autograd on the kernels.  False (default): under grad mode ``forward`` is ``torch_forward``,
+    #: differentiable to any order at the dense route's memory.  True: ``forward`` under grad mode returns the kernels'
+    #: velocity from an autograd function whose backward is ``vjp_parameters`` -- gradients for ``x`` and every parameter
+    #: the velocity depends on at the memory of ``vjp``, differentiable ONCE (a second backward raises and names this
+    #: switch).  Enough for losses that are functions of the velocity.  A ``ContinuousFlow`` differentiates a trace of the
+    #: Jacobian, second derivatives: its integrands keep calling ``torch_forward`` whatever this flag says.
+    kernel_backward = False
+
     def __init__(
         self,
         node_types,
@@ -83,6 +91,8 @@ class EGNNDynamics(FixedGraph):
     def forward(self, t, x):
         """Velocity ``(batch_size, n_nodes*3)`` at time ``t`` and positions ``x``."""
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if self.kernel_backward and self.kernels_supported():
+                return self._kernel_forward(t, x)              # the kernels, differentiable ONCE: see kernel_backward
             return self.torch_forward(t, x)                    # differentiable (to any order): see there
         if not self.kernels_supported():
             return self.torch_forward(t, x)                    # widths beyond the kernels' 64: the same map, slower
@@ -312,8 +322,10 @@ class EGNNDynamics(FixedGraph):
         return vel, jv
 
 
-def _run_vjp(self, t, x, g, trace=None, frob=None, scale=1.0, vel_sq=None):
-    """Forward pass keeping every layer's inputs, then the reverse pass (see ``EGNNDynamics.vjp``)."""
+def _run_vjp(self, t, x, g, trace=None, frob=None, scale=1.0, vel_sq=None, param_grads=None):
+    """Forward pass keeping every layer's inputs, then the reverse pass (see ``EGNNDynamics.vjp``).  ``param_grads``: a
+    ``_ParamGrads`` collector -- the parameter-gradient passes run beside the reverse sweep, whose own launches and
+    arguments are the same with and without it."""
     _lib.check_device_tensor(x, 'x')
     _lib.check_device_tensor(g, 'g')
     x, g = x.contiguous(), g.contiguous()
@@ -410,6 +422,11 @@ def _run_vjp(self, t, x, g, trace=None, frob=None, scale=1.0, vel_sq=None):
             a.g_lane = work[0 if src_owned else 1].data_ptr()     # sources: g_P; destinations: g_Q
             a.g_pos = g_pos.data_ptr()
             _lib.call('tfep_egnn_edge_backward', ctypes.byref(a), stream)
+        if param_grads is not None:
+            # (before the node reverse pass below overwrites g_h / g_nm with those of the layer before)
+            param_grads.edge(li, a, g_nm)
+            if li > 0:
+                param_grads.node(li, packed, H, NM, bstride, g_h, work)
         g_pos_out = g_pos
         if li > 0:
             nb = _lib.EgnnNodeBwdArgs()
@@ -429,8 +446,178 @@ def _run_vjp(self, t, x, g, trace=None, frob=None, scale=1.0, vel_sq=None):
     _lib.call('tfep_ode_axpy', _lib.ptr(g_pos_out), ptrs, coef, 1, g_pos_out.numel(), _lib.ptr(out), stream)
     if trace is not None or frob is not None:
         _lib.call('tfep_row_dots', _lib.ptr(out), _lib.ptr(g), B, D, float(scale), _lib.ptr(trace), _lib.ptr(frob), stream)
+    if param_grads is not None:
+        param_grads.embedding(t, emb[0], work, L > 1)
     del keep
     return vel, out
 
 
 EGNNDynamics._run_vjp = _run_vjp
+
+
+# ---------------------------------------------------------------------- parameter gradients (csrc/egnn_param_grad.hip)
+#: ctypes field of ``EgnnLayerGrads`` -> parameter name inside one ``graph_layer_{i}``
+_LAYER_GRAD_FIELDS = dict(
+    dist_log_gammas='distance_embedding._log_gammas', msg0_w='message_mlp.0.weight', msg0_b='message_mlp.0.bias',
+    msg2_w='message_mlp.2.weight', msg2_b='message_mlp.2.bias', att_w='attention_mlp.0.weight',
+    att_b='attention_mlp.0.bias', ux0_w='update_x_mlp.0.weight', ux0_b='update_x_mlp.0.bias',
+    ux2_w='update_x_mlp.2.weight', uh0_w='update_h_mlp.0.weight', uh0_b='update_h_mlp.0.bias',
+    uh2_w='update_h_mlp.2.weight', uh2_b='update_h_mlp.2.bias')
+
+
+class _ParamGrads:
+    """The parameter-gradient passes of one reverse sweep: called by ``_run_vjp`` per layer with the tensors it holds at
+    that moment; ``grads`` maps every ``named_parameters()`` name to a float32 tensor of the parameter's shape (zeros
+    where the velocity does not depend on the parameter: the last layer's ``update_h_mlp``)."""
+
+    def __init__(self, dyn, x, max_workgroups):
+        self.dyn, self.max_workgroups = dyn, int(max_workgroups)
+        self.dev, self.stream = x.device, _lib.stream_of(x)
+        self.grads = {k: torch.zeros(p.shape, dtype=torch.float32, device=x.device) for k, p in dyn.named_parameters()}
+
+    def _reduce(self, li, kind, nt, partials):
+        r = _lib.EgnnParamGradReduceArgs()
+        r.n_partials, r.nt, r.kind, r.partials = partials.shape[0], nt, kind, partials.data_ptr()
+        r.grads.F, r.grads.G = self.dyn._dims[1], self.dyn._dims[2]
+        for field, name in _LAYER_GRAD_FIELDS.items():
+            setattr(r.grads, field, self.grads[f'graph_layer_{li}.{name}'].data_ptr())
+        _lib.call('tfep_egnn_param_grad_reduce', ctypes.byref(r), self.stream)
+
+    def _partials(self, items, nt, kind):
+        lib = _lib.load()
+        return torch.empty(lib.tfep_egnn_param_grad_workgroups(items, self.max_workgroups),
+                           lib.tfep_egnn_param_grad_partial_entries(nt, kind), dtype=torch.float64, device=self.dev)
+
+    def edge(self, li, bwd, g_nm):
+        """Layer ``li``'s edge pass, from the arguments of its reverse edge pass."""
+        partials = self._partials(bwd.B * ((bwd.n_nodes + 15) // 16), bwd.nt, 0)
+        a = _lib.EgnnEdgeParamGradArgs()
+        for k in ('B', 'n_nodes', 'nt', 'split', 'r_cutoff', 'speed_factor', 'packed', 'pos', 'P', 'Q', 'pq_bstride',
+                  'g_pos_out'):
+            setattr(a, k, getattr(bwd, k))
+        a.max_workgroups = self.max_workgroups
+        a.g_nm = g_nm.data_ptr() if g_nm is not None else None
+        a.partials = partials.data_ptr()
+        _lib.call('tfep_egnn_edge_param_grad', ctypes.byref(a), self.stream)
+        self._reduce(li, 0, bwd.nt, partials)
+
+    def node(self, li, packed, H, NM, bstride, g_h, work):
+        """The node update between layer ``li - 1`` and ``li``: the node columns of layer ``li``'s first message linear
+        (part 0) and layer ``li - 1``'s ``update_h_mlp`` (part 1)."""
+        _, B, n, fp = work.shape
+        nt = fp // 16
+        for part in (0, 1):
+            partials = self._partials((B * n + 15) // 16, nt, 1 + part)
+            a = _lib.EgnnNodeParamGradArgs()
+            a.B, a.n_nodes, a.nt, a.part, a.max_workgroups = B, n, nt, part, self.max_workgroups
+            a.packed, a.packed_next = packed[li - 1].data_ptr(), packed[li].data_ptr()
+            a.h, a.h_bstride, a.nm = H[li - 1].data_ptr(), bstride[li - 1], NM[li - 1].data_ptr()
+            a.h_next = H[li].data_ptr()
+            a.g_h_next = g_h.data_ptr() if g_h is not None else None
+            a.g_P, a.g_Q = work[0].data_ptr(), work[1].data_ptr()
+            a.partials = partials.data_ptr()
+            _lib.call('tfep_egnn_node_param_grad', ctypes.byref(a), self.stream)
+            self._reduce(li if part == 0 else li - 1, 1 + part, nt, partials)
+
+    def embedding(self, t, h0, work, have_g_h):
+        """Layer 0's inputs are the shared embedding: their cotangents summed over the batch (float64, fixed order), then
+        ``O(n F)`` float64 expressions for layer 0's node columns, ``h_embedding`` and the time embedding's widths."""
+        dyn, f64 = self.dyn, torch.float64
+        _, F, _ = dyn._dims
+        g_P, g_Q = (torch.sum(work[k], dim=0, dtype=f64)[:, :F] for k in (0, 1))
+        h0 = h0[:, :F].to(f64)
+        msg0 = dyn.graph_layer_0.message_mlp[0]
+        w0 = msg0.weight.detach().to(device=self.dev, dtype=f64)
+        gw0 = self.grads['graph_layer_0.message_mlp.0.weight']
+        gw0[:, :F] = (g_P.T @ h0).float()
+        gw0[:, F:2 * F] = (g_Q.T @ h0).float()
+        self.grads['graph_layer_0.message_mlp.0.bias'].copy_(g_Q.sum(0))
+        g_h0 = g_P @ w0[:, :F] + g_Q @ w0[:, F:2 * F]
+        if have_g_h:
+            g_h0 = g_h0 + torch.sum(work[2], dim=0, dtype=f64)[:, :F]
+        te = dyn.time_embedding
+        mu, lg = (p.detach().to(device=self.dev, dtype=f64) for p in (te._means, te._log_gammas))
+        t_emb = torch.exp(-torch.exp(lg) * (t - mu) ** 2)
+        one_hot = dyn._node_types_one_hot.detach().to(device=self.dev, dtype=f64)
+        feat = torch.cat([one_hot, t_emb[None].expand(one_hot.shape[0], -1)], dim=-1)
+        self.grads['h_embedding.weight'].copy_(g_h0.T @ feat)
+        self.grads['h_embedding.bias'].copy_(g_h0.sum(0))
+        if isinstance(te._log_gammas, torch.nn.Parameter):
+            w_t = dyn.h_embedding.weight.detach().to(device=self.dev, dtype=f64)[:, one_hot.shape[1]:]
+            g_t = (g_h0 @ w_t).sum(0)
+            self.grads['time_embedding._log_gammas'].copy_(g_t * t_emb * (-torch.exp(lg) * (t - mu) ** 2))
+
+
+def _unused_parameter_names(self):
+    """The parameters the velocity does not depend on: the last layer updates no features anybody reads."""
+    last = f'graph_layer_{self._n_layers - 1}.update_h_mlp.'
+    return {k for k, _ in self.named_parameters() if k.startswith(last)}
+
+
+def vjp_parameters(self, t, x, g, max_workgroups=0):
+    """``(velocity, g^T J, grads)``: ``vjp(t, x, g)`` and, from the same reverse sweep, the gradient of
+    ``<g, velocity(t, x; theta)>`` with respect to every parameter -- ``grads`` is keyed like
+    ``dict(self.named_parameters())``, float32, each of its parameter's shape (exact zeros for the last layer's
+    ``update_h_mlp``, which the velocity does not depend on).  Memory: that of ``vjp`` plus a partials buffer that does not
+    grow with the batch.  ``max_workgroups`` (0: the library's default) caps the grids of the gradient passes; it regroups
+    their fp32 sums and nothing else.  Results are bit-reproducible from run to run."""
+    _lib.check_device_tensor(x, 'x')
+    _lib.check_device_tensor(g, 'g')
+    if x.dim() != 2 or x.shape[1] != 3 * self.n_nodes or g.shape != x.shape:
+        raise ValueError(f'x and g must have shape (batch_size, {3 * self.n_nodes})')
+    self._tile()
+    pg = _ParamGrads(self, x, max_workgroups)
+    if x.shape[0] == 0:
+        return torch.empty_like(x), torch.empty_like(x), pg.grads
+    vel, gx = self._run_vjp(t, x, g, param_grads=pg)
+    return vel, gx, pg.grads
+
+
+class _KernelVelocity(torch.autograd.Function):
+    """``forward`` on the kernels with a first-order backward from ``vjp_parameters`` (``kernel_backward = True``)."""
+
+    SECOND_ORDER_MESSAGE = ('EGNNDynamics.kernel_backward = True gives first derivatives only (the backward runs on the HIP '
+                            'kernels and is differentiable once); set kernel_backward = False for the double-differentiable '
+                            'torch route (torch_forward)')
+
+    @staticmethod
+    def forward(ctx, dyn, t, x, names, *params):
+        ctx.dyn, ctx.t, ctx.names = dyn, float(t), names
+        ctx.save_for_backward(x)
+        return dyn._run(t, x.detach())[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        dyn = ctx.dyn
+        with torch.no_grad():
+            _, gx, grads = dyn.vjp_parameters(ctx.t, x, g.detach().contiguous())
+        unused = _unused_parameter_names(dyn)
+        outs = [gx if ctx.needs_input_grad[2] else None]
+        outs += [grads[k] if (need and k not in unused) else None for k, need in zip(ctx.names, ctx.needs_input_grad[4:])]
+        if torch.is_grad_enabled():            # create_graph: what once_differentiable does, with a message that says where to go
+            live = [i for i, o in enumerate(outs) if o is not None]
+            marked = _OnceDifferentiable.apply(torch.zeros((), device=x.device, requires_grad=True), *[outs[i] for i in live])
+            for i, o in zip(live, marked[1:]):
+                outs[i] = o
+        return (None, None, outs[0], None, *outs[1:])
+
+
+class _OnceDifferentiable(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flag, *tensors):
+        return (flag.clone(), *[v.clone() for v in tensors])
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise RuntimeError(_KernelVelocity.SECOND_ORDER_MESSAGE)
+
+
+def _kernel_forward(self, t, x):
+    _lib.check_device_tensor(x, 'x')
+    names, params = zip(*self.named_parameters())
+    return _KernelVelocity.apply(self, t, x, names, *params)
+
+
+EGNNDynamics.vjp_parameters = vjp_parameters
+EGNNDynamics._kernel_forward = _kernel_forward

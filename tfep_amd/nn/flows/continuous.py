@@ -190,7 +190,9 @@ class _ODEFunc(torch.nn.Module):
         with torch.enable_grad():
             if not x.requires_grad:
                 x = x.detach().requires_grad_(True) if not create_graph else x.requires_grad_(True)
-            vel = self.dynamics(t, x)
+            dyn = self.dynamics
+            # (the trace below is differentiated a second time: never the first-order ``kernel_backward`` route)
+            vel = dyn.torch_forward(t, x) if getattr(dyn, 'kernel_backward', False) else dyn(t, x)
             if self._trace_estimator == self.TraceEstimators.hutchinson:
                 rows = torch.stack([torch.autograd.grad(vel, x, e, create_graph=create_graph, retain_graph=True)[0]
                                     for e in self._eps])                         # e^T J per noise sample
