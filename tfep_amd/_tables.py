@@ -1,6 +1,7 @@
 """The integer tables that the kernels cannot validate, prepared on the host in pure torch (no library, no GPU): one integer
-check, one range check, one ``incidence`` builder and one ``Cache`` class, then the index tables of ``internal_coordinates``,
-the level-sorted Z-matrix of ``zmatrix_place`` and the node-incidence list of ``edge_geometry_backward`` built on them."""
+check, one range check, one ``incidence`` builder, the degree-sorted packing order of the MAF layers (``stable_order``,
+``packed_rows``) and one ``Cache`` class, then the index tables of ``internal_coordinates``, the level-sorted Z-matrix of
+``zmatrix_place`` and the node-incidence list of ``edge_geometry_backward`` built on them."""
 import collections
 
 import torch
@@ -35,6 +36,31 @@ def incidence(keys, n_bins):
     start = torch.zeros(n_bins + 1, dtype=torch.int64, device=keys.device)
     start[1:] = torch.cumsum(torch.bincount(keys, minlength=n_bins), 0)
     return start, order
+
+
+def stable_order(degrees):
+    """``(order, position)`` of a degree vector (torch, numpy or a list) as CPU int64 tensors: ``order[p]`` = the unit at packed
+    position ``p`` (stable sort by degree), ``position[u]`` = the packed position (the slot) of unit ``u``.  THE order of every
+    degree-sorted packing: hidden units (``MADE.plan``), output rows (``packed_rows``), the float64 blocked inverse."""
+    degrees = torch.as_tensor(degrees).detach().to('cpu', torch.int64)
+    order = torch.argsort(degrees, stable=True)
+    position = torch.empty_like(order)
+    position[order] = torch.arange(len(order))
+    return order, position
+
+
+def packed_rows(position, P_real, P, tiling=None):
+    """Packed row of every output row ``o = p * n + t`` (parameter ``p < P_real`` of feature ``t`` in slot ``position[t]``) of a
+    MADE output layer packed feature-major in slot order, ``P`` parameter rows per slot (``P_real < P``: the others stay
+    zero).  No ``tiling``: row ``slot * P + p`` (the backward).  ``tiling = (FT, tile_cols)``: the fused kernels' column tiles
+    of ``FT`` x 16 slots, ``[16 slots][parameter][slot]`` inside a tile, relative to the first tile of the group."""
+    n = len(position)
+    sl = position.repeat(P_real)
+    pp = torch.arange(P_real).repeat_interleave(n)
+    if tiling is None:
+        return sl * P + pp
+    FT, tile_cols = tiling
+    return (sl // (16 * FT)) * tile_cols + (((sl // 16) % FT) * P + pp) * 16 + sl % 16
 
 
 class Cache:

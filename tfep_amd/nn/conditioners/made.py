@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from ... import ops
+from ..._tables import stable_order
 from ...utils.misc import ensure_tensor_sequence
 from .. import masked
 from .conditioner import Conditioner
@@ -342,10 +343,7 @@ class MADE(Conditioner):
                     deg = self._degrees[li + 1].cpu()
                 else:       # masks of unknown origin: fewer connections first (any order is correct, see k_ranges below)
                     deg = torch.count_nonzero(lin.mask, dim=1).cpu()
-                order = torch.argsort(deg, stable=True)              # packed position -> hidden unit
-                row = torch.empty_like(order)
-                row[order] = torch.arange(len(order), device='cpu')                # hidden unit -> packed position
-                row_of_out = row.to(device=device, dtype=torch.int32)
+                row_of_out = stable_order(deg)[1].to(device=device, dtype=torch.int32)       # hidden unit -> packed position
                 n_pad = ops.round_up(lin.out_features, tk)
             plan['row_of_out'].append(row_of_out)
             plan['col_of_in'].append(col_of_in)

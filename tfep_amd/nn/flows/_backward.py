@@ -22,6 +22,7 @@ import os
 import torch
 
 from ... import _lib, ops
+from ..._tables import packed_rows
 from ..conditioners.made import MADE
 from ..masked import GRAD_IS_MASKED
 from ..embeddings.mafembed import FlipInvariantEmbedding, MAFEmbedding, PeriodicEmbedding
@@ -436,28 +437,18 @@ def _backward_plan(layer, device):
     bp = layer._dev.get(key)
     if bp is not None:
         return bp
-    made = layer._conditioner
-    mplan = made.plan(device)
+    mplan, lins, L, n_out, n_out_pad, n_pad, k_pad = _dims(layer, device)
     tm, tn, tk = ops.tile_sizes()
-    lins = made._linears()
-    L = len(lins) - 1
-    tables = layer._tables(device)
-    n_tr = tables['n_tr']
-    n_out = lins[-1].out_features
+    n_tr = layer._tables(device)['n_tr']
     P = n_out // n_tr
     i32 = dict(device=device, dtype=torch.int32)
     bp = dict(sorted_out=type(layer._transformer) in (AffineTransformer, NeuralSplineTransformer, SOSPolynomialTransformer))
     k_ranges = list(mplan['k_ranges'])
     if bp['sorted_out']:
-        deg_tr = made._degrees[-1][:n_tr].cpu()
-        order = torch.argsort(deg_tr, stable=True)                 # slot -> transformed feature
-        slot_of = torch.empty_like(order)
-        slot_of[order] = torch.arange(n_tr, device='cpu')
-        p = torch.arange(P, device='cpu').repeat_interleave(n_tr)
-        row_of_out = (slot_of.repeat(P) * P + p).to(**i32)         # row of reference output o = p*n_tr + t
+        order, slot_of = layer._slot_order(0, n_tr)                # slot -> transformed feature, and back
+        row_of_out = packed_rows(slot_of, P, P).to(**i32)          # row of reference output o = p*n_tr + t
         bp.update(order=order.to(**i32), row_of_out=row_of_out)
-        n_out_pad = ops.round_up(n_out, tk)
-        k_ranges[L] = ops.mask_k_ranges(lins[L].mask, tn, (n_out_pad + tn - 1) // tn, mplan['k_pad'][L], row_of_out,
+        k_ranges[L] = ops.mask_k_ranges(lins[L].mask, tn, (n_out_pad + tn - 1) // tn, k_pad[L], row_of_out,
                                         mplan['col_of_in'][L])
     bp['k_ranges'] = k_ranges
     use_list = os.environ.get('TFEP_TILE_LIST', '1') != '0'
@@ -468,9 +459,7 @@ def _backward_plan(layer, device):
         dx_ranges, live, live_list = [], [], []
         for li, lin in enumerate(lins):
             kr = k_ranges[li].cpu().long()                            # per 256-row tile of W: [kb, ke)
-            n_pad = ops.round_up(lin.out_features, tk) if li == L else mplan['n_pad'][li]
-            k_pad = mplan['k_pad'][li]
-            n_col_tiles = (k_pad + col_width - 1) // col_width
+            n_col_tiles = (k_pad[li] + col_width - 1) // col_width
             lo = torch.arange(n_col_tiles) * col_width
             hi = lo + col_width
             hit = (kr[:, 0:1] < hi[None, :]) & (kr[:, 1:2] > lo[None, :])          # (row tiles, col tiles)
@@ -483,7 +472,7 @@ def _backward_plan(layer, device):
                 rows = torch.nonzero(hit[:, j]).flatten()
                 if len(rows):
                     rng[j, 0] = int(rows.min()) * tn
-                    rng[j, 1] = min((int(rows.max()) + 1) * tn, n_pad)
+                    rng[j, 1] = min((int(rows.max()) + 1) * tn, n_pad[li])
             dx_ranges.append(rng.to(device))
         return dict(dx_ranges=dx_ranges, live=live, live_list=live_list)
 
@@ -496,8 +485,7 @@ def _backward_plan(layer, device):
         wide = tables(tw)
         wide['tile_n'] = tw
         row_of_out = bp.get('row_of_out', mplan['row_of_out'][L])
-        n_out_pad = ops.round_up(n_out, tk)
-        wide['k_ranges_out'] = ops.mask_k_ranges(lins[L].mask, tw, (n_out_pad + tw - 1) // tw, mplan['k_pad'][L], row_of_out,
+        wide['k_ranges_out'] = ops.mask_k_ranges(lins[L].mask, tw, (n_out_pad + tw - 1) // tw, k_pad[L], row_of_out,
                                                  mplan['col_of_in'][L])
         bp['wide'] = wide
     layer._dev[key] = bp
@@ -573,17 +561,25 @@ def _weights(layer, dev):
     return wts
 
 
+def _hidden_forward(layer, wts, cin, Bc):
+    """Hidden activations of the conditioner on the packing of ``wts``: ``h[0]`` = the zero-padded conditioner input."""
+    dev = cin.device
+    mplan, lins, L, n_out, n_out_pad, n_pad, k_pad = _dims(layer, dev)
+    h = [ops.pad_columns(cin, k_pad[0])]
+    for l in range(L):
+        h.append(ops.gemm(h[-1], wts['W'][l], torch.empty(Bc, n_pad[l], dtype=torch.float32, device=dev), Bc, n_pad[l], n_pad[l],
+                          bias=wts['bias'][l], k_ranges=mplan['k_ranges'][l], act=1, split=wts['split'], w_split=wts['Ws'][l]))
+    return h
+
+
 def _conditioner_forward(layer, wts, cin, Bc):
-    """Hidden activations (``h[0]`` = the zero-padded conditioner input) and transformer parameters, backward row order."""
+    """Hidden activations (``_hidden_forward``) and transformer parameters, backward row order."""
     dev = cin.device
     mplan, lins, L, n_out, n_out_pad, n_pad, k_pad = _dims(layer, dev)
     bplan = _backward_plan(layer, dev)
     f32 = dict(dtype=torch.float32, device=dev)
     split = wts['split']
-    h = [ops.pad_columns(cin, k_pad[0])]
-    for l in range(L):
-        h.append(ops.gemm(h[-1], wts['W'][l], torch.empty(Bc, n_pad[l], **f32), Bc, n_pad[l], n_pad[l], bias=wts['bias'][l],
-                          k_ranges=mplan['k_ranges'][l], act=1, split=split, w_split=wts['Ws'][l]))
+    h = _hidden_forward(layer, wts, cin, Bc)
     theta = torch.empty(Bc, n_out_pad, **f32)
     wide = bplan['wide'] if split else None
     ops.gemm(h[-1], wts['W'][L], theta, Bc, n_out_pad, n_pad[L], bias=wts['bias'][L],
@@ -636,15 +632,12 @@ def _fused_saving_plan(layer, dev):
     bplan = _backward_plan(layer, dev)
     if type(layer._transformer) is NeuralSplineTransformer and bplan['sorted_out'] and layer._fused_kind() == _FUSED_SPLINE \
             and os.environ.get('TFEP_FUSED_SAVING', '1') != '0':
-        made = layer._conditioner
         mplan, lins, L, n_out, n_out_pad, n_pad, k_pad = _dims(layer, dev)
+        # (the group's slots and the backward's rows are one order: ``layer._slot_order``)
         grp = layer._fused_plan(dev, _FUSED_SPLINE, layer._tables(dev))['groups'][0]
         P = grp['P']
-        n_tr = layer._tables(dev)['n_tr']
-        # the fused plan and the backward sort the features the same way (stable argsort of their degrees)
-        same = torch.equal(grp['feat_tr'][:n_tr].cpu().long(), bplan['order'].cpu().long())
         desc = layer._transformer.config(dev).desc
-        if same and P * n_tr == n_out and _lib.load().tfep_fused_saving_supported(ctypes.byref(desc)):
+        if P * layer._tables(dev)['n_tr'] == n_out and _lib.load().tfep_fused_saving_supported(ctypes.byref(desc)):
             n_tiles = grp['n_slots'] // 16
             k_ranges = ops.mask_k_ranges(lins[L].mask, 16 * P, n_tiles, k_pad[L], bplan['row_of_out'], mplan['col_of_in'][L])
             plan = dict(grp=grp, P=P, k_ranges=k_ranges, tile_order=ops.heavy_first_order(k_ranges))
@@ -672,10 +665,7 @@ def forward_saving(layer, x):
     fs = _fused_saving_plan(layer, dev) if wts['split'] else None
     if fs is not None:
         f32 = dict(dtype=torch.float32, device=dev)
-        h = [ops.pad_columns(cin, k_pad[0])]
-        for l in range(L):
-            h.append(ops.gemm(h[-1], wts['W'][l], torch.empty(B, n_pad[l], **f32), B, n_pad[l], n_pad[l], bias=wts['bias'][l],
-                              k_ranges=mplan['k_ranges'][l], act=1, split=True, w_split=wts['Ws'][l]))
+        h = _hidden_forward(layer, wts, cin, B)
         hs, h_inv = ops.split_rows(h[-1], h[-1].shape[1])
         theta = torch.empty(B, n_out_pad, **f32)
         if n_out_pad > n_out:

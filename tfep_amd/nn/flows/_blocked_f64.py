@@ -18,6 +18,8 @@ which slots are the components of one vector, for ``tfep_inverse_chain_vec_f64``
 """
 import numpy as np
 
+from ..._tables import stable_order    # noqa: F401  (the one definition of the packing order; callers take it from here too)
+
 ALIGN = 16            # k granularity of tfep_masked_linear_gemm_f64
 STEP_INTS = 16        # ints per degree in the chain kernel's step table
 FEAT_INTS = 8         # ints per feature slot
@@ -25,16 +27,6 @@ MAX_LINEARS = 5       # TFEP_INVERSE_F64_MAX_LINEARS
 MAX_MEMBERS = 4       # TFEP_INVERSE_F64_MAX_MEMBERS
 LDS_LIMIT = 160 * 1024
 ROWS = 64             # sample rows per workgroup of the chain kernel
-
-
-def stable_order(degrees):
-    """``(order, position)``: ``order[p]`` = the unit at packed position ``p`` (stable sort by degree), ``position[u]`` = the
-    packed position of unit ``u``."""
-    degrees = np.asarray(degrees, dtype=np.int64)
-    order = np.argsort(degrees, kind='stable')
-    position = np.empty_like(order)
-    position[order] = np.arange(len(order))
-    return order, position
 
 
 def lds_bytes(n_cols_total, par_cols, max_feats):
@@ -133,7 +125,7 @@ def feature_slots(deg_tr, params_of, member_of=None, local_of=None, member_offse
     deg_tr = np.asarray(deg_tr, dtype=np.int64)
     params_of = np.asarray(params_of, dtype=np.int64)
     n_tr = len(deg_tr)
-    order, _ = stable_order(deg_tr)
+    order = stable_order(deg_tr)[0].numpy()
     p_slot = params_of[order]
     base = np.concatenate([[0], np.cumsum(p_slot)])
     row_of_out = np.full(int(params_of.sum()), -1, dtype=np.int64)

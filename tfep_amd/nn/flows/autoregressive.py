@@ -17,6 +17,7 @@ from typing import Optional, Sequence
 import torch
 
 from ... import _lib, ops
+from ..._tables import packed_rows, stable_order
 from ...utils.misc import ensure_tensor_sequence
 from ..conditioners.made import MADE
 from ..embeddings.mafembed import FlipInvariantEmbedding, MixedEmbedding, PeriodicEmbedding
@@ -104,8 +105,7 @@ class AutoregressiveFlow(torch.nn.Module):
 
     def _sync_conditioner(self):
         """After a ``load_state_dict`` the MADE conditioner re-derives its degrees from the loaded buffers; the input
-        degrees come from this layer's own ``_inverse_masks`` (feature c is transformed at step d iff
-        ``_inverse_masks[d, c]``; every other feature conditions: -1), mapped through the embedding if there is one."""
+        degrees come from this layer's own ``_inverse_masks`` (``_feature_degrees``), through the embedding if there is one."""
         made = self._conditioner
         if isinstance(made, MADE):
             made.begin_call()
@@ -114,12 +114,23 @@ class AutoregressiveFlow(torch.nn.Module):
         self._dev = {}
         hint = None
         if len(self._conditioner_indices) == 0:
-            deg_x = torch.full((self._inverse_masks.shape[1],), -1, dtype=torch.long)
-            for d_, m_ in enumerate(self._inverse_masks.cpu()):
-                deg_x[m_] = d_
+            deg_x = self._feature_degrees()
             emb = getattr(made, 'embedding', None)
             hint = deg_x if emb is None else emb.get_degrees_out(deg_x.to(self._inverse_masks.device)).cpu()
         made._sync_degrees(hint)
+
+    def _feature_degrees(self):
+        """Degrees in x space (CPU int64; ``made._degrees[0]`` is in the conditioner-input space, which an embedding widens):
+        feature c is transformed at step d of the inverse iff ``_inverse_masks[d, c]``, every other feature conditions: -1."""
+        deg_x = torch.full((self._inverse_masks.shape[1],), -1, dtype=torch.long)
+        for d_, m_ in enumerate(self._inverse_masks.cpu()):
+            deg_x[m_] = d_
+        return deg_x
+
+    def _slot_order(self, off, n):
+        """``stable_order`` of the ``n`` transformed features whose parameters start at conditioner output ``off``: the ONE slot
+        order of the fused plan and the backward plan, whose tables ``_backward._fused_saving_plan`` uses together."""
+        return stable_order(self._conditioner._degrees[-1][off:off + n])
 
     # ------------------------------------------------------------------ device-side index tables
     def _tables(self, device):
@@ -283,17 +294,12 @@ class AutoregressiveFlow(torch.nn.Module):
             tile_cols = lib.tfep_fused_tile_columns(k_g, ctypes.byref(desc) if desc is not None else None)
             FT = tile_cols // (16 * P)
             n_slots = ops.round_up(n_g, 16 * FT)
-            deg = made._degrees[-1][off:off + n_g].cpu()
-            order = torch.argsort(deg, stable=True)                # slot -> feature of the group
-            slot_of = torch.empty_like(order)
-            slot_of[order] = torch.arange(n_g, device='cpu')
+            order, slot_of = self._slot_order(off, n_g)            # slot -> feature of the group, and back
             feat_tr = torch.zeros(n_slots, dtype=torch.long, device='cpu')
             feat_tr[:n_g] = order
             feat_index = torch.full((n_slots,), -1, dtype=torch.long, device='cpu')
             feat_index[:n_g] = (cols_tr if rel is None else cols_tr[rel])[order]
-            sl = slot_of.repeat(P_real)                            # slot of output row o = off + p*n_g + t
-            pp = torch.arange(P_real, device='cpu').repeat_interleave(n_g)
-            local = (sl // (16 * FT)) * tile_cols + (((sl // 16) % FT) * P + pp) * 16 + (sl % 16)
+            local = packed_rows(slot_of, P_real, P, (FT, tile_cols))      # of output row o = off + p*n_g + t, in the group
             n_tiles = n_slots // (16 * FT)
             row_of_out[off:off + P_real * n_g] = base + local
             grp = {'kind': k_g, 'transformer': t_g, 'P': P, 'FT': FT, 'n_slots': n_slots, 'n_rows': n_tiles * tile_cols,
@@ -871,12 +877,7 @@ class AutoregressiveFlow(torch.nn.Module):
         tables = self._tables(device)
         deg_in = made._degrees[0].cpu()
         tr_idx = tables['tr'].cpu().long()
-        # degrees in x space (deg_in lives in the conditioner-input space, which an embedding widens): feature c is
-        # transformed at step d of the inverse iff _inverse_masks[d, c]
-        deg_x = torch.full((self._inverse_masks.shape[1],), -1, dtype=torch.long)
-        for d_, m_ in enumerate(self._inverse_masks.cpu()):
-            deg_x[m_] = d_
-        deg_tr = deg_x[tr_idx]
+        deg_tr = self._feature_degrees()[tr_idx]
         n_tr = len(tr_idx)
         P = lins[-1].out_features // n_tr
         max_deg = int(deg_tr.max())
@@ -1805,9 +1806,7 @@ class AutoregressiveFlow(torch.nn.Module):
             return None
         dev0 = self._inverse_masks.device
         D = self._inverse_masks.shape[1]
-        deg_x = torch.full((D,), -1, dtype=torch.long)
-        for d_, m_ in enumerate(self._inverse_masks.cpu()):
-            deg_x[m_] = d_
+        deg_x = self._feature_degrees()
         tr_idx = (self._transformer_indices.cpu() if self.has_fixed_indices else torch.arange(D)).long()
         deg_tr = deg_x[tr_idx]
         n_tr = len(tr_idx)
@@ -1842,9 +1841,9 @@ class AutoregressiveFlow(torch.nn.Module):
         if int(params_of.sum()) != lins[-1].out_features:
             return None
         slot_order, base, row_of_out = bf.feature_slots(deg_tr.numpy(), params_of, member_of, local_of, offsets, counts)
-        order0, pos0 = bf.stable_order(deg_in.numpy())
-        hidden = [bf.stable_order(d.numpy()) for d in degs[1:-1]]
-        deg_cols = [deg_in.numpy()[order0]] + [d.numpy()[o] for d, (o, _) in zip(degs[1:-1], hidden)]
+        order0, pos0 = stable_order(deg_in)
+        hidden = [stable_order(d) for d in degs[1:-1]]
+        deg_cols = [deg_in[order0].numpy()] + [d[o].numpy() for d, (o, _) in zip(degs[1:-1], hidden)]
         plan = bf.fit_block(deg_cols, deg_tr.numpy()[slot_order], params_of[slot_order], G)
         if plan is None:
             return None
@@ -1868,7 +1867,7 @@ class AutoregressiveFlow(torch.nn.Module):
             feats[:, 6:8] = links
         fixed = [int(c) for c in self._fixed_indices.cpu().tolist()]
         plan.update(feats=feats, slot_member=mem[slot_order], slot_local=np.asarray(local_of)[slot_order], members=members,
-                    kinds=kinds, row_of_out=row_of_out, pos0=pos0, hidden_pos=[p for _, p in hidden], limits=limits,
+                    kinds=kinds, row_of_out=row_of_out, pos0=pos0.numpy(), hidden_pos=[p.numpy() for _, p in hidden], limits=limits,
                     fixed_plain=[(c, input_pos(c)) for c in fixed if not periodic[c]],
                     fixed_periodic=[(c, input_pos(c)) for c in fixed if periodic[c]])
         return plan
