@@ -737,6 +737,16 @@ int tfep_symmetrized_moebius_backward_f64(const double* x, int64_t ldx, const do
                                           double max_radius, int inverse, const double* gy, int64_t ldgy,
                                           const double* g_log_det_J, double* gparams, int64_t ldgp, double* gx, int64_t ldgx,
                                           int B, int D, void* stream);
+/* float64 I/O and IEEE division, square root and logarithm; arguments as tfep_moebius_forward / tfep_moebius_backward */
+int tfep_moebius_forward_f64(const double* x, int64_t ldx, const double* params, int64_t ldp,
+                             int dimension, double max_radius, int unit_sphere, int sign,
+                             double* y, int64_t ldy, double* log_det_J, int accumulate,
+                             int B, int D, void* stream);
+int tfep_moebius_backward_f64(const double* x, int64_t ldx, const double* params, int64_t ldp,
+                              int dimension, double max_radius, int unit_sphere, int sign,
+                              const double* gy, int64_t ldgy, const double* g_log_det_J,
+                              double* gparams, int64_t ldgp, double* gx, int64_t ldgx,
+                              int B, int D, void* stream);
 /* float64 I/O, IEEE division and square root */
 int tfep_quaternion_product_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int inverse, double* y,
                                 int64_t ldy, double* log_det_J, int accumulate, int B, int D, void* stream);
@@ -838,14 +848,19 @@ int64_t tfep_inverse_chain_f64_lds_bytes(int n_cols_total, int par_cols, int max
 int tfep_inverse_chain_f64(const tfep_inverse_chain_f64_desc* desc, void* stream);
 
 /*
- * The same chain with vector-valued members: a symmetrized Moebius transformer or a quaternion product, alone or as
- * members of a mixed transformer beside affine / RQ-spline members.  `chain` is read exactly as tfep_inverse_chain_f64
+ * The same chain with vector-valued members: a symmetrized Moebius transformer, a quaternion product or a Moebius
+ * transformer, alone or as members of a mixed transformer beside affine / RQ-spline members.  `chain` is read exactly as tfep_inverse_chain_f64
  * reads its descriptor (every check of that entry point applies; kinds 0 and 1 run on the same device functions, with the
  * same summation order), plus:
  *   member_kind 2  symmetrized Moebius on member_dim[m]-vectors (2 .. 8), 0 < member_max_radius[m] < 1.  One parameter per
  *                  feature (the raw vector w).  log_det_J[b] += log|det J| of the inverse map, once per vector.
  *   member_kind 3  quaternion product: member_dim[m] = 4, scalar last, one parameter per feature (the raw quaternion p);
  *                  x = conj(p / |p|) (x) y.  Adds exactly 0 to log_det_J.
+ *   member_kind 5  Moebius (moebius.py:374-478) on member_dim[m]-vectors (1 .. 8), 0 < member_max_radius[m] < 1, one
+ *                  parameter per feature (the raw vector w): x = the map of y with -w (moebius.py:142-147), and
+ *                  log_det_J[b] += log|det J| of that map, once per vector.
+ *   member_kind 6  the same on the unit sphere (unit_sphere = True: |y| = 1 is the caller's).
+ *   (member_kind 4 is not assigned: it is refused like any unknown kind.)
  * The components of a vector are features of ONE degree; they need not sit in adjacent slots.  The two last ints of a
  * feature record link them:
  *   feats[s][6]    0 for a feature of a scalar member, 1 + i for component i of a vector,

@@ -174,8 +174,6 @@ _SIGNATURES = {
                                     _P, c_int, c_int, c_int, _P]),
     'tfep_spline_inverse': (c_int, [_P, c_int64, _P, ParamLayout, POINTER(SplineDesc), _P, c_int64,
                                     _P, c_int, c_int, c_int, _P]),
-    'tfep_moebius_forward': (c_int, [_P, c_int64, _P, c_int64, c_int, c_float, c_int, c_int,
-                                     _P, c_int64, _P, c_int, c_int, c_int, _P]),
     'tfep_moebius_forward_split_out': (c_int, [_P, c_int64, _P, c_int64, c_float, _P, c_int64, _P, c_int, _P, c_int64, _P,
                                                c_int, c_int, _P]),
     'tfep_periodic_embedding': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_float, c_float,
@@ -224,8 +222,6 @@ _SIGNATURES = {
     'tfep_add_inplace': (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, _P]),
     'tfep_spline_backward': (c_int, [_P, c_int64, _P, ParamLayout, POINTER(SplineDesc), _P, c_int64, _P, _P,
                                      ParamLayout, _P, c_int64, c_int, c_int, _P]),
-    'tfep_moebius_backward': (c_int, [_P, c_int64, _P, c_int64, c_int, c_float, c_int, c_int, _P, c_int64, _P,
-                                      _P, c_int64, _P, c_int64, c_int, c_int, _P]),
     'tfep_copy_2d': (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, _P]),
     'tfep_weight_norm_backward_prefix': (c_int, [_P, c_int64, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     'tfep_periodic_embedding_backward': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_float, c_float, _P, c_int64,
@@ -297,6 +293,10 @@ for _s in ('', '_f64'):
                                                   c_int, _P]),
         'tfep_symmetrized_moebius_backward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, _P,
                                                            c_int64, _P, c_int64, c_int, c_int, _P]),
+        'tfep_moebius_forward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, c_double if _s else c_float, c_int, c_int,
+                                              _P, c_int64, _P, c_int, c_int, c_int, _P]),
+        'tfep_moebius_backward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, c_double if _s else c_float, c_int, c_int, _P,
+                                               c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int, _P]),
         'tfep_quaternion_product' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
         'tfep_quaternion_product_backward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int64, _P, c_int64,
                                                           c_int, c_int, _P]),

@@ -657,16 +657,19 @@ __global__ void __launch_bounds__(WNB_THREADS) weight_norm_backward_prefix_kerne
 }
 
 // ---------------------------------------------------------------- Moebius VJP (moebius.py:374-478)
-// Reverse mode through the closed-form forward of moebius_kernel (transformers.hip); one lane per vector.
+// Reverse mode through the closed-form forward of moebius_kernel (transformers.hip); one lane per vector.  The arithmetic
+// is fp64 with IEEE sqrt and division for both element types T; sign = -1: the VJP of the inverse (the forward map on
+// negated parameters).
 constexpr int MOEBIUS_MAX_DIM_B = 8;
 
-__global__ void __launch_bounds__(256) moebius_backward_kernel(const float* __restrict__ x, int64_t ldx,
-                                                               const float* __restrict__ params, int64_t ldp, int dim,
-                                                               float max_radius, int unit_sphere, float sign,
-                                                               const float* __restrict__ gy, int64_t ldgy,
-                                                               const float* __restrict__ gldj,
-                                                               float* __restrict__ gparams, int64_t ldgp,
-                                                               float* __restrict__ gx, int64_t ldgx, int B, int D) {
+template <typename T>
+__global__ void __launch_bounds__(256) moebius_backward_kernel(const T* __restrict__ x, int64_t ldx,
+                                                               const T* __restrict__ params, int64_t ldp, int dim,
+                                                               T max_radius, int unit_sphere, T sign,
+                                                               const T* __restrict__ gy, int64_t ldgy,
+                                                               const T* __restrict__ gldj,
+                                                               T* __restrict__ gparams, int64_t ldgp,
+                                                               T* __restrict__ gx, int64_t ldgx, int B, int D) {
     const int b = blockIdx.x * ROWS_PER_BLOCK_B + (threadIdx.x >> 6);
     if (b >= B) return;
     const int lane = threadIdx.x & 63;
@@ -757,8 +760,8 @@ __global__ void __launch_bounds__(256) moebius_backward_kernel(const float* __re
                 double wb = s * ub[i];
                 if (nw > 0.0) wb += nwb * wv[i] / nw;
                 if (!unit_sphere) xb[i] += nxb * xv[i] / nx;
-                gparams[(int64_t)b * ldgp + v * dim + i] = (float)(sign * wb);
-                gx[(int64_t)b * ldgx + v * dim + i] = (float)xb[i];
+                gparams[(int64_t)b * ldgp + v * dim + i] = (T)(sign * wb);
+                gx[(int64_t)b * ldgx + v * dim + i] = (T)xb[i];
             }
     }
 }
@@ -897,6 +900,20 @@ static int launch_periodic_embedding_backward(const char* who, const T* x, int64
     return check_launch("periodic_embedding_kernel");
 }
 
+template <typename T>
+static int launch_moebius_backward(const char* who, const T* x, int64_t ldx, const T* params, int64_t ldp, int dimension,
+                                   T max_radius, int unit_sphere, int sign, const T* gy, int64_t ldgy, const T* gl, T* gparams,
+                                   int64_t ldgp, T* gx, int64_t ldgx, int B, int D, void* stream) {
+    TFEP_REQUIRE(dimension >= 1 && dimension <= MOEBIUS_MAX_DIM_B, "%s: dimension=%d unsupported", who, dimension);
+    TFEP_REQUIRE(D % dimension == 0 && (sign == 1 || sign == -1), "%s: bad arguments", who);
+    if (B <= 0 || D <= 0) return TFEP_OK;
+    TFEP_REQUIRE(x && params && gy && gparams && gx, "%s: NULL pointer", who);
+    moebius_backward_kernel<T><<<row_blocks_b(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, ldp, dimension, max_radius,
+                                                                                unit_sphere, (T)sign, gy, ldgy, gl, gparams,
+                                                                                ldgp, gx, ldgx, B, D);
+    return check_launch("moebius_backward_kernel");
+}
+
 template <typename T, bool INVERSE>
 static int launch_symmoebius_backward_dir(const T* x, int64_t ldx, const T* params, int64_t ldp, int dim, double max_radius,
                                           const T* gy, int64_t ldgy, const T* gl, T* gparams, int64_t ldgp, T* gx,
@@ -1027,14 +1044,16 @@ int tfep_moebius_backward(const float* x, int64_t ldx, const float* params, int6
                           float max_radius, int unit_sphere, int sign, const float* gy, int64_t ldgy,
                           const float* g_log_det_J, float* gparams, int64_t ldgp, float* gx, int64_t ldgx, int B, int D,
                           void* stream) {
-    TFEP_REQUIRE(dimension >= 1 && dimension <= MOEBIUS_MAX_DIM_B, "moebius_backward: dimension=%d unsupported", dimension);
-    TFEP_REQUIRE(D % dimension == 0 && (sign == 1 || sign == -1), "moebius_backward: bad arguments");
-    if (B <= 0 || D <= 0) return TFEP_OK;
-    TFEP_REQUIRE(x && params && gy && gparams && gx, "moebius_backward: NULL pointer");
-    moebius_backward_kernel<<<row_blocks_b(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, ldp, dimension, max_radius,
-                                                                             unit_sphere, (float)sign, gy, ldgy, g_log_det_J,
-                                                                             gparams, ldgp, gx, ldgx, B, D);
-    return check_launch("moebius_backward_kernel");
+    return launch_moebius_backward("moebius_backward", x, ldx, params, ldp, dimension, max_radius, unit_sphere, sign, gy, ldgy,
+                                   g_log_det_J, gparams, ldgp, gx, ldgx, B, D, stream);
+}
+
+int tfep_moebius_backward_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int dimension,
+                              double max_radius, int unit_sphere, int sign, const double* gy, int64_t ldgy,
+                              const double* g_log_det_J, double* gparams, int64_t ldgp, double* gx, int64_t ldgx, int B,
+                              int D, void* stream) {
+    return launch_moebius_backward("moebius_backward_f64", x, ldx, params, ldp, dimension, max_radius, unit_sphere, sign, gy,
+                                   ldgy, g_log_det_J, gparams, ldgp, gx, ldgx, B, D, stream);
 }
 
 int tfep_symmetrized_moebius_backward(const float* x, int64_t ldx, const float* params, int64_t ldp, int dimension,

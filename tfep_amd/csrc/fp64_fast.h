@@ -55,4 +55,19 @@ __device__ __forceinline__ double fast_log64(double a) {          // a >= 0; log
     return a > 0.0 ? (a < INFINITY ? out : a) : (a == 0.0 ? -INFINITY : a);
 }
 
+// The reciprocal, square root and logarithm of the Moebius maps (moebius.h, symmoebius.h) by the element type T of the
+// kernel: float kernels compute in fp64 with the ~1 ulp helpers above (their results are rounded to float), double kernels
+// with IEEE division, square root and logarithm.
+template <typename T> struct SymMath;
+template <> struct SymMath<float> {
+    static __device__ __forceinline__ double rcp(double a) { return fast_rcp64(a); }
+    static __device__ __forceinline__ double sqrt(double a) { return fast_sqrt64(a); }
+    static __device__ __forceinline__ double log(double a) { return fast_log64(a); }
+};
+template <> struct SymMath<double> {
+    static __device__ __forceinline__ double rcp(double a) { return 1.0 / a; }
+    static __device__ __forceinline__ double sqrt(double a) { return ::sqrt(a); }
+    static __device__ __forceinline__ double log(double a) { return ::log(a); }
+};
+
 }  // namespace tfep

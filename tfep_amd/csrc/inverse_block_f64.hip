@@ -23,8 +23,10 @@
 // is one unit of work of a degree.  The wave that owns it follows the links of its feature records (feats[s][6]: 1 +
 // component index, feats[s][7]: the slot of the next component), reads the d parameters from `par` (P = 1 per feature)
 // and the d values of y, evaluates the map of symmoebius.h / quatprod.h once and writes every component; the log-det
-// goes to the slot of component 0, 0.0 to the others, so the row's sum stays "in slot order, wave 0".  The scalar
-// instantiation chain_kernel<KMAX, false> compiles none of this.
+// goes to the slot of component 0, 0.0 to the others, so the row's sum stays "in slot order, wave 0".  The plain Moebius
+// map (kinds 5: general, 6: on the unit sphere; 4 is not assigned) is a vector member of the same shape: its inverse is moebius.h's
+// moebius_vector<double> on the negated parameters (moebius.py:142-147), whose log-det is that of the inverse itself.
+// The scalar instantiation chain_kernel<KMAX, false> compiles none of this.
 #include <type_traits>
 
 #include "common.h"
@@ -138,6 +140,10 @@ __global__ void __launch_bounds__(THREADS) chain_kernel(std::conditional_t<VEC, 
                             quatprod_element<double, true>(y4, w4, x4);
 #pragma unroll
                             for (int i = 0; i < 4; ++i) xv[i] = x4[i];
+                        } else if (kind >= 5) {                             // Moebius: the map with -w (moebius.py:142-147)
+#pragma unroll
+                            for (int i = 0; i < MOEBIUS_MAX_DIM; ++i) wv[i] = -wv[i];
+                            ld = moebius_vector<double>(yv, wv, dim, g.max_radius[member], kind == 6 ? 1 : 0, xv);
                         } else {                                            // log|det J| of the inverse itself (symmoebius.h)
                             ld = symmoebius_vector<double, true>(yv, wv, dim, g.max_radius[member], xv);
                         }
@@ -224,7 +230,7 @@ int launch(const std::conditional_t<VEC, ChainVecArgs, ChainArgs>& g, size_t lds
     return check_launch(VEC ? "inverse_chain_vec_f64_kernel" : "inverse_chain_f64_kernel");
 }
 
-// The argument checks and the launch of both entry points; `who` prefixes the error messages.  VEC: member kinds 2 and 3
+// The argument checks and the launch of both entry points; `who` prefixes the error messages.  VEC: member kinds 2, 3, 5 and 6
 // with member_dim / member_max_radius.
 template <bool VEC>
 int run(const char* who, const tfep_inverse_chain_f64_desc* d, const int32_t* member_dim, const double* member_max_radius,
@@ -263,9 +269,14 @@ int run(const char* who, const tfep_inverse_chain_f64_desc* d, const int32_t* me
     for (int m = 0; m < d->n_members; ++m) {
         const int kind = d->member_kind[m];
         if constexpr (VEC) {
-            TFEP_REQUIRE(kind >= 0 && kind <= 3, "%s: member %d: kind must be 0 (affine), 1 (RQ spline), 2 (symmetrized Moebius) "
-                         "or 3 (quaternion product)", who, m);
-            if (kind == 2) {
+            TFEP_REQUIRE(kind >= 0 && kind <= 6 && kind != 4, "%s: member %d: kind must be 0 (affine), 1 (RQ spline), "
+                         "2 (symmetrized Moebius), 3 (quaternion product), 5 (Moebius) or 6 (Moebius on the unit sphere)", who, m);
+            if (kind >= 5) {
+                TFEP_REQUIRE(member_dim[m] >= 1 && member_dim[m] <= MOEBIUS_MAX_DIM, "%s: member %d: member_dim=%d of a "
+                             "Moebius member must be in 1..%d", who, m, member_dim[m], MOEBIUS_MAX_DIM);
+                TFEP_REQUIRE(member_max_radius[m] > 0.0 && member_max_radius[m] < 1.0, "%s: member %d: max_radius=%g must be "
+                             "in (0, 1)", who, m, member_max_radius[m]);
+            } else if (kind == 2) {
                 TFEP_REQUIRE(member_dim[m] >= 2 && member_dim[m] <= MOEBIUS_MAX_DIM, "%s: member %d: member_dim=%d of a "
                              "symmetrized Moebius member must be in 2..%d", who, m, member_dim[m], MOEBIUS_MAX_DIM);
                 TFEP_REQUIRE(member_max_radius[m] > 0.0 && member_max_radius[m] < 1.0, "%s: member %d: max_radius=%g must be "
@@ -275,7 +286,7 @@ int run(const char* who, const tfep_inverse_chain_f64_desc* d, const int32_t* me
                              member_dim[m]);
             }
             g.dim[m] = kind >= 2 ? member_dim[m] : 0;
-            g.max_radius[m] = kind == 2 ? member_max_radius[m] : 0.0;
+            g.max_radius[m] = kind == 2 || kind >= 5 ? member_max_radius[m] : 0.0;
         } else {
             TFEP_REQUIRE(kind == 0 || kind == 1, "%s: member %d: kind must be 0 (affine) or 1 (RQ spline)", who, m);
         }

@@ -18,8 +18,13 @@ constexpr int MOEBIUS_MAX_DIM = 8;
 // HBM traffic; 0.30 ms now)
 // xv: the point, wv: the (signed: the inverse is the map with -w, moebius.py:142-147) raw parameter vector, rescaled
 // in place; yv: the image.  Returns log|det J|.
+// T is the element type of the kernel, which is also the type of its max_radius argument (the float32 call sites deduce
+// it from there): float kernels take the ~1 ulp helpers, double kernels IEEE division, square root and logarithm
+// (SymMath<T>, fp64_fast.h).
+template <typename T>
 __device__ __forceinline__ double moebius_vector(const double (&xv)[MOEBIUS_MAX_DIM], double (&wv)[MOEBIUS_MAX_DIM], int dim,
-                                                 float max_radius, int unit_sphere, double (&yv)[MOEBIUS_MAX_DIM]) {
+                                                 T max_radius, int unit_sphere, double (&yv)[MOEBIUS_MAX_DIM]) {
+    using M = SymMath<T>;
     double dv[MOEBIUS_MAX_DIM];
     double wn2 = 0.0, xn2 = 0.0;
 #pragma unroll
@@ -28,11 +33,11 @@ __device__ __forceinline__ double moebius_vector(const double (&xv)[MOEBIUS_MAX_
             wn2 += wv[i] * wv[i];
             xn2 += xv[i] * xv[i];
         }
-    const double wn = fast_sqrt64(wn2);
-    double resc = (double)max_radius * fast_rcp64(1.0 + wn);       // moebius.py:437-441
+    const double wn = M::sqrt(wn2);
+    double resc = (double)max_radius * M::rcp(1.0 + wn);       // moebius.py:437-441
     double xn = 1.0;
     if (!unit_sphere) {
-        xn = fast_sqrt64(xn2);
+        xn = M::sqrt(xn2);
         resc *= xn;
     }
     const double wns = resc * wn;
@@ -45,12 +50,12 @@ __device__ __forceinline__ double moebius_vector(const double (&xv)[MOEBIUS_MAX_
             dv[i] = xv[i] - wv[i];
             dn2 += dv[i] * dv[i];
         }
-    const double inv_dn2 = fast_rcp64(dn2);
+    const double inv_dn2 = M::rcp(dn2);
     const double c = numer * inv_dn2;
 #pragma unroll
     for (int i = 0; i < MOEBIUS_MAX_DIM; ++i)
         if (i < dim) yv[i] = c * dv[i] - wv[i];                // moebius.py:452
-    const double log_c = fast_log64(fabs(c));
+    const double log_c = M::log(fabs(c));
     if (unit_sphere) return dim * log_c;
     double dy = 0.0;   // d . y
     double xy = 0.0;   // x . y
@@ -63,7 +68,7 @@ __device__ __forceinline__ double moebius_vector(const double (&xv)[MOEBIUS_MAX_
             xd += xv[i] * dv[i];
         }
     const double xRy = xy - 2.0 * xd * dy * inv_dn2;           // x . (R y)
-    return (dim - 1) * log_c - fast_log64(xn2) + fast_log64(fabs(xRy));
+    return (dim - 1) * log_c - M::log(xn2) + M::log(fabs(xRy));
 }
 
 }  // namespace tfep

@@ -18,7 +18,7 @@
 // gradient of |w| as 0, like torch.
 //
 // T is the element type of the kernel: float kernels compute in fp64 with the ~1 ulp helpers of fp64_fast.h (their
-// results are rounded to float), double kernels with IEEE division, square root and logarithm.
+// results are rounded to float), double kernels with IEEE division, square root and logarithm (SymMath<T>, fp64_fast.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,18 +26,6 @@
 #include "moebius.h"
 
 namespace tfep {
-
-template <typename T> struct SymMath;
-template <> struct SymMath<float> {
-    static __device__ __forceinline__ double rcp(double a) { return fast_rcp64(a); }
-    static __device__ __forceinline__ double sqrt(double a) { return fast_sqrt64(a); }
-    static __device__ __forceinline__ double log(double a) { return fast_log64(a); }
-};
-template <> struct SymMath<double> {
-    static __device__ __forceinline__ double rcp(double a) { return 1.0 / a; }
-    static __device__ __forceinline__ double sqrt(double a) { return ::sqrt(a); }
-    static __device__ __forceinline__ double log(double a) { return ::log(a); }
-};
 
 __device__ __forceinline__ double sym_powi(double a, int n) {      // a^n, n = 1 .. MOEBIUS_MAX_DIM - 1
     double out = a;

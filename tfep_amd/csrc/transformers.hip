@@ -3,7 +3,7 @@
 // per-sample log|det J| reduction: one wavefront owns one sample (row), its 64 lanes walk the
 // features with unit stride (coalesced 256-B segments per parameter row) and the log-derivative
 // is summed in fp64 with a wave butterfly -- no atomics, bit-reproducible.
-// Affine, volume-preserving shift, SOS, symmetrized Moebius, quaternion product, periodic embedding and column gather / scatter are templates on the element
+// Affine, volume-preserving shift, SOS, Moebius, symmetrized Moebius, quaternion product, periodic embedding and column gather / scatter are templates on the element
 // type: the float instantiation serves the float32 entry points, the double one their _f64 twins.  (The float64 RQ spline
 // has numerics of its own: spline_f64.hip.)
 #include "common.h"
@@ -15,6 +15,8 @@
 #include "embedding.h"
 
 #include <stdarg.h>
+
+#include <type_traits>
 
 namespace tfep {
 
@@ -135,29 +137,32 @@ __global__ void __launch_bounds__(256) spline_kernel(const float* __restrict__ x
 // ---------------------------------------------------------------- Moebius (moebius.py:374-478)
 // One lane per d-vector; the map and its closed-form log|det J| are in moebius.h.  DIM > 0: the dimension is a compile-time
 // constant (d = 2, 3: the loops of moebius_vector unroll to d steps instead of MOEBIUS_MAX_DIM predicated ones; the
-// d = 2 vector is one 8-byte load / store) -- the same arithmetic in the same order, bit for bit; DIM = 0: any d.
-template <int DIM>
-__global__ void __launch_bounds__(256) moebius_kernel(const float* __restrict__ x, int64_t ldx,
-                                                      const float* __restrict__ params, int64_t ldp, int dim_rt,
-                                                      float max_radius, int unit_sphere, float sign,
-                                                      float* __restrict__ y, int64_t ldy, float* __restrict__ ldj,
+// d = 2 vector is one 8-byte (float) or 16-byte (double) load / store) -- the same arithmetic in the same order, bit for
+// bit; DIM = 0: any d.  T = double: float64 I/O and the IEEE arithmetic of SymMath<double>; the split-f16 copy of y
+// (y_split) is a float kernel's only.
+template <typename T, int DIM>
+__global__ void __launch_bounds__(256) moebius_kernel(const T* __restrict__ x, int64_t ldx,
+                                                      const T* __restrict__ params, int64_t ldp, int dim_rt,
+                                                      T max_radius, int unit_sphere, T sign,
+                                                      T* __restrict__ y, int64_t ldy, T* __restrict__ ldj,
                                                       int accumulate, int B, int D, uint32_t* __restrict__ y_split = nullptr,
                                                       int64_t ld_split = 0, float* __restrict__ y_inv_scale = nullptr) {
+    using T2 = std::conditional_t<std::is_same_v<T, float>, float2, double2>;
     const int b = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (b >= B) return;
     const int lane = threadIdx.x & 63;
     const int dim = DIM > 0 ? DIM : dim_rt;
     const int nvec = D / dim;
-    const float* xr = x + (int64_t)b * ldx;
-    const float* pr = params + (int64_t)b * ldp;
-    float* yr = y + (int64_t)b * ldy;
-    // (8-byte accesses for d = 2 when the three rows start on 8-byte boundaries: wave uniform)
-    const bool vec2 = DIM == 2 && (((uintptr_t)xr | (uintptr_t)pr | (uintptr_t)yr) & 7u) == 0;
+    const T* xr = x + (int64_t)b * ldx;
+    const T* pr = params + (int64_t)b * ldp;
+    T* yr = y + (int64_t)b * ldy;
+    // (one access per vector for d = 2 when the three rows start on boundaries of a whole vector: wave uniform)
+    const bool vec2 = DIM == 2 && (((uintptr_t)xr | (uintptr_t)pr | (uintptr_t)yr) & (uintptr_t)(sizeof(T2) - 1)) == 0;
     double acc = 0.0;
     for (int v = lane; v < nvec; v += 64) {
         double xv[MOEBIUS_MAX_DIM], wv[MOEBIUS_MAX_DIM], yv[MOEBIUS_MAX_DIM];
         if (vec2) {
-            const float2 xx = reinterpret_cast<const float2*>(xr)[v], pp = reinterpret_cast<const float2*>(pr)[v];
+            const T2 xx = reinterpret_cast<const T2*>(xr)[v], pp = reinterpret_cast<const T2*>(pr)[v];
             xv[0] = (double)xx.x; xv[1] = (double)xx.y;
             wv[0] = (double)(sign * pp.x); wv[1] = (double)(sign * pp.y);
         } else {
@@ -168,29 +173,33 @@ __global__ void __launch_bounds__(256) moebius_kernel(const float* __restrict__ 
                     wv[i] = (double)(sign * pr[v * dim + i]);
                 }
         }
-        acc += moebius_vector(xv, wv, dim, max_radius, unit_sphere, yv);
+        acc += moebius_vector<T>(xv, wv, dim, max_radius, unit_sphere, yv);
         if (vec2) {
-            reinterpret_cast<float2*>(yr)[v] = float2{(float)yv[0], (float)yv[1]};
-            if (y_split) {
-                // the same row as split-f16 halves for the next layer's GEMM (tfep_split_rows' format: per 8 features 8 hi then
-                // 8 lo halves), with the scale of the bound |y| <= 1 of a unit-sphere map: 2^14
-                typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                const float t0 = (float)yv[0] * 16384.0f, t1 = (float)yv[1] * 16384.0f;
-                const _Float16 h0 = (_Float16)t0, h1 = (_Float16)t1;
-                const h2 hi = {h0, h1}, lo = {(_Float16)(t0 - (float)h0), (_Float16)(t1 - (float)h1)};
-                uint32_t* grp = y_split + (int64_t)b * ld_split + (v >> 2) * 8;        // 8 words = 32 bytes per group of 8 features
-                grp[v & 3] = __builtin_bit_cast(uint32_t, hi);
-                grp[4 + (v & 3)] = __builtin_bit_cast(uint32_t, lo);
+            reinterpret_cast<T2*>(yr)[v] = T2{(T)yv[0], (T)yv[1]};
+            if constexpr (std::is_same_v<T, float>) {
+                if (y_split) {
+                    // the same row as split-f16 halves for the next layer's GEMM (tfep_split_rows' format: per 8 features 8 hi
+                    // then 8 lo halves), with the scale of the bound |y| <= 1 of a unit-sphere map: 2^14
+                    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+                    const float t0 = (float)yv[0] * 16384.0f, t1 = (float)yv[1] * 16384.0f;
+                    const _Float16 h0 = (_Float16)t0, h1 = (_Float16)t1;
+                    const h2 hi = {h0, h1}, lo = {(_Float16)(t0 - (float)h0), (_Float16)(t1 - (float)h1)};
+                    uint32_t* grp = y_split + (int64_t)b * ld_split + (v >> 2) * 8;        // 8 words = 32 bytes per group of 8 features
+                    grp[v & 3] = __builtin_bit_cast(uint32_t, hi);
+                    grp[4 + (v & 3)] = __builtin_bit_cast(uint32_t, lo);
+                }
             }
         } else {
 #pragma unroll
             for (int i = 0; i < MOEBIUS_MAX_DIM; ++i)
-                if (i < dim) yr[v * dim + i] = (float)yv[i];
+                if (i < dim) yr[v * dim + i] = (T)yv[i];
         }
     }
-    if (y_split) {
-        // padding groups up to the row's k-tile stay zero (the caller clears the buffer once); the row's 1/scale
-        if (lane == 0) y_inv_scale[b] = 1.0f / 16384.0f;
+    if constexpr (std::is_same_v<T, float>) {
+        if (y_split) {
+            // padding groups up to the row's k-tile stay zero (the caller clears the buffer once); the row's 1/scale
+            if (lane == 0) y_inv_scale[b] = 1.0f / 16384.0f;
+        }
     }
     acc = wave_sum(acc);
     if (ldj) store_ldj(ldj, b, acc, accumulate);
@@ -372,6 +381,21 @@ static int launch_sos(const char* who, const T* x, int64_t ldx, const T* params,
     TFEP_REQUIRE(x && params && y, "%s: x/params/y must be non-NULL", who);
     sos_kernel<T><<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, L, K, y, ldy, ldj, accumulate, B, D);
     return check_launch("sos_kernel");
+}
+
+template <typename T>
+static int launch_moebius(const char* who, const T* x, int64_t ldx, const T* params, int64_t ldp, int dimension, T max_radius,
+                          int unit_sphere, int sign, T* y, int64_t ldy, T* ldj, int accumulate, int B, int D, void* stream) {
+    TFEP_REQUIRE(B == 0 || (x && params && y), "%s: x/params/y must be non-NULL", who);
+    TFEP_REQUIRE(dimension >= 1 && dimension <= MOEBIUS_MAX_DIM, "%s: dimension=%d unsupported (1..%d)", who, dimension,
+                 MOEBIUS_MAX_DIM);
+    TFEP_REQUIRE(D % dimension == 0, "%s: n_features=%d is not a multiple of dimension=%d", who, D, dimension);
+    TFEP_REQUIRE(sign == 1 || sign == -1, "%s: sign must be +1 or -1", who);
+    if (B == 0) return TFEP_OK;
+    auto kernel = dimension == 2 ? moebius_kernel<T, 2> : dimension == 3 ? moebius_kernel<T, 3> : moebius_kernel<T, 0>;
+    kernel<<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, ldp, dimension, max_radius, unit_sphere, (T)sign, y,
+                                                           ldy, ldj, accumulate, B, D, nullptr, 0, nullptr);
+    return check_launch("moebius_kernel");
 }
 
 template <typename T, bool INVERSE>
@@ -557,16 +581,15 @@ int tfep_spline_inverse(const float* y, int64_t ldy, const float* params, tfep_p
 int tfep_moebius_forward(const float* x, int64_t ldx, const float* params, int64_t ldp, int dimension,
                          float max_radius, int unit_sphere, int sign, float* y, int64_t ldy, float* log_det_J,
                          int accumulate, int B, int D, void* stream) {
-    TFEP_REQUIRE(B == 0 || (x && params && y), "moebius: x/params/y must be non-NULL");
-    TFEP_REQUIRE(dimension >= 1 && dimension <= MOEBIUS_MAX_DIM, "moebius: dimension=%d unsupported (1..%d)", dimension,
-                 MOEBIUS_MAX_DIM);
-    TFEP_REQUIRE(D % dimension == 0, "moebius: n_features=%d is not a multiple of dimension=%d", D, dimension);
-    TFEP_REQUIRE(sign == 1 || sign == -1, "moebius: sign must be +1 or -1");
-    if (B == 0) return TFEP_OK;
-    auto kernel = dimension == 2 ? moebius_kernel<2> : dimension == 3 ? moebius_kernel<3> : moebius_kernel<0>;
-    kernel<<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, ldp, dimension, max_radius, unit_sphere, (float)sign, y,
-                                                           ldy, log_det_J, accumulate, B, D, nullptr, 0, nullptr);
-    return check_launch("moebius_kernel");
+    return launch_moebius("moebius", x, ldx, params, ldp, dimension, max_radius, unit_sphere, sign, y, ldy, log_det_J,
+                          accumulate, B, D, stream);
+}
+
+int tfep_moebius_forward_f64(const double* x, int64_t ldx, const double* params, int64_t ldp, int dimension,
+                             double max_radius, int unit_sphere, int sign, double* y, int64_t ldy, double* log_det_J,
+                             int accumulate, int B, int D, void* stream) {
+    return launch_moebius("moebius_f64", x, ldx, params, ldp, dimension, max_radius, unit_sphere, sign, y, ldy, log_det_J,
+                          accumulate, B, D, stream);
 }
 
 int tfep_symmetrized_moebius(const float* x, int64_t ldx, const float* params, int64_t ldp, int dimension, double max_radius,
@@ -603,7 +626,7 @@ int tfep_moebius_forward_split_out(const float* x, int64_t ldx, const float* par
     TFEP_REQUIRE(((uintptr_t)x & 7) == 0 && ((uintptr_t)params & 7) == 0 && ((uintptr_t)y & 7) == 0 && ldx % 2 == 0 && ldp % 2 == 0 && ldy % 2 == 0,
                  "moebius_split_out: x, params and y rows must start on 8-byte boundaries");
     if (B == 0) return TFEP_OK;
-    moebius_kernel<2><<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, ldp, 2, max_radius, 1, 1.0f, y, ldy, log_det_J, accumulate, B,
+    moebius_kernel<float, 2><<<row_blocks(B), 256, 0, (hipStream_t)stream>>>(x, ldx, params, ldp, 2, max_radius, 1, 1.0f, y, ldy, log_det_J, accumulate, B,
                                                                       D, (uint32_t*)y_split, ld_split, y_inv_scale);
     return check_launch("moebius_kernel");
 }

@@ -112,7 +112,7 @@ def transformer_vjp(tr, x, theta, th_off, gy, gl, gtheta, gx, layout=None, order
         th, out = block(2 * tr.n_polynomials + 1)
         ops.sos_backward(x, th, tr.n_polynomials, gy, layout=layout, out=out)
     elif type(tr) is MoebiusTransformer:
-        if f64:
+        if f64 and not tr.float64_kernels:
             raise TypeError(f'{type(tr).__name__}: float64 is not supported for this transformer yet (float32 only)')
         th, out = block(1)
         ops.moebius_backward(x, th, tr.dimension, tr.max_radius, tr.unit_sphere, gy, gl, out=out)

@@ -36,6 +36,18 @@ _FUSED_AFFINE, _FUSED_SPLINE, _FUSED_MIXED, _FUSED_SOS = 0, 1, 2, 3
 _F64_CHAIN_KINDS = (AffineTransformer, NeuralSplineTransformer, SymmetrizedMoebiusTransformer, QuaternionProductTransformer)
 
 
+def _f64_chain_kind(t, vectors):
+    """member_kind of transformer ``t`` in the float64 chain kernels, or None where they have none for it.  ``vectors``
+    (the layer's ``blocked_inverse_f64_vectors``) admits the vector-valued kinds: 2, 3 and -- for a Moebius transformer
+    that has its own ``float64_kernels`` on -- 5 (general) or 6 (on the unit sphere; 4 is not assigned)."""
+    if type(t) is MoebiusTransformer:
+        return (6 if t.unit_sphere else 5) if vectors and t.float64_kernels else None
+    if type(t) not in _F64_CHAIN_KINDS:
+        return None
+    kind = _F64_CHAIN_KINDS.index(type(t))
+    return kind if kind < 2 or vectors else None
+
+
 class AutoregressiveFlow(torch.nn.Module):
     """Transform features with a transformer parametrised by a conditioner (Papamakarios et al. 2017)."""
 
@@ -480,7 +492,7 @@ class AutoregressiveFlow(torch.nn.Module):
         ops.check_device_tensor(x, name, torch.float64 if self.is_float64 else torch.float32)
         self._check_features(x, name)
         tr = self._transformer
-        if type(tr) is MoebiusTransformer:
+        if type(tr) is MoebiusTransformer and not tr.float64_kernels:
             raise TypeError(f'{type(self).__name__}: float64 is not supported for the Moebius transformer yet (float32 only)')
         if type(tr) is MixedTransformer:
             check_float64_members(tr)
@@ -1762,9 +1774,10 @@ class AutoregressiveFlow(torch.nn.Module):
     #: (``_blocked_f64.fit_block``).  Larger blocks mean fewer, fuller panel GEMMs; 16 is what fits a cfg2-sized layer.
     inverse_block_f64 = 16
 
-    #: Opt-in: let the float64 blocked inverse also take a ``SymmetrizedMoebiusTransformer`` or a
-    #: ``QuaternionProductTransformer``, alone or as a member of a mixed transformer, when every vector lies inside one
-    #: degree (chain kernel ``tfep_inverse_chain_vec_f64``).  Off by default: such layers keep the pass per degree.
+    #: Opt-in: let the float64 blocked inverse also take a ``SymmetrizedMoebiusTransformer``, a
+    #: ``QuaternionProductTransformer`` or a ``MoebiusTransformer`` with ``float64_kernels`` on, alone or as a member of a
+    #: mixed transformer, when every vector lies inside one degree (chain kernel ``tfep_inverse_chain_vec_f64``).  Off by
+    #: default: such layers keep the pass per degree.
     blocked_inverse_f64_vectors = False
 
     def _blocked_f64_ok(self):
@@ -1772,7 +1785,8 @@ class AutoregressiveFlow(torch.nn.Module):
         a degree assignment reproduces, no embedding or a PeriodicEmbedding, no ``_conditioner_indices``) and an affine or
         RQ-spline transformer, or a mixed transformer of up to four such members; features that no step transforms pass
         through.  With ``blocked_inverse_f64_vectors`` a symmetrized Moebius or quaternion-product transformer (or member)
-        whose vectors each lie inside one degree qualifies too.  Everything else keeps the pass per degree."""
+        whose vectors each lie inside one degree qualifies too, and so does a Moebius transformer with ``float64_kernels``
+        on.  Everything else keeps the pass per degree."""
         made = self._conditioner
         if not self.blocked_inverse or not self.is_float64 or not isinstance(made, MADE) or len(self._conditioner_indices) > 0:
             return False
@@ -1783,8 +1797,7 @@ class AutoregressiveFlow(torch.nn.Module):
             return False
         tr = self._transformer
         members = tr._transformers if type(tr) is MixedTransformer else [tr]
-        kinds = _F64_CHAIN_KINDS if self.blocked_inverse_f64_vectors else _F64_CHAIN_KINDS[:2]
-        if not all(type(t) in kinds for t in members):
+        if any(_f64_chain_kind(t, self.blocked_inverse_f64_vectors) is None for t in members):
             return False
         return self._blocked_f64_host_plan() is not None
 
@@ -1792,7 +1805,11 @@ class AutoregressiveFlow(torch.nn.Module):
         """The host plan of the float64 blocked inverse (``flows/_blocked_f64.py``), or None when the layer's degrees do not
         fit it; cached per block size and mask version."""
         made = self._conditioner
-        key = ('blocked_f64_host', int(self.inverse_block_f64), bool(self.blocked_inverse_f64_vectors), made._mask_versions())
+        tr = self._transformer
+        moebius = tuple(bool(t.float64_kernels) for t in (tr._transformers if type(tr) is MixedTransformer else [tr])
+                        if type(t) is MoebiusTransformer)
+        key = ('blocked_f64_host', int(self.inverse_block_f64), bool(self.blocked_inverse_f64_vectors), moebius,
+               made._mask_versions())
         if key not in self._dev:
             self._dev[key] = self._make_blocked_f64_host_plan(max(1, int(self.inverse_block_f64)))
         return self._dev[key]
@@ -1834,7 +1851,9 @@ class AutoregressiveFlow(torch.nn.Module):
             offsets, counts = tr.host_splits(), [len(i) for i in inds]
         else:
             members, member_of, local_of, offsets, counts = [tr], None, np.arange(n_tr), None, None
-        kinds = [_F64_CHAIN_KINDS.index(type(t)) for t in members]       # (member_kind of the chain kernel)
+        kinds = [_f64_chain_kind(t, self.blocked_inverse_f64_vectors) for t in members]       # (member_kind of the chain kernel)
+        if any(k is None for k in kinds):
+            return None
         P_of = [t.n_parameters_per_feature if k == 1 else 2 if k == 0 else 1 for k, t in zip(kinds, members)]
         mem = np.zeros(n_tr, dtype=np.int64) if member_of is None else member_of
         params_of = np.asarray(P_of, dtype=np.int64)[mem]
@@ -1915,7 +1934,7 @@ class AutoregressiveFlow(torch.nn.Module):
                 for g, (t, kind) in enumerate(zip(hp['members'], hp['kinds'])):
                     if kind >= 2:
                         vd.member_dim[g] = int(t.dimension)
-                        vd.member_max_radius[g] = float(t.max_radius) if kind == 2 else 0.0
+                        vd.member_max_radius[g] = float(t.max_radius) if kind != 3 else 0.0
                 outer.append(vd)
             else:
                 d = _lib.InverseChainF64Desc()

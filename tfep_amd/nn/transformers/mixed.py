@@ -9,9 +9,10 @@ from .transformer import MAFTransformer
 
 
 def check_float64_members(tr):
-    """A float64 mixed transformer runs its members on the float64 kernels; the Moebius transformer has none yet."""
+    """A float64 mixed transformer runs its members on the float64 kernels; a Moebius member takes part only with its
+    ``float64_kernels`` switch on."""
     from .moebius import MoebiusTransformer
-    if any(isinstance(t, MoebiusTransformer) for t in tr._transformers):
+    if any(isinstance(t, MoebiusTransformer) and not t.float64_kernels for t in tr._transformers):
         raise TypeError('MixedTransformer: float64 is not supported for a mixed transformer with a Moebius member yet '
                         '(float32 only)')
 

@@ -10,6 +10,11 @@ def _float32_only(x):
         raise TypeError('MoebiusTransformer: float64 is not supported for the Moebius transformer yet (float32 only)')
 
 
+def moebius_float64(tr):
+    """Is ``tr`` a Moebius transformer that has opted in to the float64 kernels (``float64_kernels``)?"""
+    return isinstance(tr, MoebiusTransformer) and bool(tr.float64_kernels)
+
+
 class MoebiusTransformer(MAFTransformer):
     r""":math:`y = \frac{\|x\|^2 - \|w\|^2}{\|x - w\|^2}(x - w) - w` on ``dimension``-vectors.
 
@@ -17,21 +22,32 @@ class MoebiusTransformer(MAFTransformer):
     inverse is the forward map with ``-w`` (reference moebius.py:142-147).
     """
 
+    #: Opt-in: run float64 tensors on the float64 kernels (``tfep_moebius_forward_f64`` / ``_backward_f64``: IEEE division,
+    #: square root and logarithm), alone, in a float64 MAF layer or as a member of a float64 mixed transformer.  False (the
+    #: default): float64 is refused with a TypeError, as before the float64 kernels existed.  A class attribute; an
+    #: instance may set its own.
+    float64_kernels = False
+
     def __init__(self, dimension: int, max_radius: float = 0.99, unit_sphere: bool = False):
         super().__init__()
         self.dimension = dimension
         self.max_radius = max_radius
         self.unit_sphere = unit_sphere
 
+    def _check(self, x, name):
+        if self.float64_kernels:
+            ops.check_device_tensor(x, name, ops._dtype(x))                # float32, or float64 (the float64 kernels)
+        else:
+            _float32_only(x)
+            ops.check_device_tensor(x, name)
+
     def forward(self, x, parameters):
-        _float32_only(x)
-        ops.check_device_tensor(x, 'x')
+        self._check(x, 'x')
         return tuple(torch.ops.tfep.moebius_forward(x, parameters, int(self.dimension), float(self.max_radius),
                                                     bool(self.unit_sphere)))                   # differentiable
 
     def inverse(self, y, parameters):
-        _float32_only(y)
-        ops.check_device_tensor(y, 'y')
+        self._check(y, 'y')
         return tuple(torch.ops.tfep.moebius_inverse(y, parameters, int(self.dimension), float(self.max_radius),
                                                     bool(self.unit_sphere)))
 

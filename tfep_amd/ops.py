@@ -243,23 +243,26 @@ def spline_backward(x, parameters, cfg, grad_y, grad_log_det_J, *, layout=None, 
 # ----------------------------------------------------------------------------- moebius
 
 def moebius(x, parameters, dimension, max_radius=0.99, unit_sphere=False, inverse=False, log_det_J=None):
-    """MoebiusTransformer.forward / .inverse (reference moebius.py:104-147, :374-478)."""
-    x, ldx = rows(x, 'x')
+    """MoebiusTransformer.forward / .inverse (reference moebius.py:104-147, :374-478).  float64 tensors run on the float64
+    kernels; mixed float32 / float64 arguments are a TypeError."""
+    dt = _dtype(x)
+    x, ldx = rows(x, 'x', dt)
     B, D = x.shape
-    parameters, ldp = _check_params(parameters, B, D)
+    parameters, ldp = _check_params(parameters, B, D, dtype=dt)
     y = torch.empty(B, D, dtype=x.dtype, device=x.device)
-    ldj, acc = _ldj_out(log_det_J, B, x)
-    call('tfep_moebius_forward', ptr(x), ldx, ptr(parameters), ldp,
+    ldj, acc = _ldj_out(log_det_J, B, x, dt)
+    call('tfep_moebius_forward' + _sfx(dt), ptr(x), ldx, ptr(parameters), ldp,
          int(dimension), float(max_radius), int(bool(unit_sphere)), -1 if inverse else 1,
          ptr(y), max(D, 1), ptr(ldj), acc, B, D, stream_of(x))
     return y, ldj
 
 
 def moebius_backward(x, parameters, dimension, max_radius, unit_sphere, grad_y, grad_log_det_J, *, out=None):
-    """VJP of ``moebius`` (forward) at ``x``: ``(grad_x, grad_parameters)``; float32 only; ``_vjp_args``."""
-    head, cot, gl, tail, grads, keep = _vjp_args(torch.float32, x, parameters, 1, grad_y, grad_log_det_J, None, out, zeros,
-                                                 ld_only=True)
-    call('tfep_moebius_backward', *head, int(dimension), float(max_radius), int(bool(unit_sphere)), 1, *cot, gl, *tail)
+    """VJP of ``moebius`` (forward) at ``x``: ``(grad_x, grad_parameters)``; float32 or float64 by ``x``; ``_vjp_args``."""
+    dt = _dtype(x)
+    head, cot, gl, tail, grads, keep = _vjp_args(dt, x, parameters, 1, grad_y, grad_log_det_J, None, out, zeros, ld_only=True)
+    call('tfep_moebius_backward' + _sfx(dt), *head, int(dimension), float(max_radius), int(bool(unit_sphere)), 1, *cot, gl,
+         *tail)
     return grads
 
 

@@ -226,7 +226,16 @@ def _moebius_bwd(ctx, gy, gl):
     return gx, gp, None, None, None
 
 
+def _moebius_inverse_bwd(ctx, gy, gl):
+    # the inverse is the forward map on negated parameters (reference moebius.py:142-147): its VJP at -p, and d(-p)/dp = -1
+    y, p = ctx.saved_tensors
+    gy, gl = _vjp_inputs(ctx, (gy, gl))
+    gx, gp = torch.ops.tfep.moebius_backward(y, -p, gy, gl, *ctx.cfg)
+    return gx, -gp, None, None, None
+
+
 moebius_forward.register_autograd(_moebius_bwd, setup_context=_moebius_setup)
+moebius_inverse.register_autograd(_moebius_inverse_bwd, setup_context=_moebius_setup)
 
 
 # ============================================================================= symmetrized Moebius
