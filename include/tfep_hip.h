@@ -239,9 +239,11 @@ int tfep_spline_inverse(const float* y, int64_t ldy, const float* params, tfep_p
                         float* log_det_J, int accumulate, int B, int D, void* stream);
 
 /* Moebius transformer on `dimension`-vectors (moebius.py:374-478); inverse = forward with
- * -w (moebius.py:142-147): pass sign = -1.  D = n_vectors * dimension, dimension <= 8. */
+ * -w (moebius.py:142-147): pass sign = -1.  D = n_vectors * dimension, dimension <= 8.  max_radius is a double here, in
+ * the VJP, in the split-out variant and in the two layer descriptors below: the arithmetic is fp64, and the float32
+ * rounding of 0.99 (a relative 1e-8) is a relative 1e-6 in the derivative of a vector with |x - u| = 0.01 |x|. */
 int tfep_moebius_forward(const float* x, int64_t ldx, const float* params, int64_t ldp,
-                         int dimension, float max_radius, int unit_sphere, int sign,
+                         int dimension, double max_radius, int unit_sphere, int sign,
                          float* y, int64_t ldy, float* log_det_J, int accumulate,
                          int B, int D, void* stream);
 /* The forward map of unit-sphere 2-vectors (dimension 2, unit_sphere 1, sign +1) that ALSO writes y as split-f16 rows for the
@@ -249,7 +251,7 @@ int tfep_moebius_forward(const float* x, int64_t ldx, const float* params, int64
  * D are not written: clear the buffer once) with the row scale of the bound |y| <= 1 (y_inv_scale[b] = 2^-14) -- the
  * conversion pass between two MAF layers (one read + one write of the batch) disappears.  Rows of x, params, y on 8-byte
  * boundaries. */
-int tfep_moebius_forward_split_out(const float* x, int64_t ldx, const float* params, int64_t ldp, float max_radius,
+int tfep_moebius_forward_split_out(const float* x, int64_t ldx, const float* params, int64_t ldp, double max_radius,
                                    float* y, int64_t ldy, float* log_det_J, int accumulate,
                                    void* y_split, int64_t ld_split, float* y_inv_scale, int B, int D, void* stream);
 
@@ -482,7 +484,7 @@ typedef struct tfep_inverse_block_desc {
     int32_t cache_len, max_feats;
     const tfep_spline_desc* spline;
     int32_t moebius_dim, moebius_unit_sphere;
-    float moebius_max_radius;
+    double moebius_max_radius;
     int32_t rows_per_wave;      /* 64 (or 0): one sample row per lane; 16: four lanes per row, 4x the waves (for batches
                                    that leave SIMDs idle: the chain is bound by one wave's instruction issue rate) */
     int32_t n_spline_groups;    /* kind 3: descriptors in `spline` */
@@ -564,7 +566,7 @@ typedef struct tfep_maf_layer_desc {
     void* scratch[2]; int64_t ld_scratch;
     int32_t kind;
     const float* x; int64_t ldx; float* y; int64_t ldy; float* log_det_J;
-    int32_t n_features, moebius_dim, moebius_unit_sphere; float moebius_max_radius;
+    int32_t n_features, moebius_dim, moebius_unit_sphere; double moebius_max_radius;
 } tfep_maf_layer_desc;
 int tfep_maf_layer_tile_n(void);
 int tfep_maf_layer_forward_split(const tfep_maf_layer_desc* desc, void* stream);
@@ -621,7 +623,7 @@ int tfep_sos_backward(const float* x, int64_t ldx, const float* params, tfep_par
 
 /* VJP of tfep_moebius_forward (moebius.py:374-478): gparams / gx (B, D), same `sign` as the forward. */
 int tfep_moebius_backward(const float* x, int64_t ldx, const float* params, int64_t ldp,
-                          int dimension, float max_radius, int unit_sphere, int sign,
+                          int dimension, double max_radius, int unit_sphere, int sign,
                           const float* gy, int64_t ldgy, const float* g_log_det_J,
                           float* gparams, int64_t ldgp, float* gx, int64_t ldgx,
                           int B, int D, void* stream);

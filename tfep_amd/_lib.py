@@ -51,7 +51,7 @@ class InverseBlockDesc(Structure):
                 ('emb_lower', c_float), ('emb_upper', c_float),
                 ('cache_col0', c_int32 * 4), ('cache_n_old', c_int32 * 4),
                 ('cache_len', c_int32), ('max_feats', c_int32), ('spline', c_void_p),
-                ('moebius_dim', c_int32), ('moebius_unit_sphere', c_int32), ('moebius_max_radius', c_float),
+                ('moebius_dim', c_int32), ('moebius_unit_sphere', c_int32), ('moebius_max_radius', c_double),
                 ('rows_per_wave', c_int32), ('n_spline_groups', c_int32), ('waves_per_workgroup', c_int32), ('paired', c_int32),
                 ('n_blocks', c_int32), ('blocks', c_void_p), ('z_extra', c_void_p * 4), ('zout_extra', c_void_p),
                 ('ws', c_void_p * 5), ('ldws', c_int64 * 5), ('ws_inv_scale', c_void_p * 5), ('h_inv_scale', c_void_p * 5)]
@@ -64,7 +64,7 @@ class MafLayerDesc(Structure):
                 ('scratch', c_void_p * 2), ('ld_scratch', c_int64), ('kind', c_int32),
                 ('x', c_void_p), ('ldx', c_int64), ('y', c_void_p), ('ldy', c_int64), ('log_det_J', c_void_p),
                 ('n_features', c_int32), ('moebius_dim', c_int32), ('moebius_unit_sphere', c_int32),
-                ('moebius_max_radius', c_float)]
+                ('moebius_max_radius', c_double)]
 
 
 class SplineDesc(Structure):
@@ -174,7 +174,7 @@ _SIGNATURES = {
                                     _P, c_int, c_int, c_int, _P]),
     'tfep_spline_inverse': (c_int, [_P, c_int64, _P, ParamLayout, POINTER(SplineDesc), _P, c_int64,
                                     _P, c_int, c_int, c_int, _P]),
-    'tfep_moebius_forward_split_out': (c_int, [_P, c_int64, _P, c_int64, c_float, _P, c_int64, _P, c_int, _P, c_int64, _P,
+    'tfep_moebius_forward_split_out': (c_int, [_P, c_int64, _P, c_int64, c_double, _P, c_int64, _P, c_int, _P, c_int64, _P,
                                                c_int, c_int, _P]),
     'tfep_periodic_embedding': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_float, c_float,
                                         _P, c_int64, c_int, _P]),
@@ -293,9 +293,9 @@ for _s in ('', '_f64'):
                                                   c_int, _P]),
         'tfep_symmetrized_moebius_backward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, _P, c_int64, _P, _P,
                                                            c_int64, _P, c_int64, c_int, c_int, _P]),
-        'tfep_moebius_forward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, c_double if _s else c_float, c_int, c_int,
+        'tfep_moebius_forward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, c_int,
                                               _P, c_int64, _P, c_int, c_int, c_int, _P]),
-        'tfep_moebius_backward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, c_double if _s else c_float, c_int, c_int, _P,
+        'tfep_moebius_backward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, c_double, c_int, c_int, _P,
                                                c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int, _P]),
         'tfep_quaternion_product' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int, c_int, c_int, _P]),
         'tfep_quaternion_product_backward' + _s: (c_int, [_P, c_int64, _P, c_int64, c_int, _P, c_int64, _P, c_int64, _P, c_int64,

@@ -665,7 +665,7 @@ constexpr int MOEBIUS_MAX_DIM_B = 8;
 template <typename T>
 __global__ void __launch_bounds__(256) moebius_backward_kernel(const T* __restrict__ x, int64_t ldx,
                                                                const T* __restrict__ params, int64_t ldp, int dim,
-                                                               T max_radius, int unit_sphere, T sign,
+                                                               double max_radius, int unit_sphere, T sign,
                                                                const T* __restrict__ gy, int64_t ldgy,
                                                                const T* __restrict__ gldj,
                                                                T* __restrict__ gparams, int64_t ldgp,
@@ -690,7 +690,7 @@ __global__ void __launch_bounds__(256) moebius_backward_kernel(const T* __restri
                 nx2 += xv[i] * xv[i];
             }
         const double nw = sqrt(nw2), nx = sqrt(nx2);
-        const double s = (double)max_radius / (1.0 + nw) * (unit_sphere ? 1.0 : nx);
+        const double s = max_radius / (1.0 + nw) * (unit_sphere ? 1.0 : nx);
         double nu2 = 0.0, Dd = 0.0;
 #pragma unroll
         for (int i = 0; i < MOEBIUS_MAX_DIM_B; ++i)
@@ -902,7 +902,7 @@ static int launch_periodic_embedding_backward(const char* who, const T* x, int64
 
 template <typename T>
 static int launch_moebius_backward(const char* who, const T* x, int64_t ldx, const T* params, int64_t ldp, int dimension,
-                                   T max_radius, int unit_sphere, int sign, const T* gy, int64_t ldgy, const T* gl, T* gparams,
+                                   double max_radius, int unit_sphere, int sign, const T* gy, int64_t ldgy, const T* gl, T* gparams,
                                    int64_t ldgp, T* gx, int64_t ldgx, int B, int D, void* stream) {
     TFEP_REQUIRE(dimension >= 1 && dimension <= MOEBIUS_MAX_DIM_B, "%s: dimension=%d unsupported", who, dimension);
     TFEP_REQUIRE(D % dimension == 0 && (sign == 1 || sign == -1), "%s: bad arguments", who);
@@ -1041,7 +1041,7 @@ int tfep_spline_backward(const float* x, int64_t ldx, const float* params, tfep_
 }
 
 int tfep_moebius_backward(const float* x, int64_t ldx, const float* params, int64_t ldp, int dimension,
-                          float max_radius, int unit_sphere, int sign, const float* gy, int64_t ldgy,
+                          double max_radius, int unit_sphere, int sign, const float* gy, int64_t ldgy,
                           const float* g_log_det_J, float* gparams, int64_t ldgp, float* gx, int64_t ldgx, int B, int D,
                           void* stream) {
     return launch_moebius_backward("moebius_backward", x, ldx, params, ldp, dimension, max_radius, unit_sphere, sign, gy, ldgy,

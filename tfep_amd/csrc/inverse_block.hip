@@ -58,7 +58,7 @@ struct InverseBlockArgs {
     int stage_gstride;            // floats per 8-row group of the LDS weight stage
     int lds_floats;               // whole dynamic LDS allocation (a multiple of 4)
     int mb_dim, mb_unit_sphere;   // kind 2: Moebius
-    float mb_max_radius;
+    double mb_max_radius;
     SplineArgs sp;
     SplineArgs spg[IB_MAX_GROUPS];   // kind 3: one per member; the step record names the member of its features
 };
@@ -410,7 +410,7 @@ __global__ void __launch_bounds__(64) inverse_block_kernel(InverseBlockArgs a) {
                         yv[i] = (double)a.y[r * a.ldy + a.feat_sel[foff + f + i]];
                         wv[i] = (double)(-acc[i]);
                     }
-                ldj_acc += moebius_vector(yv, wv, dim, a.mb_max_radius, a.mb_unit_sphere, xv);
+                ldj_acc += moebius_vector<float>(yv, wv, dim, a.mb_max_radius, a.mb_unit_sphere, xv);
 #pragma unroll
                 for (int i = 0; i < MOEBIUS_MAX_DIM; ++i)
                     if (i < dim) emit(foff + f + i, (float)xv[i]);
@@ -880,7 +880,7 @@ __global__ void __launch_bounds__(512) inverse_block_q4_kernel(InverseBlockArgs 
                             yv[i] = (double)a.y[r * a.ldy + a.feat_sel[foff + f + i]];
                             wv[i] = (double)(-acc[i]);
                         }
-                    ldj_acc += moebius_vector(yv, wv, dim, a.mb_max_radius, a.mb_unit_sphere, xv);
+                    ldj_acc += moebius_vector<float>(yv, wv, dim, a.mb_max_radius, a.mb_unit_sphere, xv);
 #pragma unroll
                     for (int i = 0; i < MOEBIUS_MAX_DIM; ++i)
                         if (i < dim) emit(foff + f + i, (float)xv[i]);
@@ -1754,7 +1754,7 @@ __global__ void __launch_bounds__(128 * PAIRS) inverse_superblock_kernel
                                 yv[i] = (double)ytab[(floc + f + i) * Q4_ROWS + s];
                                 wv[i] = (double)(-acc[i]);
                             }
-                        ldj_acc += moebius_vector(yv, wv, dim, a.mb_max_radius, a.mb_unit_sphere, xv);
+                        ldj_acc += moebius_vector<float>(yv, wv, dim, a.mb_max_radius, a.mb_unit_sphere, xv);
 #pragma unroll
                         for (int i = 0; i < MOEBIUS_MAX_DIM; ++i)
                             if (i < dim) emit(floc + f + i, (float)xv[i]);

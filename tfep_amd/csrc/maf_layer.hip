@@ -57,7 +57,7 @@ struct MafLayerArgs {
     const int32_t* k_ranges[ML_MAX_LINEARS];
     float* h[2]; int64_t ldh;                                           // scratch split rows (ping-pong between layers)
     const float* x; int64_t ldx; float* y; int64_t ldy; float* ldj;
-    int n_features, mb_unit_sphere; float mb_max_radius;
+    int n_features, mb_unit_sphere; double mb_max_radius;
 };
 
 // The k-loop of split_gemm_kernel (same schedule: B fragments two column groups ahead, the next tile's LDS-DMA one
@@ -329,7 +329,7 @@ __global__ void __launch_bounds__(STHREADS, ML_OCC) maf_layer_moebius2_kernel(Ma
                         xd[1] = (double)xcur[1];
                         wd[0] = ok ? (double)p2[0] : 0.0;
                         wd[1] = ok ? (double)p2[1] : 0.0;
-                        double ld = moebius_vector(xd, wd, 2, a.mb_max_radius, UNIT ? 1 : 0, yd);
+                        double ld = moebius_vector<float>(xd, wd, 2, a.mb_max_radius, UNIT ? 1 : 0, yd);
                         if (ok) *(f32x2_alias*)(a.y + (int64_t)row * a.ldy + col) = (f32x2){(float)yd[0], (float)yd[1]};
                         ld = ok ? ld : 0.0;
 #pragma unroll

@@ -18,12 +18,12 @@ constexpr int MOEBIUS_MAX_DIM = 8;
 // HBM traffic; 0.30 ms now)
 // xv: the point, wv: the (signed: the inverse is the map with -w, moebius.py:142-147) raw parameter vector, rescaled
 // in place; yv: the image.  Returns log|det J|.
-// T is the element type of the kernel, which is also the type of its max_radius argument (the float32 call sites deduce
-// it from there): float kernels take the ~1 ulp helpers, double kernels IEEE division, square root and logarithm
-// (SymMath<T>, fp64_fast.h).
+// T is the element type of the kernel, named at every call site: float kernels take the ~1 ulp helpers, double kernels IEEE
+// division, square root and logarithm (SymMath<T>, fp64_fast.h).  max_radius is a double for both: the arithmetic is fp64,
+// and 0.99 rounded to float32 (a relative 1e-8) moves the derivative of a vector with c = 197 by 1e-6.
 template <typename T>
 __device__ __forceinline__ double moebius_vector(const double (&xv)[MOEBIUS_MAX_DIM], double (&wv)[MOEBIUS_MAX_DIM], int dim,
-                                                 T max_radius, int unit_sphere, double (&yv)[MOEBIUS_MAX_DIM]) {
+                                                 double max_radius, int unit_sphere, double (&yv)[MOEBIUS_MAX_DIM]) {
     using M = SymMath<T>;
     double dv[MOEBIUS_MAX_DIM];
     double wn2 = 0.0, xn2 = 0.0;
@@ -34,7 +34,7 @@ __device__ __forceinline__ double moebius_vector(const double (&xv)[MOEBIUS_MAX_
             xn2 += xv[i] * xv[i];
         }
     const double wn = M::sqrt(wn2);
-    double resc = (double)max_radius * M::rcp(1.0 + wn);       // moebius.py:437-441
+    double resc = max_radius * M::rcp(1.0 + wn);       // moebius.py:437-441
     double xn = 1.0;
     if (!unit_sphere) {
         xn = M::sqrt(xn2);

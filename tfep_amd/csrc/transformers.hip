@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(256) spline_kernel(const float* __restrict__ x
 template <typename T, int DIM>
 __global__ void __launch_bounds__(256) moebius_kernel(const T* __restrict__ x, int64_t ldx,
                                                       const T* __restrict__ params, int64_t ldp, int dim_rt,
-                                                      T max_radius, int unit_sphere, T sign,
+                                                      double max_radius, int unit_sphere, T sign,
                                                       T* __restrict__ y, int64_t ldy, T* __restrict__ ldj,
                                                       int accumulate, int B, int D, uint32_t* __restrict__ y_split = nullptr,
                                                       int64_t ld_split = 0, float* __restrict__ y_inv_scale = nullptr) {
@@ -384,7 +384,7 @@ static int launch_sos(const char* who, const T* x, int64_t ldx, const T* params,
 }
 
 template <typename T>
-static int launch_moebius(const char* who, const T* x, int64_t ldx, const T* params, int64_t ldp, int dimension, T max_radius,
+static int launch_moebius(const char* who, const T* x, int64_t ldx, const T* params, int64_t ldp, int dimension, double max_radius,
                           int unit_sphere, int sign, T* y, int64_t ldy, T* ldj, int accumulate, int B, int D, void* stream) {
     TFEP_REQUIRE(B == 0 || (x && params && y), "%s: x/params/y must be non-NULL", who);
     TFEP_REQUIRE(dimension >= 1 && dimension <= MOEBIUS_MAX_DIM, "%s: dimension=%d unsupported (1..%d)", who, dimension,
@@ -579,7 +579,7 @@ int tfep_spline_inverse(const float* y, int64_t ldy, const float* params, tfep_p
 }
 
 int tfep_moebius_forward(const float* x, int64_t ldx, const float* params, int64_t ldp, int dimension,
-                         float max_radius, int unit_sphere, int sign, float* y, int64_t ldy, float* log_det_J,
+                         double max_radius, int unit_sphere, int sign, float* y, int64_t ldy, float* log_det_J,
                          int accumulate, int B, int D, void* stream) {
     return launch_moebius("moebius", x, ldx, params, ldp, dimension, max_radius, unit_sphere, sign, y, ldy, log_det_J,
                           accumulate, B, D, stream);
@@ -617,7 +617,7 @@ int tfep_quaternion_product_f64(const double* x, int64_t ldx, const double* para
                            stream);
 }
 
-int tfep_moebius_forward_split_out(const float* x, int64_t ldx, const float* params, int64_t ldp, float max_radius, float* y, int64_t ldy,
+int tfep_moebius_forward_split_out(const float* x, int64_t ldx, const float* params, int64_t ldp, double max_radius, float* y, int64_t ldy,
                                    float* log_det_J, int accumulate, void* y_split, int64_t ld_split, float* y_inv_scale, int B, int D,
                                    void* stream) {
     TFEP_REQUIRE(B == 0 || (x && params && y && y_split && y_inv_scale), "moebius_split_out: NULL pointer");

@@ -325,7 +325,9 @@ def moebius_split_out(x, parameters, max_radius, cols_padded):
     B, D = x.shape
     parameters, ldp = _check_params(parameters, B, D)
     if ldx % 2 or ldp % 2 or x.data_ptr() % 8 or parameters.data_ptr() % 8:
-        x, ldx, parameters, ldp = x.contiguous(), D, parameters.contiguous(), D
+        # (copies, not .contiguous(): a single row counts as contiguous wherever it starts and would keep its pointer)
+        x, parameters = (t.clone(memory_format=torch.contiguous_format) for t in (x, parameters))
+        ldx = ldp = D
     y = torch.empty(B, D, dtype=x.dtype, device=x.device)
     ldj = torch.empty(B, dtype=x.dtype, device=x.device)
     ys = zeros(B, cols_padded, dtype=torch.float32, device=x.device) if cols_padded > D else \
