@@ -7,11 +7,18 @@ bound; tests/test_spline_cases_host.py holds cases and restatement to their own 
    for K <= 16, unstaged above), the latter also inside a padded wider buffer, strided ``x`` views, a row alone;
 3. the fused epilogue (``rq_spline_forward_full``: the ``exact`` and ``split`` paths of a MAF layer) and the blocked inverse
    (``rq_spline_inverse_selects``) at KNOWN parameters: a layer with zero conditioner weights hands every sample its output
-   bias.
+   bias;
+4. the stand-alone kernels, the default-layout VJP and the super-block kernel of the blocked inverse against the BITS the
+   commit before the shared steps of ``csrc/spline.h`` gave (``tests/golden/spline_core_parent.json``, written from that commit
+   by tools/dump_spline_digests.py, whose functions the test runs).
 
 Every bound is that of ``spline_cases`` (values per element and log-det per sample: ``value_errors`` returns the error in
 units of its bound; gradients: ``grad_bounds``); every test prints the error it saw in those units (bound: 1).
 """
+import importlib.util
+import os
+import sys
+
 import pytest
 import torch
 
@@ -226,3 +233,25 @@ def test_blocked_inverse_at_known_parameters(name):
             print(f'    the same bits as the pass per degree: x {torch.equal(xb, xd)}, log-det {torch.equal(lb, ld)}')
             if not (schedule == 'super_kernel' and specialised):
                 assert torch.equal(xb, xd), (name, rows, waves, paired, split, schedule, float((xb - xd).abs().max()))
+
+
+# ------------------------------------------------------------------ 4. the bits of the parent commit
+
+def test_the_bits_of_the_parent_commit():
+    """SHA-256 of the raw bytes of every output of ``ops.spline`` (both directions), of ``ops.spline_backward`` in the default
+    layout and -- on the cases of ``test_blocked_inverse_at_known_parameters`` that take it -- of the super-block kernel, case
+    by case, against the digests recorded from the commit before the evaluators were rebuilt from shared steps."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('dump_spline_digests', os.path.join(root, 'tools', 'dump_spline_digests.py'))
+    dump = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(dump)
+    want = dump.load()
+    assert sorted(want) == sorted(sc.NAMES) and sum('super_x' in d for d in want.values()) == 13
+    differ = {}
+    for name in sc.NAMES:
+        got = dump.case_digests(name, sc, sys.modules[__name__])
+        assert sorted(got) == sorted(want[name]), name
+        bad = [k for k in sorted(got) if got[k] != want[name][k]]
+        if bad:
+            differ[name] = bad
+    assert differ == {}, f'other bits than the parent commit: {differ}'

@@ -148,12 +148,6 @@ __global__ void __launch_bounds__(256) affine_backward_kernel(const T* __restric
 }
 
 // ---------------------------------------------------------------- RQ spline backward
-struct SplineArgsB {
-    const float *x0, *xf, *y0, *yf;
-    SplineFlags f;
-    int P;
-};
-
 // sigmoid on the softmax's exponential (both signs through exp of a non-positive argument) and the hardware-seeded
 // reciprocal: ~1e-11 relative, a fifth of the instructions of exp() + an IEEE division
 __device__ inline double sigmoid_d(double z) {
@@ -172,46 +166,15 @@ __device__ inline void rq_spline_backward(const float (&w)[KMAX], const float (&
                                           double* gxin) {
     const int K = f.K;
     const double mb = (double)f.min_bin;
-    // domain (spline.py:384-410), as in rq_spline_element
-    double x0 = x0f, y0 = y0f;
-    double W = (double)xff - (double)x0f - K * mb, H = (double)yff - (double)y0f - K * mb;
+    // the preamble of rq_spline_element, from the steps of spline.h
+    double x0, y0, W, H;
+    spline_domain(f, K, last, last2, x0f, xff, y0f, yff, x0, y0, W, H);
     const bool learn = f.learn_lower || f.learn_upper;
-    if (learn) {
-        const double scale = exp((double)last);
-        W *= scale;
-        H *= scale;
-        if (f.learn_lower && f.learn_upper) {
-            x0 += (double)last2;
-            y0 += (double)last2;
-        } else if (f.learn_lower) {
-            x0 = (double)xff - W - K * mb;
-            y0 = (double)yff - H - K * mb;
-        }
-    }
     double gx0 = 0.0, gy0 = 0.0, gWt = 0.0, gHt = 0.0;   // grads w.r.t. x0', y0' and extra direct terms of W, H
     double v = vin;
-    if (f.circular) v = py_mod(v - x0 + (double)last, (double)xff - x0) + x0;
-
-    float mw = -INFINITY, mh = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-        if (k < K) {
-            mw = fmaxf(mw, w[k]);
-            mh = fmaxf(mh, h[k]);
-        }
-    double pw[KMAX], ph[KMAX];
-    double sw = 0.0, sh = 0.0;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        pw[k] = 0.0;
-        ph[k] = 0.0;
-        if (k < K) {
-            pw[k] = exp_nonpos((double)w[k] - (double)mw);
-            ph[k] = exp_nonpos((double)h[k] - (double)mh);
-            sw += pw[k];
-            sh += ph[k];
-        }
-    }
+    if (f.circular) v = spline_wrap<1>(v, x0, last, xff);
+    double pw[KMAX], ph[KMAX], sw, sh;
+    spline_softmax_exps<KMAX>(w, h, K, pw, ph, sw, sh);
     {
         const double isw = fast_rcp64(sw), ish = fast_rcp64(sh);       // (sums >= 1: the largest term is exp(0))
 #pragma unroll
@@ -254,7 +217,6 @@ __device__ inline void rq_spline_backward(const float (&w)[KMAX], const float (&
     gd[KMAX] = 0.0;
     double gv;
 
-    auto slope = [&](float r) { return (double)(softplus_f(r + f.slope_offset) + f.min_slope); };
     if (lower_tail || !found) {
         // y = y_b + d (v - x_b), ld = log d; the boundary knot is a constant of the softmax outputs
         float rs = sraw[0];
@@ -265,7 +227,7 @@ __device__ inline void rq_spline_backward(const float (&w)[KMAX], const float (&
                 if (k == K - 1) rs = sraw[k + 1];
             jb = K;
         }
-        const double d = slope(rs);
+        const double d = spline_slope(f, rs);
         const double bx = lower_tail ? x0 : kx;
         const double gdb = gy * (v - bx) + gl * fast_rcp64(d);
         ja = jb;
@@ -289,7 +251,7 @@ __device__ inline void rq_spline_backward(const float (&w)[KMAX], const float (&
                 rs0 = sraw[k];
                 rs1 = sraw[k + 1];
             }
-        const double dk = slope(rs0), dk1 = slope(rs1);
+        const double dk = spline_slope(f, rs0), dk1 = spline_slope(f, rs1);
         ja = kbin;
         jb2 = kbin + 1;
         sga = sigmoid_d((double)rs0 + (double)f.slope_offset);
@@ -367,7 +329,7 @@ __device__ inline void rq_spline_backward(const float (&w)[KMAX], const float (&
 template <int KMAX>
 __global__ void __launch_bounds__(256, 3) spline_backward_kernel(const float* __restrict__ x, int64_t ldx,
                                                               const float* __restrict__ params, tfep_param_layout L,
-                                                              SplineArgsB a, const float* __restrict__ gy, int64_t ldgy,
+                                                              SplineArgs a, const float* __restrict__ gy, int64_t ldgy,
                                                               const float* __restrict__ gldj,
                                                               float* __restrict__ gparams, tfep_param_layout GL,
                                                               float* __restrict__ gx, int64_t ldgx, int B, int D) {
@@ -1023,7 +985,7 @@ int tfep_spline_backward(const float* x, int64_t ldx, const float* params, tfep_
     TFEP_REQUIRE(B >= 0 && D >= 0, "spline_backward: negative size");
     if (B == 0 || D == 0) return TFEP_OK;
     TFEP_REQUIRE(x && params && gy && gparams && gx && d->x0 && d->xf && d->y0 && d->yf, "spline_backward: NULL pointer");
-    SplineArgsB a;
+    SplineArgs a;
     a.x0 = d->x0; a.xf = d->xf; a.y0 = d->y0; a.yf = d->yf;
     a.f.K = d->n_bins; a.f.circular = d->circular != 0; a.f.identity = d->identity_boundary_slopes != 0;
     a.f.learn_lower = d->learn_lower_bound != 0; a.f.learn_upper = d->learn_upper_bound != 0;

@@ -27,11 +27,9 @@ struct SplineFlags {
     float slope_offset;   // log(exp(1 - min_slope) - 1), spline.py:414
 };
 
-// exp(x) for x <= 0 (softmax arguments after subtracting the maximum), fp64, relative error < 1e-11:
-// one-constant range reduction + degree-9 Taylor + v_ldexp_f64.  About 4x fewer instructions than the
-// library exp(): the 16 softmax exponentials dominate the fused epilogue.
-__device__ inline double exp_nonpos(double x) {
-    x = fmax(x, -700.0);
+// exp(x) for |x| <= 700, fp64, relative error < 1e-11: one-constant range reduction + degree-9 Taylor + v_ldexp_f64.  About 4x
+// fewer instructions than the library exp(), and none of its registers.  The callers clamp.
+__device__ __forceinline__ double exp_reduced(double x) {
     const double n = rint(x * 1.4426950408889634);
     const double r = fma(n, -0.69314718055994530942, x);
     double p = 1.0 / 362880.0;
@@ -46,25 +44,10 @@ __device__ inline double exp_nonpos(double x) {
     p = fma(p, r, 1.0);
     return ldexp(p, (int)n);
 }
-
-// exp(x) for |x| <= 700 by the same reduction and polynomial (relative error < 1e-11): the scale of a learnable domain
-// in the fused epilogue, where the library exp() costs registers the 512-register GEMM wave does not have.
-__device__ inline double exp_poly(double x) {
-    x = fmin(fmax(x, -700.0), 700.0);
-    const double n = rint(x * 1.4426950408889634);
-    const double r = fma(n, -0.69314718055994530942, x);
-    double p = 1.0 / 362880.0;
-    p = fma(p, r, 1.0 / 40320.0);
-    p = fma(p, r, 1.0 / 5040.0);
-    p = fma(p, r, 1.0 / 720.0);
-    p = fma(p, r, 1.0 / 120.0);
-    p = fma(p, r, 1.0 / 24.0);
-    p = fma(p, r, 1.0 / 6.0);
-    p = fma(p, r, 0.5);
-    p = fma(p, r, 1.0);
-    p = fma(p, r, 1.0);
-    return ldexp(p, (int)n);
-}
+// x <= 0: softmax arguments after subtracting the maximum (the 16 softmax exponentials dominate the fused epilogue)
+__device__ inline double exp_nonpos(double x) { return exp_reduced(fmax(x, -700.0)); }
+// any x: the scale of a learnable domain in the fused epilogue, where the 512-register GEMM wave has no room for exp()
+__device__ inline double exp_poly(double x) { return exp_reduced(fmin(fmax(x, -700.0), 700.0)); }
 
 __device__ inline float softplus_f(float z) {
     // torch softplus, beta = 1, threshold = 20 (spline.py:415).
@@ -90,6 +73,83 @@ __host__ __device__ inline int spline_n_params(int K, bool circular, bool identi
     return n;
 }
 
+// ---------------------------------------------------------------- the steps every evaluator is composed of
+// (rq_spline_element below; rq_spline_backward in backward.hip).  Each formula stands here once; the
+// order of the operations is part of the contract (the kernels are held to recorded bits).  `K` is passed beside the flags
+// because the fused epilogue knows it at compile time.
+
+// Knot slope of a raw parameter: softplus in fp32 (spline.py:414-415).
+__device__ __forceinline__ double spline_slope(const SplineFlags& f, float raw) {
+    return (double)(softplus_f(raw + f.slope_offset) + f.min_slope);
+}
+
+// Domain (spline.py:384-410): lower corner (x0, y0) and the width / height W, H left for the softmax shares.
+__device__ __forceinline__ void spline_domain(const SplineFlags& f, int K, float last, float last2, float x0f, float xff,
+                                              float y0f, float yff, double& x0, double& y0, double& W, double& H) {
+    const double mb = (double)f.min_bin;
+    x0 = x0f;
+    y0 = y0f;
+    W = (double)xff - (double)x0f - K * mb;
+    H = (double)yff - (double)y0f - K * mb;
+    if (f.learn_lower || f.learn_upper) {                                         // wave-uniform
+        const double scale = exp((double)last);
+        W *= scale;
+        H *= scale;
+        if (f.learn_lower && f.learn_upper) {
+            x0 += (double)last2;
+            y0 += (double)last2;
+        } else if (f.learn_lower) {
+            x0 = (double)xff - W - K * mb;
+            y0 = (double)yff - H - K * mb;
+        }
+    }
+}
+
+// Circular shift (xf fixed for circular splines): SIGN = +1 on the input of the forward map (spline.py:236-238), -1 on the
+// output of the inverse (spline.py:257-259).
+template <int SIGN>
+__device__ __forceinline__ double spline_wrap(double v, double x0, float last, float xff) {
+    return py_mod(SIGN > 0 ? v - x0 + (double)last : v - x0 - (double)last, (double)xff - x0) + x0;
+}
+
+// Softmax numerators (spline.py:394-395): exponentials of widths / heights minus their maximum, and their sums.  In fp64: a
+// 1-ulp fp32 softmax moves the knots by ~2e-7 of the domain, which a narrow bin amplifies to > 1e-5 in the log-derivative.
+// (The `k < K` predicates are wave-uniform.)
+template <int KMAX>
+__device__ __forceinline__ void spline_softmax_exps(const float (&w)[KMAX], const float (&h)[KMAX], int K, double (&ew)[KMAX],
+                                                    double (&eh)[KMAX], double& sw, double& sh) {
+    float mw = -INFINITY, mh = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+        if (k < K) {
+            mw = fmaxf(mw, w[k]);
+            mh = fmaxf(mh, h[k]);
+        }
+    sw = 0.0;
+    sh = 0.0;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        ew[k] = 0.0;
+        eh[k] = 0.0;
+        if (k < K) {
+            ew[k] = exp_nonpos((double)w[k] - (double)mw);
+            eh[k] = exp_nonpos((double)h[k] - (double)mh);
+            sw += ew[k];
+            sh += eh[k];
+        }
+    }
+}
+
+// Argument of the log-derivative inside a bin (spline.py:556-558): s^2 (dk1 eps^2 + 2 s eps (1 - eps) + dk (1 - eps)^2) /
+// (s + t eps (1 - eps))^2.
+__device__ __forceinline__ double spline_logd_arg(double s, double t, double dk, double dk1, double eps) {
+    const double e1 = eps * (1.0 - eps);
+    const double om = 1.0 - eps;
+    const double num = s * s * (dk1 * eps * eps + 2.0 * s * e1 + dk * om * om);
+    const double den = s + t * e1;
+    return num / (den * den);
+}
+
 // Evaluate one element.
 //   w[k], h[k]   raw (pre-softmax) widths / heights, k < K
 //   sraw[j]      raw (pre-softplus) slopes of the K+1 knots, already expanded
@@ -104,53 +164,12 @@ __device__ inline double rq_spline_element(const float (&w)[KMAX], const float (
                                            float yff, float vin, double* logd) {
     const int K = f.K;
     const double mb = (double)f.min_bin;
-
-    // ---- domain (spline.py:384-410)
-    double x0 = x0f, y0 = y0f;
-    double W = (double)xff - (double)x0f - K * mb;
-    double H = (double)yff - (double)y0f - K * mb;
-    if (f.learn_lower || f.learn_upper) {
-        double scale = exp((double)last);
-        W *= scale;
-        H *= scale;
-        if (f.learn_lower && f.learn_upper) {
-            x0 += (double)last2;
-            y0 += (double)last2;
-        } else if (f.learn_lower) {
-            x0 = (double)xff - W - K * mb;
-            y0 = (double)yff - H - K * mb;
-        }
-    }
-
+    double x0, y0, W, H;
+    spline_domain(f, K, last, last2, x0f, xff, y0f, yff, x0, y0, W, H);
     double v = vin;
-    if (f.circular && !INVERSE) {
-        // spline.py:236-238 (xf fixed for circular splines)
-        v = py_mod(v - x0 + (double)last, (double)xff - x0) + x0;
-    }
-
-    // ---- softmax normalisation (spline.py:394-395)
-    float mw = -INFINITY, mh = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-        if (k < K) {
-            mw = fmaxf(mw, w[k]);
-            mh = fmaxf(mh, h[k]);
-        }
-    // exp in fp64: a 1-ulp fp32 softmax moves the knots by ~2e-7 of the domain, which a narrow
-    // bin amplifies to > 1e-5 in the log-derivative.
-    double ew[KMAX], eh[KMAX];
-    double sw = 0.0, sh = 0.0;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        ew[k] = 0.0;
-        eh[k] = 0.0;
-        if (k < K) {
-            ew[k] = exp_nonpos((double)w[k] - (double)mw);
-            eh[k] = exp_nonpos((double)h[k] - (double)mh);
-            sw += ew[k];
-            sh += eh[k];
-        }
-    }
+    if (f.circular && !INVERSE) v = spline_wrap<1>(v, x0, last, xff);
+    double ew[KMAX], eh[KMAX], sw, sh;
+    spline_softmax_exps<KMAX>(w, h, K, ew, eh, sw, sh);
     const double iw = W / sw, ih = H / sh;
 
     // ---- bin search: strict '>' (spline.py:622-625).  v <= first knot -> lower tail.
@@ -187,14 +206,12 @@ __device__ inline double rq_spline_element(const float (&w)[KMAX], const float (
     if (lower_tail || !found) {
         // Linear continuation with the boundary slope (spline.py:599-614; reference
         // NumPy oracle tests/nn/transformers/test_spline.py:83-87).
-        const float rs = lower_tail ? sraw[0] : rs_last;
-        const double d = (double)(softplus_f(rs + f.slope_offset) + f.min_slope);
+        const double d = spline_slope(f, lower_tail ? sraw[0] : rs_last);
         const double bx = lower_tail ? x0 : kx, by = lower_tail ? y0 : ky;
         out = INVERSE ? (bx + (v - by) / d) : (by + d * (v - bx));
         ld = (double)logf((float)d);
     } else {
-        const double dk = (double)(softplus_f(rs0 + f.slope_offset) + f.min_slope);
-        const double dk1 = (double)(softplus_f(rs1 + f.slope_offset) + f.min_slope);
+        const double dk = spline_slope(f, rs0), dk1 = spline_slope(f, rs1);
         const double s = bh / bw;                                  // spline.py:643
         const double t = dk1 + dk - 2.0 * s;
         double eps;
@@ -210,17 +227,9 @@ __device__ inline double rq_spline_element(const float (&w)[KMAX], const float (
             const double e1 = eps * (1.0 - eps);
             out = ky + bh * (s * eps * eps + dk * e1) / (s + t * e1);
         }
-        const double e1 = eps * (1.0 - eps);                       // spline.py:556-558
-        const double om = 1.0 - eps;
-        const double num = s * s * (dk1 * eps * eps + 2.0 * s * e1 + dk * om * om);
-        const double den = s + t * e1;
-        ld = (double)logf((float)(num / (den * den)));
+        ld = (double)logf((float)spline_logd_arg(s, t, dk, dk1, eps));
     }
-
-    if (f.circular && INVERSE) {
-        // spline.py:257-259
-        out = py_mod(out - x0 - (double)last, (double)xff - x0) + x0;
-    }
+    if (f.circular && INVERSE) out = spline_wrap<-1>(out, x0, last, xff);
     *logd = ld;
     return out;
 }
@@ -419,6 +428,11 @@ __device__ __forceinline__ void spline_expand(const SplineFlags& f, Get&& get, f
     last2 = get(std::integral_constant<int, P - 2>{});
 }
 
+// (Written out, not composed from the steps above: with spline_slope and spline_domain alone in it, 21 of the fused-epilogue
+// kernels of split_gemm*.hip change their SGPR, VGPR, AGPR or scratch numbers -- profiles/spline_core_resources.md.)
+// rq_spline_inverse_selects above is written out too: with domain, slopes and log-derivative argument from the steps every
+// resource number and instruction count of the super-block kernels stayed, their register assignment did not, and the cfg4
+// inverse timed 0.3 % above the parent's spread.
 // Branch-free forward evaluation for the fused epilogue of the split-f16 GEMM: exactly K bins, the K + 1 slopes
 // already expanded (spline_expand).  The same arithmetic in the same order as rq_spline_element<K, false>
 // (bit-identical results), written as straight-line code with selects: a lone wave on a SIMD has no partner to
