@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from symmoebius_ref import sym_torch
+
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'symmoebius.npz')
 CASES = [(d, R) for d in (2, 3, 4) for R in (0.99, 0.7)]
@@ -51,34 +53,6 @@ def max_err(got, ref):
 
 def _case(g, d, R, dt, *keys):
     return [torch.from_numpy(g[f'tr/d{d}_R{R}/{k}']).cuda().to(dt) for k in keys]
-
-
-def sym_torch(x, w, dim, R, inverse=False):
-    """float64 torch restatement of the reference's two functions (moebius.py:481-629) on (B, D) tensors."""
-    B = x.shape[0]
-    x, w = x.reshape(B, -1, dim), w.reshape(B, -1, dim)
-    xn = x.norm(dim=-1, keepdim=True)
-    wn = w.norm(dim=-1, keepdim=True)
-    u = R / (1 + wn) * w
-    r2 = (u * u).sum(-1, keepdim=True)
-
-    def log_det(xu):
-        q = r2 - (xu * u).sum(-1, keepdim=True) ** 2
-        return torch.log((1 - r2) * (1 + r2) ** (dim - 1) / (4 * q + (1 - r2) ** 2) ** (dim / 2)).squeeze(-1).sum(1)
-    if not inverse:
-        def f(ws):
-            diff = x - ws
-            return (xn ** 2 - (ws * ws).sum(-1, keepdim=True)) / (diff * diff).sum(-1, keepdim=True) * diff - ws
-        s = f(xn * u) + f(-xn * u)
-        return (xn * s / s.norm(dim=-1, keepdim=True)).reshape(B, -1), log_det(x / xn)
-    xu = x / xn
-    da = u / r2.sqrt()
-    a = (xu * da).sum(-1, keepdim=True)
-    db = xu - a * da
-    db = db / db.norm(dim=-1, keepdim=True)
-    a_inv = -a * (r2 + 1) / torch.sqrt(1 + r2 ** 2 + r2 * (4 * a ** 2 - 2))
-    x_inv = -(a_inv * da - torch.sqrt(1 - a_inv ** 2) * db)
-    return (xn * x_inv).reshape(B, -1), -log_det(x_inv)
 
 
 # ------------------------------------------------------------------ the transformer against the golden
