@@ -882,6 +882,62 @@ typedef struct tfep_inverse_chain_vec_f64_desc {
 } tfep_inverse_chain_vec_f64_desc;
 int tfep_inverse_chain_vec_f64(const tfep_inverse_chain_vec_f64_desc* desc, void* stream);
 
+/*
+ * float64 blocked BACKWARD through the inverse of a MAF layer: the in-block chain (tfep_amd/nn/flows/_backward.py:
+ * BlockedInverseBackwardF64; host plan tfep_amd/nn/flows/_blocked_f64_backward.py).  For cotangents (gx, gl) of the
+ * inverse's (x, log_det_J) the gradient with respect to y is the u that solves J^T u + gl grad_x ldj = gx, J the triangular
+ * Jacobian of the forward layer at x.  The solve walks the degrees downwards, in blocks.  Packing as tfep_inverse_chain_f64
+ * (rows and columns of every masked linear sorted by degree); here a mask COLUMN is a suffix [start, n) of the packed rows.
+ * ga[l]: (B, ldga[l]) cotangent of the pre-activation of linear l (ga[n_linears - 1]: of the transformer parameters), zero
+ * where not yet known and in the padding.  At the head of a block one tfep_masked_linear_gemm_f64 per linear forms
+ * G[l][:, block columns] = ga[l][:, R[l]:] wt[l][block columns, R[l]:]^T -- rows all final, R[l] = the first final row rounded
+ * UP to a multiple of 16.  One call of this entry point then walks the n_steps degrees of the block, descending.  Per degree:
+ *   hidden    for l = n_linears - 1 .. 1, columns j of this degree: g = (has_panel ? G[l][b, j] : 0)
+ *             + sum_{r in [start, R[l])} wt[l][j, r] ga[l][b, r];   ga[l - 1][b, j] = g * (h > 0 ? 1 : h + 1), h = h[l][b, j];
+ *   features  g0 = the same sum of linear 0 at column pos(f) (and g1 at pos + 1 of a periodic feature);
+ *             s = g0, or emb_scale (-h[0][b, pos + 1] g0 + h[0][b, pos] g1)   (h[0]: the conditioner inputs (cos t, sin t));
+ *             u[b, f] = (r[b, f] - s) / tau_x[b, f];   ga[L][b, prow0 + p] = A[b, prow0 + p] u[b, f] + c[b, prow0 + p].
+ * r = gx - gl L_x and tau_x in slot order, A = tau_theta and c = gl L_theta in packed-row order: from the transformer's VJP.
+ * Each product is counted once: the panel starts at R, the chain stops there.  Sums run in ascending row order on two
+ * interleaved accumulators, per sample row: results do not depend on the batch a row sits in.  fp64 fma throughout.
+ *
+ * wt[l]: the TRANSPOSED packed weights (columns of linear l x ldwt[l]), zero in the padding.  row0[l]: the first row of the
+ * block; rows [row0, R) are kept in LDS; n_old[l] (< 16): rows [R - n_old, R) come from earlier blocks; lds_row0[l]: running
+ * sum of R - row0.  steps: (n_steps, 20) int32: [slot0, slot1, then (col0, col1, start) per linear l = 0 ..], absolute
+ * indices.  feats: as tfep_inverse_chain_f64.  LDS: tfep_inverse_backward_chain_f64_lds_bytes(sum of R - row0) <= 160 KiB,
+ * else TFEP_ERR_INVALID_ARGUMENT.  64 sample rows per workgroup.  B = 0 and n_steps = 0 are no-ops.
+ */
+typedef struct tfep_inverse_backward_chain_f64_desc {
+    int32_t B, n_linears, n_steps, reserved;
+    double* ga[TFEP_INVERSE_F64_MAX_LINEARS];
+    int64_t ldga[TFEP_INVERSE_F64_MAX_LINEARS];
+    const double* wt[TFEP_INVERSE_F64_MAX_LINEARS];
+    int64_t ldwt[TFEP_INVERSE_F64_MAX_LINEARS];
+    const double* h[TFEP_INVERSE_F64_MAX_LINEARS];
+    int64_t ldh[TFEP_INVERSE_F64_MAX_LINEARS];
+    const double* G[TFEP_INVERSE_F64_MAX_LINEARS];
+    int64_t ldG[TFEP_INVERSE_F64_MAX_LINEARS];
+    int32_t R[TFEP_INVERSE_F64_MAX_LINEARS];
+    int32_t row0[TFEP_INVERSE_F64_MAX_LINEARS];
+    int32_t n_old[TFEP_INVERSE_F64_MAX_LINEARS];
+    int32_t lds_row0[TFEP_INVERSE_F64_MAX_LINEARS];
+    int32_t has_panel[TFEP_INVERSE_F64_MAX_LINEARS];
+    int32_t reserved2;
+    const double* r;
+    const double* tau_x;
+    int64_t ldr;
+    const double* A;
+    const double* c;
+    int64_t ldA;
+    double* u;
+    int64_t ldu;
+    const int32_t* steps;
+    const int32_t* feats;
+    double emb_scale;
+} tfep_inverse_backward_chain_f64_desc;
+int64_t tfep_inverse_backward_chain_f64_lds_bytes(int n_rows_total);
+int tfep_inverse_backward_chain_f64(const tfep_inverse_backward_chain_f64_desc* desc, void* stream);
+
 int tfep_periodic_embedding_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
                                 const int32_t* nonperiodic_indices, int n_nonperiodic,
                                 double lower, double upper, double* out, int64_t ldo, int B, void* stream);

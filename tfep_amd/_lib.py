@@ -95,6 +95,16 @@ class InverseChainVecF64Desc(Structure):
     _fields_ = [('chain', InverseChainF64Desc), ('member_dim', c_int32 * 4), ('member_max_radius', c_double * 4)]
 
 
+class InverseBackwardChainF64Desc(Structure):
+    _fields_ = [('B', c_int32), ('n_linears', c_int32), ('n_steps', c_int32), ('reserved', c_int32),
+                ('ga', c_void_p * 5), ('ldga', c_int64 * 5), ('wt', c_void_p * 5), ('ldwt', c_int64 * 5),
+                ('h', c_void_p * 5), ('ldh', c_int64 * 5), ('G', c_void_p * 5), ('ldG', c_int64 * 5),
+                ('R', c_int32 * 5), ('row0', c_int32 * 5), ('n_old', c_int32 * 5), ('lds_row0', c_int32 * 5),
+                ('has_panel', c_int32 * 5), ('reserved2', c_int32),
+                ('r', c_void_p), ('tau_x', c_void_p), ('ldr', c_int64), ('A', c_void_p), ('c', c_void_p), ('ldA', c_int64),
+                ('u', c_void_p), ('ldu', c_int64), ('steps', c_void_p), ('feats', c_void_p), ('emb_scale', c_double)]
+
+
 class EgnnLayerParams(Structure):
     _fields_ = [('F', c_int32), ('G', c_int32)] + [(k, c_void_p) for k in (
         'dist_means', 'dist_log_gammas', 'msg0_w', 'msg0_b', 'msg2_w', 'msg2_b', 'att_w', 'att_b', 'ux0_w', 'ux0_b',
@@ -266,6 +276,8 @@ _SIGNATURES = {
     'tfep_inverse_chain_f64_lds_bytes': (c_int64, [c_int, c_int, c_int]),
     'tfep_inverse_chain_f64': (c_int, [POINTER(InverseChainF64Desc), _P]),
     'tfep_inverse_chain_vec_f64': (c_int, [POINTER(InverseChainVecF64Desc), _P]),
+    'tfep_inverse_backward_chain_f64_lds_bytes': (c_int64, [c_int]),
+    'tfep_inverse_backward_chain_f64': (c_int, [POINTER(InverseBackwardChainF64Desc), _P]),
     'tfep_periodic_embedding_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double,
                                             _P, c_int64, c_int, _P]),
     'tfep_periodic_embedding_backward_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double, _P, c_int64,

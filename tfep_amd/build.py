@@ -15,7 +15,7 @@ LIB_DIR = os.path.join(HERE, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libtfep_hip.so')
 SOURCES = ['transformers.hip', 'masked_linear.hip', 'split_gemm.hip', 'split_gemm_layouts.hip', 'inverse_block.hip',
            'reduce.hip', 'backward.hip', 'egnn.hip', 'maf_layer.hip', 'masked_linear_f64.hip',
-           'spline_f64.hip', 'inverse_block_f64.hip', 'flipembed.hip', 'frames.hip', 'geometry.hip', 'zmatrix.hip',
+           'spline_f64.hip', 'inverse_block_f64.hip', 'inverse_backward_f64.hip', 'flipembed.hip', 'frames.hip', 'geometry.hip', 'zmatrix.hip',
            'relframe.hip', 'graph_ops.hip', 'edge_ops.hip', 'egnn_param_grad.hip']
 # Per-file flags.  egnn.hip: the edge kernels are bound by vector-instruction issue, and on gfx950 a packed fp32
 # instruction (v_pk_fma_f32 ...) is no cheaper than the two scalar ones it replaces (the fp32 vector peak is reached

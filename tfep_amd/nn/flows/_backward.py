@@ -392,6 +392,7 @@ class LazyInverseFunction(torch.autograd.Function):
     def backward(ctx, gx, gldj):
         (y,) = ctx.saved_tensors
         layer, params = ctx.layer, ctx.params
+        layer.last_inverse_backward_route = 'per_degree'
         with torch.enable_grad():
             y_ = y.detach().requires_grad_(True)
             x2, l2 = generic_inverse(layer, y_)
@@ -408,6 +409,65 @@ class LazyInverseFunction(torch.autograd.Function):
         it = iter(grads[1:])
         gparams = [next(it) if p.requires_grad else None for p in params]
         return (None, gy, *gparams)
+
+
+class BlockedInverseBackwardF64(torch.autograd.Function):
+    """``layer.inverse(y)`` under grad mode with ``layer.blocked_inverse_backward`` on (float64 layers that take the blocked
+    inverse, affine / RQ-spline members only: ``AutoregressiveFlow._blocked_f64_backward_ok``).  The values come from the
+    fast path, as in ``LazyInverseFunction``; the backward is no second differentiable algorithm but one triangular solve
+    with the transposed Jacobian of the FORWARD layer at the ``x`` the inverse returned.  With y = f(x; W) and the outputs
+    (x, -ldj_f(x)), for cotangents (gx, gl):
+
+        g_y = u,   J^T u + gl grad_x ldj_f = gx        (``AutoregressiveFlow._inverse_backward_blocked_f64``:
+                                                        descending blocks of degrees, ``tfep_inverse_backward_chain_f64``)
+        g_W = -(f_W^T u + gl d_W ldj_f)                (minus the parameter side of the forward layer's VJP with (u, gl):
+                                                        ``generic_forward`` under autograd, the float64 training route)
+
+    about one forward + backward of the layer instead of ``n_degrees`` conditioner passes kept for the backward.  Vector-
+    valued members (symmetrized Moebius, quaternion product, Moebius), other embeddings than a PeriodicEmbedding,
+    ``_conditioner_indices`` and float32 layers keep ``LazyInverseFunction``.  Eager only (not captured in a HIP graph);
+    first order only."""
+
+    @staticmethod
+    def forward(ctx, layer, y, *params):
+        with torch.no_grad():
+            x, ldj = layer._inverse_impl(y)
+        ctx.layer, ctx.params = layer, params
+        ctx.save_for_backward(x)
+        return x, ldj
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gx, gldj):
+        (x,) = ctx.saved_tensors
+        layer, params = ctx.layer, ctx.params
+        layer.last_inverse_backward_route = 'blocked_f64'
+        B, D = x.shape
+        like = dict(dtype=torch.float64, device=x.device)
+        wrt = [p for p in params if p.requires_grad]
+        need_gy = ctx.needs_input_grad[1]
+        none = (None, None, *([None] * len(params)))
+        if B == 0:                                          # nothing to launch
+            gy = torch.zeros(0, D, **like) if need_gy else None
+            return (None, gy, *[torch.zeros_like(p) if p.requires_grad else None for p in params])
+        if not need_gy and not wrt:
+            return none
+        x = x.detach().contiguous()
+        gx = ops.zeros(B, D, **like) if gx is None else gx.contiguous()
+        gl = ops.zeros(B, **like) if gldj is None else gldj.contiguous()
+        with torch.no_grad():
+            u = layer._inverse_backward_blocked_f64(x, gx, gl)
+        gparams = [None] * len(params)
+        if wrt:
+            with torch.enable_grad():
+                y2, l2 = generic_forward(layer, x)
+                grads = torch.autograd.grad([y2, l2], wrt, [u, gl], allow_unused=True)
+            it = iter(grads)
+            for i, p in enumerate(params):
+                if p.requires_grad:
+                    g = next(it)
+                    gparams[i] = None if g is None else -g
+        return (None, u if need_gy else None, *gparams)
 
 
 class UnsupportedBackward(torch.autograd.Function):

@@ -580,7 +580,9 @@ class AutoregressiveFlow(torch.nn.Module):
 
         Under autograd (grad mode on and ``y`` or a parameter requires grad) the outputs are differentiable like the
         reference's (``_backward.LazyInverseFunction``: the values still come from the fast path, a backward pays for the
-        reference's pass per degree).  With a MADE conditioner the values come from a blocked forward substitution: pass ``k``
+        reference's pass per degree; opt-in ``blocked_inverse_backward``: a float64 layer with affine / RQ-spline members
+        records ``_backward.BlockedInverseBackwardF64`` instead, whose backward is one blocked triangular solve).  With a
+        MADE conditioner the values come from a blocked forward substitution: pass ``k``
         evaluates only the rows of the three masked linears that belong to degree ``k`` (contiguous
         row slices of the degree-sorted packed weights), so the whole inverse costs about one forward
         in flops instead of ``n_degrees`` forwards (a mixed transformer of affine / spline members: one
@@ -601,6 +603,9 @@ class AutoregressiveFlow(torch.nn.Module):
                 # (one conditioner pass per degree) built from differentiable pieces and back-propagates through it
                 # (flows/_backward.py: LazyInverseFunction, generic_inverse).
                 from . import _backward
+                if self.blocked_inverse_backward and self._blocked_f64_backward_ok():
+                    # opt-in: the backward is one blocked triangular solve (BlockedInverseBackwardF64), no pass per degree
+                    return _backward.BlockedInverseBackwardF64.apply(self, y, *params)
                 return _backward.LazyInverseFunction.apply(self, y, *params)
         return self._inverse_impl(y)
 
@@ -1885,6 +1890,7 @@ class AutoregressiveFlow(torch.nn.Module):
                 return None
             feats[:, 6:8] = links
         fixed = [int(c) for c in self._fixed_indices.cpu().tolist()]
+        plan.update(deg_cols=deg_cols, deg_feat=deg_tr.numpy()[slot_order], p_feat=params_of[slot_order], slot_feature=slot_order)
         plan.update(feats=feats, slot_member=mem[slot_order], slot_local=np.asarray(local_of)[slot_order], members=members,
                     kinds=kinds, row_of_out=row_of_out, pos0=pos0.numpy(), hidden_pos=[p.numpy() for _, p in hidden], limits=limits,
                     fixed_plain=[(c, input_pos(c)) for c in fixed if not periodic[c]],
@@ -1984,16 +1990,8 @@ class AutoregressiveFlow(torch.nn.Module):
         if B == 0:
             return x, ldj
         dp = self._blocked_f64_device_plan(dev, hp)
-        made = self._conditioner
-        made.begin_call()
-        lins = made._linears()
-        L = len(lins) - 1
-        bias = []
-        for l, lin in enumerate(lins):             # packed on every call, like the reference's pre-hook
-            v, g = (lin.weight_v.detach(), lin.weight_g.detach()) if lin.has_weight_norm else (lin._parameters['weight'].detach(), None)
-            ops.masked_weight_prepare(v, g, lin.mask, dp['rows'][l], dp['cols'][l], dp['n_rows'][l], dp['k_pad'][l],
-                                      out=dp['w'][l], clear=False)
-            bias.append(made._pack_bias(lin, dp['rows'][l], dp['n_rows'][l]))
+        L = len(self._conditioner._linears()) - 1
+        bias = self._blocked_f64_pack(dp)
         a = [ops.zeros(B, dp['k_pad'][l], **f64) for l in range(L + 1)]
         cols_f, pos_f = dp['fixed_plain']
         if cols_f.numel():
@@ -2026,6 +2024,172 @@ class AutoregressiveFlow(torch.nn.Module):
             d.zout, d.ldzout = zout.data_ptr(), ldz
             _lib.call(dp['entry'], ctypes.byref(outer), stream)
         return x, ldj
+
+    def _blocked_f64_pack(self, dp):
+        """Packs the masked weights of every linear into ``dp['w']`` (rows and columns sorted by degree) and returns the
+        packed biases: on every call, like the reference's pre-hook."""
+        made = self._conditioner
+        made.begin_call()
+        bias = []
+        for l, lin in enumerate(made._linears()):
+            v, g = (lin.weight_v.detach(), lin.weight_g.detach()) if lin.has_weight_norm else (lin._parameters['weight'].detach(), None)
+            ops.masked_weight_prepare(v, g, lin.mask, dp['rows'][l], dp['cols'][l], dp['n_rows'][l], dp['k_pad'][l],
+                                      out=dp['w'][l], clear=False)
+            bias.append(made._pack_bias(lin, dp['rows'][l], dp['n_rows'][l]))
+        return bias
+
+    # ------------------------------------------------------------------ float64 blocked backward through the inverse
+    #: Opt-in: ``inverse()`` under grad mode records ``_backward.BlockedInverseBackwardF64`` instead of
+    #: ``_backward.LazyInverseFunction`` where the layer qualifies (``_blocked_f64_backward_ok``): the backward is then one
+    #: blocked triangular solve (about one forward + backward of the layer) instead of one conditioner pass per degree.
+    #: Class default False: ``inverse()`` builds the graph it always built.  Can be set per instance.
+    blocked_inverse_backward = False
+
+    #: Which backward the last ``backward()`` through this layer's ``inverse`` ran: ``'blocked_f64'`` or ``'per_degree'``.
+    last_inverse_backward_route = None
+
+    def _blocked_f64_backward_ok(self):
+        """Does a backward through ``inverse()`` take the blocked float64 solve?  The layer takes the float64 blocked inverse
+        (``_blocked_f64_ok``), every member of its transformer is affine or an RQ spline (element-wise: kinds 0 and 1 of the
+        host plan), and the backward plan fits the chain kernel's LDS.  Vector-valued members (symmetrized Moebius, quaternion
+        product, Moebius), other embeddings, ``_conditioner_indices`` and float32 layers keep the pass per degree."""
+        return self._blocked_f64_ok() and self._blocked_f64_backward_plan() is not None
+
+    def _blocked_f64_backward_plan(self):
+        """The host plan of the blocked backward (``flows/_blocked_f64_backward.py``), cached with the forward plan."""
+        hp = self._blocked_f64_host_plan()
+        if hp is None or any(k not in (0, 1) for k in hp['kinds']):
+            return None
+        if 'backward' not in hp:
+            from . import _blocked_f64_backward as bfb
+            hp['backward'] = bfb.fit(hp['deg_cols'], hp['deg_feat'], hp['p_feat'], max(1, int(self.inverse_block_f64)))
+        return hp['backward']
+
+    def _blocked_f64_backward_device_plan(self, device, hp):
+        """Step table, slot index tables and one prefilled descriptor per block of the blocked backward."""
+        bp = hp['backward']
+        key = str(device)
+        bd = bp.setdefault('device', {}).get(key)
+        if bd is not None:
+            return bd
+        import numpy as np
+        dp = self._blocked_f64_device_plan(device, hp)
+        L = bp['n_linears'] - 1
+        steps = torch.from_numpy(np.concatenate([b['steps'] for b in bp['blocks']], axis=0)).to(device)
+        lo, hi = hp['limits']
+        descs, step0 = [], 0
+        for b in bp['blocks']:
+            d = _lib.InverseBackwardChainF64Desc()
+            d.n_linears, d.n_steps = L + 1, len(b['steps'])
+            for l in range(L + 1):
+                d.R[l], d.row0[l], d.n_old[l], d.lds_row0[l] = b['R'][l], b['row0'][l], b['n_old'][l], b['lds_row0'][l]
+                d.has_panel[l] = int(b['R'][l] < bp['n_pad'][l])
+                d.ldga[l], d.ldwt[l], d.ldh[l], d.ldG[l] = bp['n_pad'][l], bp['n_pad'][l], dp['k_pad'][l], dp['k_pad'][l]
+            d.steps = steps.data_ptr() + step0 * steps.shape[1] * 4
+            d.feats = dp['feats'].data_ptr()
+            step0 += len(b['steps'])
+            d.emb_scale = 2.0 * math.pi / (float(hi) - float(lo))
+            descs.append(d)
+        i32 = dict(device=device, dtype=torch.int32)
+        bd = dict(steps=steps, descs=descs, slot_feature=torch.from_numpy(np.asarray(hp['slot_feature'])).to(**i32),
+                  slot_col=torch.from_numpy(hp['feats'][:, 0].copy()).to(**i32))
+        bp['device'][key] = bd
+        return bd
+
+    def _inverse_backward_blocked_f64(self, x, gx, gl):
+        """``g_y`` of ``inverse`` for the cotangents ``(gx, gl)`` of its outputs ``(x, log_det_J)``: the ``u`` that solves
+        ``J^T u + gl grad_x ldj_f = gx`` at ``x`` ("Blocked backward through the float64 inverse").  One conditioner
+        pass on the sorted packs for the activations and the transformer parameters (kept for the solve:
+        ``8 B sum(k_pad)`` bytes, what the forward substitution's own workspaces take), two calls of the transformer's VJP
+        kernel for ``tau_x``, ``tau_theta``, ``gl L_x``, ``gl L_theta``, then per block of degrees, descending, one fp64-MFMA
+        panel GEMM per linear on the transposed packs and one launch of ``tfep_inverse_backward_chain_f64``; one more GEMM for
+        the inputs that no step transforms.  All fp64; a row's bits do not depend on its batch."""
+        from . import _backward
+        hp = self._blocked_f64_host_plan()
+        bp = hp['backward']
+        B, D = x.shape
+        dev = x.device
+        f64 = dict(device=dev, dtype=torch.float64)
+        dp = self._blocked_f64_device_plan(dev, hp)
+        bd = self._blocked_f64_backward_device_plan(dev, hp)
+        made, tr = self._conditioner, self._transformer
+        lins = made._linears()
+        L = len(lins) - 1
+        n_out = lins[-1].out_features
+        n_pad, k_pad = bp['n_pad'], dp['k_pad']
+        stream = _lib.stream_of(x)
+        vp = ctypes.c_void_p
+
+        def gemm(a_ptr, lda, w_ptr, ldw, bias, out_ptr, ldo, N, n_rows_w, k, act=0):
+            _lib.call('tfep_masked_linear_gemm_f64', vp(a_ptr), lda, vp(w_ptr), ldw, bias, None, 0, vp(out_ptr), ldo,
+                      B, N, n_rows_w, k, act, 0, None, 0, stream)
+
+        # ---- weights: the degree-sorted packs and their transposes (rows padded to 16, zero in the padding)
+        bias = self._blocked_f64_pack(dp)
+        wt = [ops.transpose(dp['w'][l], bp['n_rows'][l], k_pad[l], ops.zeros(k_pad[l], n_pad[l], **f64)) for l in range(L + 1)]
+        # ---- one conditioner pass on the sorted packs: a[0] the conditioner inputs, a[l] the ELU outputs, the parameters
+        a = [ops.zeros(B, k_pad[0], **f64)]
+        ops.scatter_columns(made._embed(x).contiguous(), dp['cols'][0], a[0])
+        for l in range(L):
+            a.append(ops.zeros(B, k_pad[l + 1], **f64))
+            gemm(a[l].data_ptr(), k_pad[l], dp['w'][l].data_ptr(), k_pad[l], _lib.ptr(bias[l]), a[l + 1].data_ptr(), k_pad[l + 1],
+                 lins[l].out_features, dp['n_rows'][l], k_pad[l], act=1)
+        theta_p = torch.empty(B, n_out, **f64)
+        gemm(a[L].data_ptr(), k_pad[L], dp['w'][L].data_ptr(), k_pad[L], _lib.ptr(bias[L]), theta_p.data_ptr(), n_out, n_out,
+             dp['n_rows'][L], k_pad[L])
+        theta = ops.gather_columns(theta_p, dp['rows'][L])                 # reference parameter order
+        # ---- the transformer's VJP with cotangents (1, 0) and (0, gl): tau_x, A = tau_theta, gl L_x, c = gl L_theta
+        t = self._tables(dev)
+        x_tr = ops.gather_columns(x, t['tr']) if self.has_fixed_indices else x
+        gx_tr = ops.gather_columns(gx, t['tr']) if self.has_fixed_indices else gx
+        n_tr = x_tr.shape[1]
+        A_ref, c_ref = ops.zeros(B, n_out, **f64), ops.zeros(B, n_out, **f64)
+        tau_x, lx = torch.empty(B, n_tr, **f64), torch.empty(B, n_tr, **f64)
+        _backward.transformer_vjp(tr, x_tr, theta, 0, torch.ones(B, n_tr, **f64), ops.zeros(B, **f64), A_ref, tau_x)
+        _backward.transformer_vjp(tr, x_tr, theta, 0, ops.zeros(B, n_tr, **f64), gl, c_ref, lx)
+        r_s = ops.gather_columns(gx_tr - lx, bd['slot_feature'])
+        tau_s = ops.gather_columns(tau_x, bd['slot_feature'])
+        A, c = ops.zeros(B, n_pad[L], **f64), ops.zeros(B, n_pad[L], **f64)
+        ops.scatter_columns(A_ref, dp['rows'][L], A)
+        ops.scatter_columns(c_ref, dp['rows'][L], c)
+        del theta_p, theta, A_ref, c_ref, tau_x, lx
+        # ---- the descending block loop
+        ga = [ops.zeros(B, n_pad[l], **f64) for l in range(L + 1)]
+        G = [torch.empty(B, k_pad[l], **f64) for l in range(L + 1)]
+        n_slots = len(hp['feats'])
+        u = torch.empty(B, n_slots, **f64)
+        for blk, d in zip(bp['blocks'], bd['descs']):
+            for l in range(L + 1):
+                (c0, c1), R = blk['cols'][l], blk['R'][l]
+                if R >= n_pad[l] or c1 <= c0:
+                    continue
+                # panel: the block's columns of linear l times the final rows [R, n_pad)
+                gemm(ga[l].data_ptr() + 8 * R, n_pad[l], wt[l].data_ptr() + 8 * (c0 * n_pad[l] + R), n_pad[l], None,
+                     G[l].data_ptr() + 8 * c0, k_pad[l], c1 - c0, k_pad[l] - c0, n_pad[l] - R)
+            d.B = B
+            for l in range(L + 1):
+                d.ga[l], d.wt[l], d.h[l], d.G[l] = ga[l].data_ptr(), wt[l].data_ptr(), a[l].data_ptr(), G[l].data_ptr()
+            d.r, d.tau_x, d.ldr = r_s.data_ptr(), tau_s.data_ptr(), n_slots
+            d.A, d.c, d.ldA = A.data_ptr(), c.data_ptr(), n_pad[L]
+            d.u, d.ldu = u.data_ptr(), n_slots
+            _lib.call('tfep_inverse_backward_chain_f64', ctypes.byref(d), stream)
+        # ---- g_y: u at the transformed features; gx - s at the features that no step transforms
+        gy = gx.clone() if self.has_fixed_indices else torch.empty(B, D, **f64)
+        ops.scatter_columns(u, bd['slot_col'], gy)
+        n_fixed = bp['n_fixed']
+        if n_fixed > 0:
+            g0 = torch.empty(B, n_fixed, **f64)
+            gemm(ga[0].data_ptr(), n_pad[0], wt[0].data_ptr(), n_pad[0], None, g0.data_ptr(), n_fixed, n_fixed, k_pad[0], n_pad[0])
+            cols_f, pos_f = dp['fixed_plain']
+            if cols_f.numel():
+                gy[:, cols_f.long()] -= g0[:, pos_f.long()]
+            cols_f, pos_f = dp['fixed_periodic']
+            if cols_f.numel():
+                lo, hi = hp['limits']
+                p = pos_f.long()
+                s = (2.0 * math.pi / (hi - lo)) * (a[0][:, p] * g0[:, p + 1] - a[0][:, p + 1] * g0[:, p])
+                gy[:, cols_f.long()] -= s
+        return gy
 
     def get_transformer_parameters(self, x: torch.Tensor) -> torch.Tensor:
         """Run the conditioner (reference autoregressive.py:231-247)."""
