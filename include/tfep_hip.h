@@ -938,6 +938,43 @@ typedef struct tfep_inverse_backward_chain_f64_desc {
 int64_t tfep_inverse_backward_chain_f64_lds_bytes(int n_rows_total);
 int tfep_inverse_backward_chain_f64(const tfep_inverse_backward_chain_f64_desc* desc, void* stream);
 
+/*
+ * The same backward chain with vector-valued members: a symmetrized Moebius transformer or a quaternion product, alone or as
+ * members of a mixed transformer beside affine / RQ-spline members.  `chain` is read exactly as
+ * tfep_inverse_backward_chain_f64 reads its descriptor (every check of that entry point applies; a feature of a scalar
+ * member, feats[s][6] == 0, runs the same device code in the same summation order: kinds 0 and 1 give the same bits through
+ * either entry point), except that tau_x, A and c may be NULL when no member is of kind 0 or 1.  For a vector v of dimension
+ * k (the links feats[s][6], feats[s][7] of tfep_inverse_chain_vec_f64; a link that leaves the step's [slot0, slot1) ends
+ * the chain), with T = d y_v / d x_v and Theta = d y_v / d theta_v of the forward member, the step is
+ *   g_i = r[b, slot_i] - (the chain sum g0 of linear 0 at column pos(slot_i)),    i = 0 .. k - 1   (r carries gx there),
+ *   u_v = T^-T (g - gl l_x),      q_v = Theta^T u_v + gl l_theta,
+ * obtained without a k x k solve: the member's INVERSE map (y_v, theta_v) -> (x_v, -l) has the VJP, for the cotangents
+ * (g, gl[b]), (g_y, g_theta) = (u_v, -q_v) (differentiate x(y, theta) with d x / d theta = -T^-1 Theta).  One call of
+ * symmoebius_vjp_vector<double, true> (member_kind 2: member_dim[m] in 2 .. 8, 0 < member_max_radius[m] < 1) or
+ * quatprod_vjp_element<double, true> (member_kind 3: member_dim[m] = 4; gl takes no part) per vector, by one wave; it
+ * writes u[b, slot_i] and ga[L][b, prow0(slot_i)] = q_i.  Slots with feats[s][6] > 1 are skipped by their own wave.
+ *   y        (B, ldy): the IMAGES, the input of the inverse, indexed by the feature column feats[s][0] (not x: the
+ *            member's inverse VJP is evaluated at y_v, nothing is recomputed);
+ *   theta    (B, ldtheta): the transformer parameters of the forward layer at x, in packed-row order (row feats[s][3]);
+ *   gl       (B): the cotangent of the inverse's log_det_J.
+ * r, tau_x, A, c at the slots / rows of a vector member are not read (r excepted: it holds gx).  A vector member's features
+ * have P = 1 and periodic = 0 (the caller's guarantee, as in tfep_inverse_chain_vec_f64).  Member kinds 5 / 6 (Moebius) have
+ * no backward chain: they are refused like any unknown kind.  LDS, launch shape and no-ops as the scalar entry point.
+ */
+typedef struct tfep_inverse_backward_chain_vec_f64_desc {
+    tfep_inverse_backward_chain_f64_desc chain;
+    int32_t n_members, reserved;
+    int32_t member_kind[TFEP_INVERSE_F64_MAX_MEMBERS];
+    int32_t member_dim[TFEP_INVERSE_F64_MAX_MEMBERS];
+    double member_max_radius[TFEP_INVERSE_F64_MAX_MEMBERS];
+    const double* y;
+    int64_t ldy;
+    const double* theta;
+    int64_t ldtheta;
+    const double* gl;
+} tfep_inverse_backward_chain_vec_f64_desc;
+int tfep_inverse_backward_chain_vec_f64(const tfep_inverse_backward_chain_vec_f64_desc* desc, void* stream);
+
 int tfep_periodic_embedding_f64(const double* x, int64_t ldx, const int32_t* periodic_indices, int n_periodic,
                                 const int32_t* nonperiodic_indices, int n_nonperiodic,
                                 double lower, double upper, double* out, int64_t ldo, int B, void* stream);

@@ -105,6 +105,12 @@ class InverseBackwardChainF64Desc(Structure):
                 ('u', c_void_p), ('ldu', c_int64), ('steps', c_void_p), ('feats', c_void_p), ('emb_scale', c_double)]
 
 
+class InverseBackwardChainVecF64Desc(Structure):
+    _fields_ = [('chain', InverseBackwardChainF64Desc), ('n_members', c_int32), ('reserved', c_int32),
+                ('member_kind', c_int32 * 4), ('member_dim', c_int32 * 4), ('member_max_radius', c_double * 4),
+                ('y', c_void_p), ('ldy', c_int64), ('theta', c_void_p), ('ldtheta', c_int64), ('gl', c_void_p)]
+
+
 class EgnnLayerParams(Structure):
     _fields_ = [('F', c_int32), ('G', c_int32)] + [(k, c_void_p) for k in (
         'dist_means', 'dist_log_gammas', 'msg0_w', 'msg0_b', 'msg2_w', 'msg2_b', 'att_w', 'att_b', 'ux0_w', 'ux0_b',
@@ -278,6 +284,7 @@ _SIGNATURES = {
     'tfep_inverse_chain_vec_f64': (c_int, [POINTER(InverseChainVecF64Desc), _P]),
     'tfep_inverse_backward_chain_f64_lds_bytes': (c_int64, [c_int]),
     'tfep_inverse_backward_chain_f64': (c_int, [POINTER(InverseBackwardChainF64Desc), _P]),
+    'tfep_inverse_backward_chain_vec_f64': (c_int, [POINTER(InverseBackwardChainVecF64Desc), _P]),
     'tfep_periodic_embedding_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double,
                                             _P, c_int64, c_int, _P]),
     'tfep_periodic_embedding_backward_f64': (c_int, [_P, c_int64, _P, c_int, _P, c_int, c_double, c_double, _P, c_int64,

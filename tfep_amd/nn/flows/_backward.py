@@ -423,23 +423,25 @@ class BlockedInverseBackwardF64(torch.autograd.Function):
         g_W = -(f_W^T u + gl d_W ldj_f)                (minus the parameter side of the forward layer's VJP with (u, gl):
                                                         ``generic_forward`` under autograd, the float64 training route)
 
-    about one forward + backward of the layer instead of ``n_degrees`` conditioner passes kept for the backward.  Vector-
-    valued members (symmetrized Moebius, quaternion product, Moebius), other embeddings than a PeriodicEmbedding,
-    ``_conditioner_indices`` and float32 layers keep ``LazyInverseFunction``.  Eager only (not captured in a HIP graph);
-    first order only."""
+    about one forward + backward of the layer instead of ``n_degrees`` conditioner passes kept for the backward.  Symmetrized
+    Moebius and quaternion-product members take part with ``layer.blocked_inverse_backward_vectors`` on
+    (``tfep_inverse_backward_chain_vec_f64``: a vector's step is ``u_v = T^-T (gx_v - s_v - gl l_x)``,
+    ``q_v = Theta^T u_v + gl l_theta``, both from ONE call of the member's inverse VJP at the saved ``y``); without it, and
+    always for Moebius members, other embeddings than a PeriodicEmbedding, ``_conditioner_indices`` and float32 layers, the
+    layer keeps ``LazyInverseFunction``.  Eager only (not captured in a HIP graph); first order only."""
 
     @staticmethod
     def forward(ctx, layer, y, *params):
         with torch.no_grad():
             x, ldj = layer._inverse_impl(y)
         ctx.layer, ctx.params = layer, params
-        ctx.save_for_backward(x)
+        ctx.save_for_backward(x, y)                     # (y: the vector members' inverse VJP is evaluated there)
         return x, ldj
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gx, gldj):
-        (x,) = ctx.saved_tensors
+        x, y = ctx.saved_tensors
         layer, params = ctx.layer, ctx.params
         layer.last_inverse_backward_route = 'blocked_f64'
         B, D = x.shape
@@ -456,7 +458,7 @@ class BlockedInverseBackwardF64(torch.autograd.Function):
         gx = ops.zeros(B, D, **like) if gx is None else gx.contiguous()
         gl = ops.zeros(B, **like) if gldj is None else gldj.contiguous()
         with torch.no_grad():
-            u = layer._inverse_backward_blocked_f64(x, gx, gl)
+            u = layer._inverse_backward_blocked_f64(x, gx, gl, y=y.detach())
         gparams = [None] * len(params)
         if wrt:
             with torch.enable_grad():

@@ -581,7 +581,8 @@ class AutoregressiveFlow(torch.nn.Module):
         Under autograd (grad mode on and ``y`` or a parameter requires grad) the outputs are differentiable like the
         reference's (``_backward.LazyInverseFunction``: the values still come from the fast path, a backward pays for the
         reference's pass per degree; opt-in ``blocked_inverse_backward``: a float64 layer with affine / RQ-spline members
-        records ``_backward.BlockedInverseBackwardF64`` instead, whose backward is one blocked triangular solve).  With a
+        records ``_backward.BlockedInverseBackwardF64`` instead, whose backward is one blocked triangular solve; with
+        ``blocked_inverse_backward_vectors`` also symmetrized Moebius / quaternion-product members, never Moebius ones).  With a
         MADE conditioner the values come from a blocked forward substitution: pass ``k``
         evaluates only the rows of the three masked linears that belong to degree ``k`` (contiguous
         row slices of the degree-sorted packed weights), so the whole inverse costs about one forward
@@ -2048,27 +2049,40 @@ class AutoregressiveFlow(torch.nn.Module):
     #: Which backward the last ``backward()`` through this layer's ``inverse`` ran: ``'blocked_f64'`` or ``'per_degree'``.
     last_inverse_backward_route = None
 
+    #: Opt-in, on top of ``blocked_inverse_f64_vectors`` and ``blocked_inverse_backward``: the blocked backward also takes
+    #: layers with a ``SymmetrizedMoebiusTransformer`` or a ``QuaternionProductTransformer`` (alone or as members of a mixed
+    #: transformer) through ``tfep_inverse_backward_chain_vec_f64``.  Off: such layers keep the pass per degree, as before.
+    #: A ``MoebiusTransformer`` keeps the pass per degree either way (its VJP is no device function yet).
+    blocked_inverse_backward_vectors = False
+
+    #: (tests) drive a layer of element-wise members through ``tfep_inverse_backward_chain_vec_f64`` too: same bits.
+    _blocked_backward_force_vec = False
+
     def _blocked_f64_backward_ok(self):
         """Does a backward through ``inverse()`` take the blocked float64 solve?  The layer takes the float64 blocked inverse
         (``_blocked_f64_ok``), every member of its transformer is affine or an RQ spline (element-wise: kinds 0 and 1 of the
-        host plan), and the backward plan fits the chain kernel's LDS.  Vector-valued members (symmetrized Moebius, quaternion
-        product, Moebius), other embeddings, ``_conditioner_indices`` and float32 layers keep the pass per degree."""
+        host plan), and the backward plan fits the chain kernel's LDS.  With ``blocked_inverse_backward`` and
+        ``blocked_inverse_backward_vectors`` both on, symmetrized Moebius and quaternion-product members (kinds 2 and 3)
+        qualify too.  Moebius members, other embeddings, ``_conditioner_indices`` and float32 layers keep the pass per degree."""
         return self._blocked_f64_ok() and self._blocked_f64_backward_plan() is not None
 
     def _blocked_f64_backward_plan(self):
-        """The host plan of the blocked backward (``flows/_blocked_f64_backward.py``), cached with the forward plan."""
+        """The host plan of the blocked backward (``flows/_blocked_f64_backward.py``), cached with the forward plan.  The
+        member kinds are judged on every call, outside the cached entry: toggling a flag on a live layer takes effect."""
         hp = self._blocked_f64_host_plan()
-        if hp is None or any(k not in (0, 1) for k in hp['kinds']):
+        vectors = self.blocked_inverse_backward and self.blocked_inverse_backward_vectors
+        if hp is None or any(k not in ((0, 1, 2, 3) if vectors else (0, 1)) for k in hp['kinds']):
             return None
         if 'backward' not in hp:
             from . import _blocked_f64_backward as bfb
             hp['backward'] = bfb.fit(hp['deg_cols'], hp['deg_feat'], hp['p_feat'], max(1, int(self.inverse_block_f64)))
         return hp['backward']
 
-    def _blocked_f64_backward_device_plan(self, device, hp):
-        """Step table, slot index tables and one prefilled descriptor per block of the blocked backward."""
+    def _blocked_f64_backward_device_plan(self, device, hp, vec=False):
+        """Step table, slot index tables and one prefilled descriptor per block of the blocked backward.  ``vec``: descriptors
+        of ``tfep_inverse_backward_chain_vec_f64`` (``outer``: what the entry point takes; ``descs``: their ``chain`` views)."""
         bp = hp['backward']
-        key = str(device)
+        key = (str(device), bool(vec))
         bd = bp.setdefault('device', {}).get(key)
         if bd is not None:
             return bd
@@ -2077,9 +2091,21 @@ class AutoregressiveFlow(torch.nn.Module):
         L = bp['n_linears'] - 1
         steps = torch.from_numpy(np.concatenate([b['steps'] for b in bp['blocks']], axis=0)).to(device)
         lo, hi = hp['limits']
-        descs, step0 = [], 0
+        descs, outer, step0 = [], [], 0
         for b in bp['blocks']:
-            d = _lib.InverseBackwardChainF64Desc()
+            if vec:
+                vd = _lib.InverseBackwardChainVecF64Desc()
+                d = vd.chain                        # (a view: filled below like the scalar descriptor)
+                vd.n_members = len(hp['members'])
+                for g, (t, kind) in enumerate(zip(hp['members'], hp['kinds'])):
+                    vd.member_kind[g] = kind
+                    if kind >= 2:
+                        vd.member_dim[g] = int(t.dimension)
+                        vd.member_max_radius[g] = float(t.max_radius) if kind == 2 else 0.0
+                outer.append(vd)
+            else:
+                d = _lib.InverseBackwardChainF64Desc()
+                outer.append(d)
             d.n_linears, d.n_steps = L + 1, len(b['steps'])
             for l in range(L + 1):
                 d.R[l], d.row0[l], d.n_old[l], d.lds_row0[l] = b['R'][l], b['row0'][l], b['n_old'][l], b['lds_row0'][l]
@@ -2091,19 +2117,24 @@ class AutoregressiveFlow(torch.nn.Module):
             d.emb_scale = 2.0 * math.pi / (float(hi) - float(lo))
             descs.append(d)
         i32 = dict(device=device, dtype=torch.int32)
-        bd = dict(steps=steps, descs=descs, slot_feature=torch.from_numpy(np.asarray(hp['slot_feature'])).to(**i32),
+        bd = dict(steps=steps, descs=descs, outer=outer, slot_feature=torch.from_numpy(np.asarray(hp['slot_feature'])).to(**i32),
                   slot_col=torch.from_numpy(hp['feats'][:, 0].copy()).to(**i32))
         bp['device'][key] = bd
         return bd
 
-    def _inverse_backward_blocked_f64(self, x, gx, gl):
+    def _inverse_backward_blocked_f64(self, x, gx, gl, y=None):
         """``g_y`` of ``inverse`` for the cotangents ``(gx, gl)`` of its outputs ``(x, log_det_J)``: the ``u`` that solves
         ``J^T u + gl grad_x ldj_f = gx`` at ``x`` ("Blocked backward through the float64 inverse").  One conditioner
         pass on the sorted packs for the activations and the transformer parameters (kept for the solve:
         ``8 B sum(k_pad)`` bytes, what the forward substitution's own workspaces take), two calls of the transformer's VJP
         kernel for ``tau_x``, ``tau_theta``, ``gl L_x``, ``gl L_theta``, then per block of degrees, descending, one fp64-MFMA
         panel GEMM per linear on the transposed packs and one launch of ``tfep_inverse_backward_chain_f64``; one more GEMM for
-        the inputs that no step transforms.  All fp64; a row's bits do not depend on its batch."""
+        the inputs that no step transforms.  All fp64; a row's bits do not depend on its batch.
+
+        A layer with symmetrized Moebius or quaternion-product members (``blocked_inverse_backward_vectors``) goes through
+        ``tfep_inverse_backward_chain_vec_f64`` instead: the two VJP calls are made for its element-wise members only, and
+        the kernel evaluates a vector member's own inverse VJP at ``y`` (the images: the input of ``inverse``, kept by
+        ``BlockedInverseBackwardF64.forward``), the packed parameters and ``gl``."""
         from . import _backward
         hp = self._blocked_f64_host_plan()
         bp = hp['backward']
@@ -2111,7 +2142,10 @@ class AutoregressiveFlow(torch.nn.Module):
         dev = x.device
         f64 = dict(device=dev, dtype=torch.float64)
         dp = self._blocked_f64_device_plan(dev, hp)
-        bd = self._blocked_f64_backward_device_plan(dev, hp)
+        vec = self._blocked_backward_force_vec or any(k >= 2 for k in hp['kinds'])
+        if vec and y is None:
+            raise ValueError('the blocked backward of a layer with vector-valued members needs the images y')
+        bd = self._blocked_f64_backward_device_plan(dev, hp, vec)
         made, tr = self._conditioner, self._transformer
         lins = made._linears()
         L = len(lins) - 1
@@ -2143,22 +2177,48 @@ class AutoregressiveFlow(torch.nn.Module):
         x_tr = ops.gather_columns(x, t['tr']) if self.has_fixed_indices else x
         gx_tr = ops.gather_columns(gx, t['tr']) if self.has_fixed_indices else gx
         n_tr = x_tr.shape[1]
-        A_ref, c_ref = ops.zeros(B, n_out, **f64), ops.zeros(B, n_out, **f64)
-        tau_x, lx = torch.empty(B, n_tr, **f64), torch.empty(B, n_tr, **f64)
-        _backward.transformer_vjp(tr, x_tr, theta, 0, torch.ones(B, n_tr, **f64), ops.zeros(B, **f64), A_ref, tau_x)
-        _backward.transformer_vjp(tr, x_tr, theta, 0, ops.zeros(B, n_tr, **f64), gl, c_ref, lx)
-        r_s = ops.gather_columns(gx_tr - lx, bd['slot_feature'])
-        tau_s = ops.gather_columns(tau_x, bd['slot_feature'])
-        A, c = ops.zeros(B, n_pad[L], **f64), ops.zeros(B, n_pad[L], **f64)
-        ops.scatter_columns(A_ref, dp['rows'][L], A)
-        ops.scatter_columns(c_ref, dp['rows'][L], c)
-        del theta_p, theta, A_ref, c_ref, tau_x, lx
+        scalar_members = [g for g, k in enumerate(hp['kinds']) if k < 2]
+        tau_s = A = c = None
+        if not scalar_members:                                  # vector members only: r carries gx, nothing else is read
+            r_s = ops.gather_columns(gx_tr.contiguous(), bd['slot_feature'])
+        else:
+            A_ref, c_ref = ops.zeros(B, n_out, **f64), ops.zeros(B, n_out, **f64)
+            if len(scalar_members) == len(hp['kinds']):
+                tau_x, lx = torch.empty(B, n_tr, **f64), torch.empty(B, n_tr, **f64)
+                _backward.transformer_vjp(tr, x_tr, theta, 0, torch.ones(B, n_tr, **f64), ops.zeros(B, **f64), A_ref, tau_x)
+                _backward.transformer_vjp(tr, x_tr, theta, 0, ops.zeros(B, n_tr, **f64), gl, c_ref, lx)
+            else:       # a mixed transformer: the element-wise members on their own columns and parameter blocks; what tau_x,
+                #         A and c hold at the vector members is never read, and r = gx there (lx = 0)
+                tau_x, lx = torch.empty(B, n_tr, **f64), ops.zeros(B, n_tr, **f64)
+                splits = tr.host_splits()
+                for g in scalar_members:
+                    ind = tr._indices[g].to(device=dev, dtype=torch.int32)
+                    xs = ops.gather_columns(x_tr, ind)
+                    n_g = xs.shape[1]
+                    out = torch.empty(B, n_g, **f64)
+                    _backward.transformer_vjp(hp['members'][g], xs, theta, splits[g], torch.ones(B, n_g, **f64),
+                                              ops.zeros(B, **f64), A_ref, out)
+                    ops.scatter_columns(out, ind, tau_x)
+                    out = torch.empty(B, n_g, **f64)
+                    _backward.transformer_vjp(hp['members'][g], xs, theta, splits[g], ops.zeros(B, n_g, **f64), gl, c_ref, out)
+                    ops.scatter_columns(out, ind, lx)
+            r_s = ops.gather_columns(gx_tr - lx, bd['slot_feature'])
+            tau_s = ops.gather_columns(tau_x, bd['slot_feature'])
+            A, c = ops.zeros(B, n_pad[L], **f64), ops.zeros(B, n_pad[L], **f64)
+            ops.scatter_columns(A_ref, dp['rows'][L], A)
+            ops.scatter_columns(c_ref, dp['rows'][L], c)
+            del A_ref, c_ref, tau_x, lx
+        del theta
+        if vec:
+            y_rows, ldy = _lib.rows(y.detach(), 'y', torch.float64)
+        else:
+            del theta_p
         # ---- the descending block loop
         ga = [ops.zeros(B, n_pad[l], **f64) for l in range(L + 1)]
         G = [torch.empty(B, k_pad[l], **f64) for l in range(L + 1)]
         n_slots = len(hp['feats'])
         u = torch.empty(B, n_slots, **f64)
-        for blk, d in zip(bp['blocks'], bd['descs']):
+        for blk, d, outer in zip(bp['blocks'], bd['descs'], bd['outer']):
             for l in range(L + 1):
                 (c0, c1), R = blk['cols'][l], blk['R'][l]
                 if R >= n_pad[l] or c1 <= c0:
@@ -2169,10 +2229,14 @@ class AutoregressiveFlow(torch.nn.Module):
             d.B = B
             for l in range(L + 1):
                 d.ga[l], d.wt[l], d.h[l], d.G[l] = ga[l].data_ptr(), wt[l].data_ptr(), a[l].data_ptr(), G[l].data_ptr()
-            d.r, d.tau_x, d.ldr = r_s.data_ptr(), tau_s.data_ptr(), n_slots
-            d.A, d.c, d.ldA = A.data_ptr(), c.data_ptr(), n_pad[L]
+            d.r, d.tau_x, d.ldr = r_s.data_ptr(), None if tau_s is None else tau_s.data_ptr(), n_slots
+            d.A, d.c, d.ldA = None if A is None else A.data_ptr(), None if c is None else c.data_ptr(), n_pad[L]
             d.u, d.ldu = u.data_ptr(), n_slots
-            _lib.call('tfep_inverse_backward_chain_f64', ctypes.byref(d), stream)
+            if vec:
+                outer.y, outer.ldy, outer.theta, outer.ldtheta, outer.gl = y_rows.data_ptr(), ldy, theta_p.data_ptr(), n_out, gl.data_ptr()
+                _lib.call('tfep_inverse_backward_chain_vec_f64', ctypes.byref(outer), stream)
+            else:
+                _lib.call('tfep_inverse_backward_chain_f64', ctypes.byref(d), stream)
         # ---- g_y: u at the transformed features; gx - s at the features that no step transforms
         gy = gx.clone() if self.has_fixed_indices else torch.empty(B, D, **f64)
         ops.scatter_columns(u, bd['slot_col'], gy)

@@ -5,6 +5,13 @@ memory per route.  Run on an MI355X:
 
     python tools/measure_inverse_backward_f64.py d300      # D = 300, B = 1024: inverse + backward, flag on against off
     python tools/measure_inverse_backward_f64.py d3000     # D = 3000, B = 8192: flag on only, beside forward + backward
+    python tools/measure_inverse_backward_f64.py quat256   # 256 features of quaternions, 64 degrees, B = 1024:
+    python tools/measure_inverse_backward_f64.py sym2_256  # 256 features of symmetrized Moebius 2-vectors, 128 degrees:
+                                                           #   ``blocked_inverse_backward_vectors`` on against off
+
+One shape per process (a fresh process per shape keeps one shape's kept conditioner passes out of the next one's peak), each
+under a time limit of its own, e.g. ``timeout -k 10 600 python tools/measure_inverse_backward_f64.py quat256``; ``D=128``
+in the environment halves the vector shapes.
 """
 import json
 import os
@@ -16,7 +23,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tfep_amd.nn.conditioners import generate_degrees  # noqa: E402
 from tfep_amd.nn.flows import MAF  # noqa: E402
-from tfep_amd.nn.transformers import NeuralSplineTransformer  # noqa: E402
+from tfep_amd.nn.transformers import (NeuralSplineTransformer, QuaternionProductTransformer,  # noqa: E402
+                                      SymmetrizedMoebiusTransformer)
 
 dev = torch.device('cuda')
 F64 = torch.float64
@@ -38,6 +46,33 @@ def layer_rq8(D):
         torch.set_default_dtype(old)
     assert layer.is_float64
     return layer
+
+
+def layer_vectors(D, transformer, repeats):
+    """One float64 layer of vector-valued members, default width, every vector inside one degree; all opt-ins on."""
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(F64)
+    try:
+        with torch.device(dev):
+            torch.manual_seed(0)
+            layer = MAF(generate_degrees(D, repeats=repeats), transformer=transformer, initialize_identity=False)
+    finally:
+        torch.set_default_dtype(old)
+    assert layer.is_float64
+    layer.blocked_inverse_f64_vectors = True
+    layer.blocked_inverse_backward = True
+    return layer
+
+
+def inverse_backward_vectors(layer, y0, flag):
+    def run():
+        layer.blocked_inverse_backward_vectors = flag
+        layer.zero_grad(set_to_none=True)
+        y = y0.clone().requires_grad_(True)
+        x, ldj = layer.inverse(y)
+        (x.square().sum() + ldj.sum()).backward()
+        assert layer.last_inverse_backward_route == ('blocked_f64' if flag else 'per_degree')
+    return run
 
 
 def timed(fn):
@@ -115,3 +150,21 @@ if 'd3000' in which:
            multiple_of_forward_backward=round(med['on'] / med['forward_backward'], 2),
            flag_on_peak_gib=round(peak['on'] / 2 ** 30, 2), forward_backward_peak_gib=round(peak['forward_backward'] / 2 ** 30, 2),
            all_ms=all_ms)
+
+for name, make, repeats in (('quat256', QuaternionProductTransformer, 4), ('sym2_256', lambda: SymmetrizedMoebiusTransformer(2), 2)):
+    if name not in which:
+        continue
+    D, B = int(os.environ.get('D', 256)), 1024
+    layer = layer_vectors(D, make(), repeats)
+    with torch.no_grad():                                   # images of random points: no zero vector
+        y0 = layer(torch.randn(B, D, device=dev, dtype=F64, generator=gen))[0]
+    med, all_ms, peak = alternate({'on': inverse_backward_vectors(layer, y0, True), 'off': inverse_backward_vectors(layer, y0, False)},
+                                  rounds=int(os.environ.get('ROUNDS', 5)))
+    assert layer.last_inverse_route == 'blocked_f64'
+    layer.blocked_inverse_backward_vectors = True
+    plan = layer._blocked_f64_backward_plan()
+    report(what=f'float64 inverse + backward of one {type(layer._transformer).__name__} layer, default width, '
+                'blocked_inverse_backward_vectors on against off', shape=name, D=D, n_degrees=D // repeats, batch=B,
+           block=plan['block'], n_blocks=len(plan['blocks']), flag_on_ms=round(med['on'], 3), flag_off_ms=round(med['off'], 3),
+           ratio=round(med['off'] / med['on'], 2), flag_on_peak_mib=round(peak['on'] / 2 ** 20, 1),
+           flag_off_peak_mib=round(peak['off'] / 2 ** 20, 1), all_ms=all_ms)
